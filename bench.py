@@ -11,14 +11,17 @@ A "step" is one pass of the hot path over one batch of synthetic sequences resid
 Workload = BASELINE.json configs[1]: 512 sequences x T=200, n=10 per GPU (weak scaling: N=8 is
 configs[2], 4096 sequences sharded 8 x 512 with the stat all-reduce).
 
-Extra JSON objects: `roofline` (dominant kernel vs HBM peak, duration measured live with events
-on the launch stream), at N=1 on rank 0 `cpu_baseline` (the reference's own compiled E-step,
+A plain run sets up, warms up, times the K steps and prints the line; beside the headline it carries only
+`roofline` (dominant kernel vs HBM peak, duration measured live with events on the launch stream of the
+timed steps).  `--dump-outputs DIR` also writes what the last timed step computed as DIR/<name>.npy
+(dump_outputs).  `--full` adds everything else, reported beside `value`, never instead of it: the
+`parity` gate (the timed plan's outputs against the reference's compiled E-step; the process exits
+non-zero beyond PARITY_TOL), at N=1 on rank 0 `cpu_baseline` (the reference's own compiled E-step,
 oracle/_ref, timed on this box's host cores on a bounded sample of the same workload, plus the
 NumPy restatement of its Python path), and at N=1 `extra`: the same measurement for north_star's
 single-GPU target (4096 sequences on ONE GPU) and for BASELINE configs[4]'s shape (latent dim 64,
 T=1000), each with its own roofline, plus the training path at the headline shape (E-step keeping the
-hand-off + sampler + VJP), BASELINE configs[3] (SLDS local mean field) and configs[0] (GMM fixed point)
--- reported beside `value`, never instead of it.
+hand-off + sampler + VJP), BASELINE configs[3] (SLDS local mean field) and configs[0] (GMM fixed point).
 """
 import argparse
 import json
@@ -131,9 +134,33 @@ def parity_gate(snapshot, tol=PARITY_TOL):
     return out
 
 
-def measure(dev, rank, world, dist, options, T, n, B, steps, warmup, parity=0):
+DUMP_BUDGET_BYTES = 64 << 20
+
+
+def dump_outputs(plan, out_dir, budget=DUMP_BUDGET_BYTES):
+    """What the last launch of the timed plan handed its caller -> out_dir/<name>.npy, float64: the per-sequence E-step
+    outputs (lognorm, E_init, E_pair, E_node_diagxx, E_node_x) and the batch statistics of the step (`reduced_stats`,
+    all-reduced when N > 1).  If all sequences would exceed `budget` bytes, a fixed seeded sample of them is written, the
+    same rows of every per-sequence array; `sequence_index` holds the rows written."""
+    per_seq = dict(lognorm=plan.lognorm, E_init=plan.E_init, E_pair=plan.E_pair, E_node_diagxx=plan.E_node_diagxx,
+                   E_node_x=plan.E_node_x)
+    row_bytes = 8 * sum(x[0].numel() for x in per_seq.values())
+    keep = min(plan.B, max(1, (budget - 8 * (plan.reduced.numel() + plan.B)) // row_bytes))
+    idx = np.arange(plan.B)
+    if keep < plan.B:
+        idx = np.sort(np.random.default_rng(0).choice(plan.B, keep, replace=False))
+    ix = torch.as_tensor(idx, device=plan.device)
+    os.makedirs(out_dir, exist_ok=True)
+    for name, x in per_seq.items():
+        np.save(os.path.join(out_dir, name + ".npy"), x.index_select(0, ix).cpu().numpy())
+    np.save(os.path.join(out_dir, "reduced_stats.npy"), plan.reduced.cpu().numpy())
+    np.save(os.path.join(out_dir, "sequence_index.npy"), idx.astype(np.float64))
+
+
+def measure(dev, rank, world, dist, options, T, n, B, steps, warmup, parity=0, dump=None):
     """W untimed + K timed steps of the hot path on B sequences per GPU -> (elapsed s [max over ranks],
-    mean kernel ms from events on the launch stream[, parity snapshot of the timed plan's outputs])."""
+    mean kernel ms from events on the launch stream[, parity snapshot of the timed plan's outputs]).
+    dump: directory for dump_outputs of rank 0's plan after the timed steps, or None."""
     from svae_amd.lds.lds_inference import LDSEStepPlan
     from svae_amd.lds.synthetic_data import rand_node_potentials
     from svae_amd.parallel import allreduce_global_stats
@@ -186,6 +213,8 @@ def measure(dev, rank, world, dist, options, T, n, B, steps, warmup, parity=0):
         dist.all_reduce(el, op=dist.ReduceOp.MAX)
         elapsed = float(el.item())
     kern_ms = sum(a.elapsed_time(b) for a, b in ev) / max(1, steps)
+    if dump and rank == 0:
+        dump_outputs(plan, dump)
     if parity:
         return elapsed, kern_ms, snapshot_for_parity(plan, (init, pair), d_J, d_h, parity)
     return elapsed, kern_ms
@@ -537,8 +566,13 @@ def main():
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--workload", choices=sorted(WORKLOADS), default="lds10")
     ap.add_argument("--seqs-per-gpu", type=int, default=None)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extra", action="store_true", help="skip the extra single-GPU configurations")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: the parity gate against the reference, the CPU baseline and the extra "
+                         "single-GPU configurations (a plain run times the headline only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed as DIR/<name>.npy (float64, rank 0)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-extra", action="store_true", help="with --full: skip the extra single-GPU configurations")
     ap.add_argument("--kernel", choices=["auto", "twoend", "twoend_full", "split", "packed"], default="auto",
                     help="A/B measurements: force one of the E-step kernels (n <= 15)")
     ap.add_argument("--launch-check", action="store_true",
@@ -617,7 +651,9 @@ def main():
     T, n, B = WORKLOADS[args.workload]
     B = args.seqs_per_gpu or B
 
-    elapsed, kern_ms, snap = measure(dev, rank, world, dist, options, T, n, B, args.steps, args.warmup, parity=PARITY_SEQUENCES)
+    timed = measure(dev, rank, world, dist, options, T, n, B, args.steps, args.warmup,
+                    parity=PARITY_SEQUENCES if args.full else 0, dump=args.dump_outputs)
+    elapsed, kern_ms = timed[:2]
     parity_failed = False
 
     if rank == 0:
@@ -642,13 +678,14 @@ def main():
         # parity gate: PARITY_SEQUENCES sequences of the batch just timed (rank 0's shard), as the
         # timed plan left them, against the reference's compiled E-step -- the line carries the distance, and the
         # process exits non-zero beyond PARITY_TOL
-        try:
-            out["parity"] = parity_gate(snap)
-            parity_failed = not out["parity"]["ok"]
-        except Exception as e:
-            out["parity"] = {"error": repr(e)[:300], "ok": False}
-            parity_failed = True
-        if world == 1 and not args.no_extra and args.workload == "lds10" and args.seqs_per_gpu is None:
+        if args.full:
+            try:
+                out["parity"] = parity_gate(timed[2])
+                parity_failed = not out["parity"]["ok"]
+            except Exception as e:
+                out["parity"] = {"error": repr(e)[:300], "ok": False}
+                parity_failed = True
+        if args.full and world == 1 and not args.no_extra and args.workload == "lds10" and args.seqs_per_gpu is None:
             # the other single-GPU configurations BASELINE.json names, same measurement, fewer steps
             extra = []
             for (eT, en, eB, esteps, what) in ((200, 10, 4096, max(5, args.steps // 2),
@@ -687,7 +724,7 @@ def main():
                     extra.append({"error": repr(e)})
                 torch.cuda.empty_cache()
             out["extra"] = extra
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             try:
                 out["cpu_baseline"] = cpu_baseline(B, T, n)
                 out["speedup_vs_cpu_baseline"] = out["value"] / out["cpu_baseline"]["value"]
