@@ -25,7 +25,7 @@
 extern "C" {
 #endif
 
-#define SVAE_HIP_ABI_VERSION 14   /* 14: + svae_lds_estep_vjp_dense_f64 (cotangent of dense node potentials), svae_hmm_* up to K = 64, svae_lds_inference_f64 (E-step + sampler in one call; lean per-step records for large homogeneous batches), svae_lds_inference_is_lean, SVAE_OPT_LEAN_ON / _OFF / SVAE_OPT_INFER_RECORDS; 13: + svae_slds_pair_contract_f64 (the two contractions of the SLDS final pass over the per-step pair statistics in one pass); 12: svae_gmm_global_step_f64 writes kl[0..1] (as spelled | as shipped), svae_ipc_allreduce_f64 takes the mailbox stride and never writes `out` on a timeout, + svae_slds_lds_meanfield options; 11: + svae_lds_global_step_multi_f64 (K parameter sets in one launch: the SLDS global -> local maps), svae_lds_diag_sample_f64 (filter + sampler of an all-diagonal LDS: the SLDS initial path); 10: + svae_ipc_allreduce_f64 / svae_ipc_mailbox_bytes, svae_gmm_sample_f64, svae_gmm_local_vjp_f64, svae_gmm_global_step_f64 (the differentiable tail and the global side of the GMM local step); 9: keep bit SVAE_KEEP_SIGMA of svae_lds_estep_f64 (16 <= n <= 64) + svae_lds_tile_sigma_offset_bytes; 8: step ranges (t_begin, t_end) in svae_lds_tile_vjp_f64 / svae_lds_tile_noise_f64, SVAE_OPT_TILE_FORWARD / _BACKWARD; 7: + svae_slds_path_nodeparams_f64, svae_slds_mix_pair_natparam_f64; 6: per-call `options` word replaces the process-global svae_lds_set_* selectors (re-entrant library), + svae_slds_hmm_meanfield_f64, svae_slds_sweep_glue_f64, g_E_pair in svae_lds_tile_vjp_f64; 5: + svae_lds_set_prod_max_b; 4: + svae_slds_lds_meanfield_f64, svae_gmm_mw_*, svae_lds_global_step_f64, svae_lds_natgrad_f64, svae_lds_tile_vjp_f64; 2: + svae_lds_workspace_bytes_ex, svae_lds_estep_vjp_ex_f64, svae_hmm_*, tiled path (n <= 64) */
+#define SVAE_HIP_ABI_VERSION 15   /* 15: + svae_lds_filter_vjp_f64, svae_lds_smoother_vjp_f64 (+ svae_lds_smoother_vjp_workspace_bytes), svae_lds_sample_vjp_f64 (the reference's three reverse-mode primitives on caller-held forward messages); 14: + svae_lds_estep_vjp_dense_f64 (cotangent of dense node potentials), svae_hmm_* up to K = 64, svae_lds_inference_f64 (E-step + sampler in one call; lean per-step records for large homogeneous batches), svae_lds_inference_is_lean, SVAE_OPT_LEAN_ON / _OFF / SVAE_OPT_INFER_RECORDS; 13: + svae_slds_pair_contract_f64 (the two contractions of the SLDS final pass over the per-step pair statistics in one pass); 12: svae_gmm_global_step_f64 writes kl[0..1] (as spelled | as shipped), svae_ipc_allreduce_f64 takes the mailbox stride and never writes `out` on a timeout, + svae_slds_lds_meanfield options; 11: + svae_lds_global_step_multi_f64 (K parameter sets in one launch: the SLDS global -> local maps), svae_lds_diag_sample_f64 (filter + sampler of an all-diagonal LDS: the SLDS initial path); 10: + svae_ipc_allreduce_f64 / svae_ipc_mailbox_bytes, svae_gmm_sample_f64, svae_gmm_local_vjp_f64, svae_gmm_global_step_f64 (the differentiable tail and the global side of the GMM local step); 9: keep bit SVAE_KEEP_SIGMA of svae_lds_estep_f64 (16 <= n <= 64) + svae_lds_tile_sigma_offset_bytes; 8: step ranges (t_begin, t_end) in svae_lds_tile_vjp_f64 / svae_lds_tile_noise_f64, SVAE_OPT_TILE_FORWARD / _BACKWARD; 7: + svae_slds_path_nodeparams_f64, svae_slds_mix_pair_natparam_f64; 6: per-call `options` word replaces the process-global svae_lds_set_* selectors (re-entrant library), + svae_slds_hmm_meanfield_f64, svae_slds_sweep_glue_f64, g_E_pair in svae_lds_tile_vjp_f64; 5: + svae_lds_set_prod_max_b; 4: + svae_slds_lds_meanfield_f64, svae_gmm_mw_*, svae_lds_global_step_f64, svae_lds_natgrad_f64, svae_lds_tile_vjp_f64; 2: + svae_lds_workspace_bytes_ex, svae_lds_estep_vjp_ex_f64, svae_hmm_*, tiled path (n <= 64) */
 #define SVAE_HMM_MAX_K 64   /* svae_hmm_estep_f64 / svae_slds_hmm_meanfield_f64: K <= 16 one DPP row per sequence; 17 <= K <= 64 one wavefront per sequence (round 6) */
 #define SVAE_LDS_MAX_N 15   /* register/DPP path: one 16-lane row per sequence, n+1 <= 16 */
 #define SVAE_LDS_TILE_MAX_N 64   /* 16 <= n <= 64: LDS-tiled MFMA path (keep: SVAE_KEEP_SIGMA or 0) */
@@ -582,6 +582,59 @@ int svae_gmm_local_vjp_f64(int T, int N, int K, int S, const double* label_globa
 size_t svae_ipc_mailbox_bytes(int capacity, int world);
 int svae_ipc_allreduce_f64(int n, int capacity, int rank, int world, unsigned epoch, unsigned spin_limit,
                            const double* in, double* out, void* const* mailboxes, int32_t* info, void* stream);
+
+/* ---- The reference's three reverse-mode primitives, on caller-held forward messages (n <= SVAE_LDS_MAX_N) ----
+ * Each differentiates the reference's recursion as a function of the forward messages (J_pred, h_pred, J_filt, h_filt)
+ * (B,T,n,n) / (B,T,n) -- natural scaling, J = -1/2 precision, as svae_lds_filter_f64 writes them -- and rebuilds every
+ * per-step factor from them (no record of an earlier call).  Pair parameters J11, J12, J22 as in svae_lds_estep_f64:
+ * (n,n), per step (T-1,n,n) with inhomog, per sequence and step (B,T-1,n,n) with pair_batched.  All cotangents in the
+ * reference's scaling and index order.  info (int32, may be NULL): bit 0 is OR-ed in when a pivot is not positive
+ * definite.  Return values: 0; -1 B < 0; -2 T < 1; -3 n outside 1..SVAE_LDS_MAX_N; -4 bad S; -5 NULL pair parameter
+ * (T > 1); -6 NULL message; -7 pair_batched without inhomog; -8 NULL required cotangent input; -9 NULL output;
+ * -14 workspace NULL or too small; -1000 launch error.  Arguments are checked before any HIP call. */
+
+/* natural_filter_grad (/root/reference/svae/lds/cython_lds_inference.pyx:92-145, helpers
+ * cython_gaussian_grads.pxd:17-206): the cotangent of the node potentials given cotangents of the filter's outputs.
+ *  in : J11, J12; J_filt, h_filt; g_J_pred, g_J_filt (B,T,n,n), g_h_pred, g_h_filt (B,T,n), g_lognorm (B)
+ *  out: g_node_J (B,T,n) (diagonal node potentials), g_node_h (B,T,n), g_node_logZ (B,T) */
+int svae_lds_filter_vjp_f64(int B, int T, int n, int inhomog, int pair_batched,
+                            const double* J11, const double* J12,
+                            const double* J_filt, const double* h_filt,
+                            const double* g_J_pred, const double* g_h_pred,
+                            const double* g_J_filt, const double* g_h_filt, const double* g_lognorm,
+                            double* g_node_J, double* g_node_h, double* g_node_logZ,
+                            int32_t* info, void* stream);
+
+/* Bytes of workspace svae_lds_smoother_vjp_f64 needs: B * T * (3 n^2 + 2 n) * 8 (per sequence-step the smoothed
+ * Js, Cov[x_t], E[x_t+1 x_t'] and hs, E[x_t] of the RTS recursion); 0 for invalid sizes. */
+size_t svae_lds_smoother_vjp_workspace_bytes(int B, int T, int n);
+
+/* natural_smoother_general_grad (/root/reference/svae/lds/cython_lds_inference.pyx:236-306, _compute_stats_grad :212-234,
+ * helpers cython_gaussian_grads.pxd:208-430): cotangents of the four message arrays given cotangents of the statistics.
+ *  in : J11, J12, J22; the four messages; each of g_E_init (B, n*n+n) [E[x0 x0'] | E[x0]], g_E_pair ((B,3,n,n) for
+ *       homogeneous pair parameters -- the summed statistics -- else (B,T-1,3,n,n)), g_E_node_diagxx, g_E_node_x (B,T,n)
+ *       may be NULL (zero)
+ *  out: g_J_pred, g_J_filt (B,T,n,n), g_h_pred, g_h_filt (B,T,n); g_J_pred[:,0] = g_h_pred[:,0] = 0 */
+int svae_lds_smoother_vjp_f64(int B, int T, int n, int inhomog, int pair_batched,
+                              const double* J11, const double* J12, const double* J22,
+                              const double* J_pred, const double* h_pred,
+                              const double* J_filt, const double* h_filt,
+                              const double* g_E_init, const double* g_E_pair,
+                              const double* g_E_node_diagxx, const double* g_E_node_x,
+                              double* g_J_pred, double* g_h_pred, double* g_J_filt, double* g_h_filt,
+                              int32_t* info, void* workspace, size_t ws_bytes, void* stream);
+
+/* natural_sample_backward_grad (/root/reference/svae/lds/cython_lds_inference.pyx:357-409, helpers
+ * cython_gaussian_grads.pxd:456-530): cotangents of the messages given the cotangent of the samples.
+ *  in : J11, J12; J_filt, h_filt; eps, samples, g_samples (B,T,S,n) with eps[:,t] the noise applied at step t, 1 <= S <= 16
+ *       (larger S: -4)
+ *  out: g_J_filt (B,T,n,n), g_h_filt (B,T,n); g_J_pred, g_h_pred written with zeros */
+int svae_lds_sample_vjp_f64(int B, int T, int n, int S, int inhomog, int pair_batched,
+                            const double* J11, const double* J12,
+                            const double* J_filt, const double* h_filt,
+                            const double* eps, const double* samples, const double* g_samples,
+                            double* g_J_pred, double* g_h_pred, double* g_J_filt, double* g_h_filt,
+                            int32_t* info, void* stream);
 
 #ifdef __cplusplus
 }

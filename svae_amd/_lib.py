@@ -12,7 +12,7 @@ import torch  # noqa: F401  (must precede CDLL: shares torch's HIP runtime)
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("SVAE_AMD_LIB", os.path.join(_HERE, "libsvae_hip.so"))  # env: experiments only
 
-ABI_VERSION = 14
+ABI_VERSION = 15
 LDS_MAX_N = 15        # register/DPP path (E-step, sampler, VJP)
 LDS_TILE_MAX_N = 64   # LDS-tiled MFMA path (E-step only)
 
@@ -101,6 +101,11 @@ SIGNATURES = {
     "svae_gmm_global_step_f64": (ctypes.c_int, [ctypes.c_int] * 2 + [_c_double_p] * 7 + [_c_int_p, ctypes.c_void_p]),
     "svae_gmm_sample_f64": (ctypes.c_int, [ctypes.c_int] * 3 + [_c_double_p] * 3 + [ctypes.c_void_p]),
     "svae_gmm_local_vjp_f64": (ctypes.c_int, [ctypes.c_int] * 4 + [_c_double_p] * 11 + [ctypes.c_void_p]),
+    "svae_lds_filter_vjp_f64": (ctypes.c_int, [ctypes.c_int] * 5 + [_c_double_p] * 12 + [_c_int_p, ctypes.c_void_p]),
+    "svae_lds_smoother_vjp_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int] * 3),
+    "svae_lds_smoother_vjp_f64": (ctypes.c_int, [ctypes.c_int] * 5 + [_c_double_p] * 15
+                                  + [_c_int_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]),
+    "svae_lds_sample_vjp_f64": (ctypes.c_int, [ctypes.c_int] * 6 + [_c_double_p] * 11 + [_c_int_p, ctypes.c_void_p]),
     "svae_gmm_mw_fixed_point_f64": (ctypes.c_int, [ctypes.c_int] * 3 + [_c_double_p] * 5
                                     + [ctypes.c_double, ctypes.c_int] + [_c_double_p] * 8
                                     + [_c_int_p] * 3 + [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]),
