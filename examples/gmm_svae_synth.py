@@ -4,7 +4,9 @@ experiments/gmm_svae_synth.py (svae/svae.py:10-39 `make_gradfun` + SGD / natural
 2-D latents, minibatches of 50 points) with the whole structured side -- global maps, mean-field fixed point, final
 pass, sampler and the reverse pass -- running in the HIP kernels (svae_amd/models/gmm.py).
 
-  python examples/gmm_svae_synth.py [--iters 200] [--K 15] [--batch 50]
+  python examples/gmm_svae_synth.py [--iters 200] [--K 15] [--batch 50] [--latent-dim 2]
+
+--latent-dim up to 16 (9 .. 16 run the row-per-point kernels of csrc/gmm_wide.hip).
 
 Recognition network and decoder are small torch MLPs on svae_amd.nnet (the reference's gresnets, svae/nnet.py, are out
 of this library's scope).  Prints the Monte-Carlo ELBO estimate per iteration and, at the end, how many components
@@ -49,12 +51,13 @@ def main(argv=None):
     ap.add_argument("--per-cluster", type=int, default=100)
     ap.add_argument("--batch", type=int, default=50)
     ap.add_argument("--lr", type=float, default=1e-3)
+    ap.add_argument("--latent-dim", type=int, default=2, help="N, the latent dimension (1 .. 16)")
     ap.add_argument("--quiet", action="store_true")
     args = ap.parse_args(argv)
     dev = torch.device("cuda:0")
     gen = torch.Generator(device=dev).manual_seed(1)
     cpu_gen = torch.Generator().manual_seed(1)
-    K, N, P = args.K, 2, 2
+    K, N, P = args.K, args.latent_dim, 2
     data = torch.as_tensor(pinwheel(0.3, 0.05, args.clusters, args.per_cluster, 0.25, np.random.default_rng(1)), device=dev)
 
     to = lambda s: tuple(x.to(dev) for x in s)

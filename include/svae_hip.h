@@ -25,7 +25,7 @@
 extern "C" {
 #endif
 
-#define SVAE_HIP_ABI_VERSION 15   /* 15: + svae_lds_filter_vjp_f64, svae_lds_smoother_vjp_f64 (+ svae_lds_smoother_vjp_workspace_bytes), svae_lds_sample_vjp_f64 (the reference's three reverse-mode primitives on caller-held forward messages); 14: + svae_lds_estep_vjp_dense_f64 (cotangent of dense node potentials), svae_hmm_* up to K = 64, svae_lds_inference_f64 (E-step + sampler in one call; lean per-step records for large homogeneous batches), svae_lds_inference_is_lean, SVAE_OPT_LEAN_ON / _OFF / SVAE_OPT_INFER_RECORDS; 13: + svae_slds_pair_contract_f64 (the two contractions of the SLDS final pass over the per-step pair statistics in one pass); 12: svae_gmm_global_step_f64 writes kl[0..1] (as spelled | as shipped), svae_ipc_allreduce_f64 takes the mailbox stride and never writes `out` on a timeout, + svae_slds_lds_meanfield options; 11: + svae_lds_global_step_multi_f64 (K parameter sets in one launch: the SLDS global -> local maps), svae_lds_diag_sample_f64 (filter + sampler of an all-diagonal LDS: the SLDS initial path); 10: + svae_ipc_allreduce_f64 / svae_ipc_mailbox_bytes, svae_gmm_sample_f64, svae_gmm_local_vjp_f64, svae_gmm_global_step_f64 (the differentiable tail and the global side of the GMM local step); 9: keep bit SVAE_KEEP_SIGMA of svae_lds_estep_f64 (16 <= n <= 64) + svae_lds_tile_sigma_offset_bytes; 8: step ranges (t_begin, t_end) in svae_lds_tile_vjp_f64 / svae_lds_tile_noise_f64, SVAE_OPT_TILE_FORWARD / _BACKWARD; 7: + svae_slds_path_nodeparams_f64, svae_slds_mix_pair_natparam_f64; 6: per-call `options` word replaces the process-global svae_lds_set_* selectors (re-entrant library), + svae_slds_hmm_meanfield_f64, svae_slds_sweep_glue_f64, g_E_pair in svae_lds_tile_vjp_f64; 5: + svae_lds_set_prod_max_b; 4: + svae_slds_lds_meanfield_f64, svae_gmm_mw_*, svae_lds_global_step_f64, svae_lds_natgrad_f64, svae_lds_tile_vjp_f64; 2: + svae_lds_workspace_bytes_ex, svae_lds_estep_vjp_ex_f64, svae_hmm_*, tiled path (n <= 64) */
+#define SVAE_HIP_ABI_VERSION 15   /* 15: + svae_gmm_wide_mw_workspace_bytes, svae_gmm_wide_mw_begin, svae_gmm_wide_mw_step_f64, svae_gmm_wide_sample_f64, svae_gmm_wide_local_vjp_f64, svae_gmm_wide_global_step_f64 (the GMM local step for N <= 16; additions only), svae_lds_filter_vjp_f64, svae_lds_smoother_vjp_f64 (+ svae_lds_smoother_vjp_workspace_bytes), svae_lds_sample_vjp_f64 (the reference's three reverse-mode primitives on caller-held forward messages); 14: + svae_lds_estep_vjp_dense_f64 (cotangent of dense node potentials), svae_hmm_* up to K = 64, svae_lds_inference_f64 (E-step + sampler in one call; lean per-step records for large homogeneous batches), svae_lds_inference_is_lean, SVAE_OPT_LEAN_ON / _OFF / SVAE_OPT_INFER_RECORDS; 13: + svae_slds_pair_contract_f64 (the two contractions of the SLDS final pass over the per-step pair statistics in one pass); 12: svae_gmm_global_step_f64 writes kl[0..1] (as spelled | as shipped), svae_ipc_allreduce_f64 takes the mailbox stride and never writes `out` on a timeout, + svae_slds_lds_meanfield options; 11: + svae_lds_global_step_multi_f64 (K parameter sets in one launch: the SLDS global -> local maps), svae_lds_diag_sample_f64 (filter + sampler of an all-diagonal LDS: the SLDS initial path); 10: + svae_ipc_allreduce_f64 / svae_ipc_mailbox_bytes, svae_gmm_sample_f64, svae_gmm_local_vjp_f64, svae_gmm_global_step_f64 (the differentiable tail and the global side of the GMM local step); 9: keep bit SVAE_KEEP_SIGMA of svae_lds_estep_f64 (16 <= n <= 64) + svae_lds_tile_sigma_offset_bytes; 8: step ranges (t_begin, t_end) in svae_lds_tile_vjp_f64 / svae_lds_tile_noise_f64, SVAE_OPT_TILE_FORWARD / _BACKWARD; 7: + svae_slds_path_nodeparams_f64, svae_slds_mix_pair_natparam_f64; 6: per-call `options` word replaces the process-global svae_lds_set_* selectors (re-entrant library), + svae_slds_hmm_meanfield_f64, svae_slds_sweep_glue_f64, g_E_pair in svae_lds_tile_vjp_f64; 5: + svae_lds_set_prod_max_b; 4: + svae_slds_lds_meanfield_f64, svae_gmm_mw_*, svae_lds_global_step_f64, svae_lds_natgrad_f64, svae_lds_tile_vjp_f64; 2: + svae_lds_workspace_bytes_ex, svae_lds_estep_vjp_ex_f64, svae_hmm_*, tiled path (n <= 64) */
 #define SVAE_HMM_MAX_K 64   /* svae_hmm_estep_f64 / svae_slds_hmm_meanfield_f64: K <= 16 one DPP row per sequence; 17 <= K <= 64 one wavefront per sequence (round 6) */
 #define SVAE_LDS_MAX_N 15   /* register/DPP path: one 16-lane row per sequence, n+1 <= 16 */
 #define SVAE_LDS_TILE_MAX_N 64   /* 16 <= n <= 64: LDS-tiled MFMA path (keep: SVAE_KEEP_SIGMA or 0) */
@@ -566,6 +566,40 @@ int svae_gmm_local_vjp_f64(int T, int N, int K, int S, const double* label_globa
                            const double* gaussian_natparam, const double* label_natparam,
                            const double* g_kl, const double* eps, const double* g_samples,
                            double* g_node_J, double* g_node_h, void* stream);
+
+/* ---- GMM-SVAE local step for latent dimensions up to 16 (csrc/gmm_wide.hip) ---------------------------------------
+ * One 16-lane row per point (lane i: row i of the point's J, Sigma, E[x x'] and Cholesky factor), the K <= 64
+ * responsibilities spread over the row.  Each entry takes the argument list of its N <= 8 counterpart above, accepts
+ * 1 <= N <= 16 (so it can be checked against the N <= 8 kernels) and returns the same code for the same bad argument;
+ * an N outside 1..16 gets the counterpart's code for N > 8.  Arguments are checked before any HIP call.
+ *   svae_gmm_wide_mw_workspace_bytes / _mw_begin / _mw_step_f64   the per-sweep fixed point of svae_gmm_mw_*: phase 0
+ *       sweep `sweep`, phase 1 the final pass, phase 2 the global statistics; kl_hist stays at the start of the
+ *       workspace (svae_gmm_mw_kl_hist applies), sweeps after the stopping rule fired are device-side no-ops.
+ *   svae_gmm_wide_sample_f64      as svae_gmm_sample_f64.
+ *   svae_gmm_wide_local_vjp_f64   as svae_gmm_local_vjp_f64 (two launches when g_samples is given).
+ *   svae_gmm_wide_global_step_f64 as svae_gmm_global_step_f64 (one row per component). */
+size_t svae_gmm_wide_mw_workspace_bytes(int T, int N, int K, int max_iter);
+int svae_gmm_wide_mw_begin(int T, int N, int K, int max_iter, void* workspace, size_t ws_bytes, void* stream);
+int svae_gmm_wide_mw_step_f64(int phase, int sweep, int T, int N, int K,
+                              const double* label_global, const double* gaussian_globals,
+                              const double* node_J, const double* node_h,
+                              const double* label_init, double tol, int max_iter,
+                              double* label_stats, double* label_fixed, double* gaussian_stats,
+                              double* label_natparam, double* gaussian_natparam,
+                              double* dirichlet_stats, double* niw_stats,
+                              double* kl, int32_t* iters, int32_t* assign, int32_t* info,
+                              void* workspace, size_t ws_bytes, void* stream);
+int svae_gmm_wide_sample_f64(int T, int N, int S, const double* gaussian_natparam, const double* eps,
+                             double* samples, void* stream);
+int svae_gmm_wide_local_vjp_f64(int T, int N, int K, int S, const double* label_global,
+                                const double* gaussian_globals, const double* node_J, const double* node_h,
+                                const double* gaussian_natparam, const double* label_natparam,
+                                const double* g_kl, const double* eps, const double* g_samples,
+                                double* g_node_J, double* g_node_h, void* stream);
+int svae_gmm_wide_global_step_f64(int K, int N, const double* dirichlet_natparam, const double* niw_natparam,
+                                  const double* prior_dirichlet, const double* prior_niw,
+                                  double* label_global, double* gaussian_globals, double* kl, int32_t* info,
+                                  void* stream);
 
 
 /* ---- one-shot all-reduce of a small buffer over IPC-mapped mailboxes (csrc/ipc_allreduce.hip) -----------------------

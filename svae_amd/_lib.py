@@ -106,6 +106,15 @@ SIGNATURES = {
     "svae_lds_smoother_vjp_f64": (ctypes.c_int, [ctypes.c_int] * 5 + [_c_double_p] * 15
                                   + [_c_int_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]),
     "svae_lds_sample_vjp_f64": (ctypes.c_int, [ctypes.c_int] * 6 + [_c_double_p] * 11 + [_c_int_p, ctypes.c_void_p]),
+    "svae_gmm_wide_mw_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int] * 4),
+    "svae_gmm_wide_mw_begin": (ctypes.c_int, [ctypes.c_int] * 4 + [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]),
+    "svae_gmm_wide_mw_step_f64": (ctypes.c_int, [ctypes.c_int] * 5 + [_c_double_p] * 5
+                                  + [ctypes.c_double, ctypes.c_int] + [_c_double_p] * 8
+                                  + [_c_int_p] * 3 + [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]),
+    "svae_gmm_wide_sample_f64": (ctypes.c_int, [ctypes.c_int] * 3 + [_c_double_p] * 3 + [ctypes.c_void_p]),
+    "svae_gmm_wide_local_vjp_f64": (ctypes.c_int, [ctypes.c_int] * 4 + [_c_double_p] * 11 + [ctypes.c_void_p]),
+    "svae_gmm_wide_global_step_f64": (ctypes.c_int, [ctypes.c_int] * 2 + [_c_double_p] * 7
+                                      + [_c_int_p, ctypes.c_void_p]),
     "svae_gmm_mw_fixed_point_f64": (ctypes.c_int, [ctypes.c_int] * 3 + [_c_double_p] * 5
                                     + [ctypes.c_double, ctypes.c_int] + [_c_double_p] * 8
                                     + [_c_int_p] * 3 + [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]),

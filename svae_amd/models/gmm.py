@@ -17,6 +17,8 @@ from .. import _lib
 from ..distributions import expfam
 
 GMM_MAX_N, GMM_MAX_K = 8, 64
+# 9 <= N <= 16: the row-per-point kernels of csrc/gmm_wide.hip (svae_gmm_wide_*), one launch per sweep
+GMM_WIDE_MAX_N = 16
 
 
 def _dev64(x, device):
@@ -57,32 +59,36 @@ def run_sweeps(backend, max_iter, group=None):
 
 
 class _HipSweeps(object):
-    """run_sweeps backend on libsvae_hip.so (svae_gmm_mw_begin / svae_gmm_mw_step_f64)."""
+    """run_sweeps backend on libsvae_hip.so: the entry set `prefix` is svae_gmm_mw (N <= 8: begin / step_f64 /
+    workspace_bytes) or svae_gmm_wide_mw (N <= 16, csrc/gmm_wide.hip) -- the same protocol and argument lists."""
 
-    def __init__(self, lib, dims, tensors, out, tol, max_iter, dev):
+    def __init__(self, lib, dims, tensors, out, tol, max_iter, dev, prefix="svae_gmm_mw"):
         self.lib, self.dims, self.t, self.out = lib, dims, tensors, out
         self.tol, self.max_iter, self.dev = float(tol), int(max_iter), dev
+        self.prefix = prefix
+        self._begin = getattr(lib, prefix + "_begin")
+        self._step_fn = getattr(lib, prefix + "_step_f64")
         T, N, K = dims
-        self.ws_bytes = int(lib.svae_gmm_mw_workspace_bytes(T, N, K, self.max_iter))
+        self.ws_bytes = int(getattr(lib, prefix + "_workspace_bytes")(T, N, K, self.max_iter))
         self.ws = torch.empty((self.ws_bytes + 7) // 8, dtype=torch.float64, device=dev)
         self.kl_hist = self.ws[:self.max_iter + 1]
 
     def begin(self):
         T, N, K = self.dims
-        _lib.check(self.lib.svae_gmm_mw_begin(T, N, K, self.max_iter, _lib.ptr(self.ws), self.ws_bytes,
-                                              _lib.current_stream(self.dev)), "svae_gmm_mw_begin")
+        _lib.check(self._begin(T, N, K, self.max_iter, _lib.ptr(self.ws), self.ws_bytes,
+                               _lib.current_stream(self.dev)), self.prefix + "_begin")
 
     def _step(self, phase, sweep):
         T, N, K = self.dims
         p, o = _lib.ptr, self.out
         lg, gg, nJ, nh, li = self.t
-        rc = self.lib.svae_gmm_mw_step_f64(
+        rc = self._step_fn(
             phase, sweep, T, N, K, p(lg), p(gg), p(nJ), p(nh), p(li), self.tol, self.max_iter,
             p(o["label_stats"]), p(o["label_fixed"]), p(o["gaussian_stats"]), p(o["label_natparam"]),
             p(o["gaussian_natparam"]), p(o["dirichlet_stats"]), p(o["niw_stats"]),
             p(o["kl"]), p(o["iters"]), p(o["assign"]), p(o["info"]), p(self.ws), self.ws_bytes,
             _lib.current_stream(self.dev))
-        _lib.check(rc, "svae_gmm_mw_step_f64")
+        _lib.check(rc, self.prefix + "_step_f64")
 
     def sweep(self, i):
         self._step(0, i)
@@ -95,13 +101,17 @@ class _HipSweeps(object):
 
 
 def meanfield_from_globals(label_global, gaussian_globals, node_potentials, label_init,
-                           tol=1e-3, max_iter=100, check=True, multi_wg=None, group=None, persistent=True):
+                           tol=1e-3, max_iter=100, check=True, multi_wg=None, group=None, persistent=True, wide=None):
     """The kernel call: everything after gmm.py:68.  Returns a dict of device tensors.
 
     multi_wg=None picks the single-workgroup, single-launch kernel for small minibatches and the
     multi-workgroup sweeps (svae_gmm_mw_*) above GMM_SINGLE_WG_MAX_T points or when the points are sharded
     over the ranks of `group` (then T is this rank's share, the stopping rule runs on the all-reduced KL and
-    `kl` / the statistics returned are this rank's: run_inference sums them)."""
+    `kl` / the statistics returned are this rank's: run_inference sums them).
+
+    9 <= N <= 16 (or wide=True, any N <= 16: a cross-check of the two kernel families) runs the row-per-point sweeps of
+    csrc/gmm_wide.hip, one launch per sweep: out["path"] == "wide_sweeps".  There is no single-workgroup form of those:
+    multi_wg=False with N > 8 raises."""
     import torch.distributed as dist
     lib = _lib.load()
     dev = gaussian_globals.device if isinstance(gaussian_globals, torch.Tensor) and \
@@ -115,8 +125,15 @@ def meanfield_from_globals(label_global, gaussian_globals, node_potentials, labe
     D = N + 2
     if tuple(gg.shape) != (K, D, D):
         raise ValueError("gaussian_globals must be (K, N+2, N+2)")
-    if not (1 <= N <= GMM_MAX_N and 1 <= K <= GMM_MAX_K):
-        raise ValueError("GMM kernel limits: N <= %d, K <= %d" % (GMM_MAX_N, GMM_MAX_K))
+    if not (1 <= N <= GMM_WIDE_MAX_N and 1 <= K <= GMM_MAX_K):
+        raise ValueError("GMM kernel limits: N <= %d, K <= %d" % (GMM_WIDE_MAX_N, GMM_MAX_K))
+    if wide is None:
+        wide = N > GMM_MAX_N
+    if not wide and N > GMM_MAX_N:
+        raise ValueError("GMM kernel limits: N <= %d for the N <= 8 kernels (wide=False)" % GMM_MAX_N)
+    if wide and multi_wg is False:
+        raise ValueError("the GMM kernels for N <= %d (csrc/gmm_wide.hip) have no single-workgroup form: "
+                         "multi_wg=False is not available at N = %d" % (GMM_WIDE_MAX_N, N))
     li = _dev64(label_init, dev)
     if tuple(li.shape) != (T, K):
         raise ValueError("label_init must be (T, K)")
@@ -134,7 +151,12 @@ def meanfield_from_globals(label_global, gaussian_globals, node_potentials, labe
         multi_wg = sharded or T > GMM_SINGLE_WG_MAX_T
     if sharded and not multi_wg:
         raise ValueError("sharded points need the multi-workgroup sweeps (batch-total stopping rule)")
-    if multi_wg:
+    if wide:
+        # one launch per sweep (svae_gmm_wide_mw_*), on one GPU or with the points sharded over ranks
+        be = _HipSweeps(lib, (T, N, K), (lg, gg, nJ, nh, li), out, tol, max_iter, dev, prefix="svae_gmm_wide_mw")
+        out["path"] = "wide_sweeps"
+        run_sweeps(be, int(max_iter), group)
+    elif multi_wg:
         be = _HipSweeps(lib, (T, N, K), (lg, gg, nJ, nh, li), out, tol, max_iter, dev)
         want_persistent = not sharded and persistent and T <= GMM_PERSISTENT_MAX_T
         out["path"] = "sweeps"
@@ -203,8 +225,9 @@ def global_step(global_natparam, prior_natparam=None, info=None, reference_compa
             dev = x.device
     dn, nn_ = _dev64(global_natparam[0], dev), _dev64(global_natparam[1], dev)
     K, N = dn.shape[0], nn_.shape[-1] - 2
-    if tuple(nn_.shape) != (K, N + 2, N + 2) or not (1 <= N <= GMM_MAX_N and 1 <= K <= GMM_MAX_K):
-        raise ValueError("GMM global parameters: dirichlet (K), NIW (K, N+2, N+2) with N <= %d, K <= %d" % (GMM_MAX_N, GMM_MAX_K))
+    if tuple(nn_.shape) != (K, N + 2, N + 2) or not (1 <= N <= GMM_WIDE_MAX_N and 1 <= K <= GMM_MAX_K):
+        raise ValueError("GMM global parameters: dirichlet (K), NIW (K, N+2, N+2) with N <= %d, K <= %d"
+                         % (GMM_WIDE_MAX_N, GMM_MAX_K))
     f64 = dict(dtype=torch.float64, device=dev)
     lg, gg = torch.empty(K, **f64), torch.empty(K, N + 2, N + 2, **f64)
     kl, pd, pn = None, None, None
@@ -215,8 +238,9 @@ def global_step(global_natparam, prior_natparam=None, info=None, reference_compa
         info = torch.zeros(1, dtype=torch.int32, device=dev)
     global_step.last_info = info
     p = _lib.ptr
-    _lib.check(_lib.load().svae_gmm_global_step_f64(K, N, p(dn), p(nn_), p(pd), p(pn), p(lg), p(gg), p(kl), p(info),
-                                                    _lib.current_stream(dev)), "svae_gmm_global_step_f64")
+    name = "svae_gmm_global_step_f64" if N <= GMM_MAX_N else "svae_gmm_wide_global_step_f64"
+    _lib.check(getattr(_lib.load(), name)(K, N, p(dn), p(nn_), p(pd), p(pn), p(lg), p(gg), p(kl), p(info),
+                                          _lib.current_stream(dev)), name)
     return lg, gg, (kl[1 if reference_compat else 0] if kl is not None else None)
 
 
@@ -317,8 +341,9 @@ def gaussian_sample(gaussian_natparam, eps):
     if tuple(eps.shape) != (T, S, N):
         raise ValueError("eps must be (T, S, N)")
     out = torch.empty(T, S, N, dtype=torch.float64, device=gn.device)
-    _lib.check(lib.svae_gmm_sample_f64(T, N, S, _lib.ptr(gn), _lib.ptr(eps), _lib.ptr(out),
-                                       _lib.current_stream(gn.device)), "svae_gmm_sample_f64")
+    name = "svae_gmm_sample_f64" if N <= GMM_MAX_N else "svae_gmm_wide_sample_f64"
+    _lib.check(getattr(lib, name)(T, N, S, _lib.ptr(gn), _lib.ptr(eps), _lib.ptr(out),
+                                  _lib.current_stream(gn.device)), name)
     return out
 
 
@@ -344,9 +369,9 @@ class _LocalTail(torch.autograd.Function):
         p = _lib.ptr
         gs = None if g_samples is None else g_samples.to(torch.float64).contiguous()
         gk = None if g_kl is None else g_kl.to(torch.float64).reshape(1).contiguous()
-        _lib.check(lib.svae_gmm_local_vjp_f64(T, N, K, S, p(lg), p(gg), p(nJ), p(nh), p(gn), p(ln), p(gk), p(eps),
-                                              p(gs), p(gJ), p(gh), _lib.current_stream(nh.device)),
-                   "svae_gmm_local_vjp_f64")
+        name = "svae_gmm_local_vjp_f64" if N <= GMM_MAX_N else "svae_gmm_wide_local_vjp_f64"
+        _lib.check(getattr(lib, name)(T, N, K, S, p(lg), p(gg), p(nJ), p(nh), p(gn), p(ln), p(gk), p(eps),
+                                      p(gs), p(gJ), p(gh), _lib.current_stream(nh.device)), name)
         return gJ, gh, None, None, None, None
 
 
