@@ -42,13 +42,15 @@ def _canonical_init_params(init_params, device):
 
 
 _default_options = _lib.OPT_DEFAULT
+_word_before_accurate = None     # the default word set_accurate_smoother(True) replaced; False puts it back
 
 
 def set_default_options(options):
     """Kernel-selection word (svae_amd._lib.OPT_*) that plans created WITHOUT an explicit `options` take; returns
     the previous one.  Host-side convenience for the tests and A/B tools that run a whole suite through one
     kernel family -- the library itself holds no selection state: each plan passes its word with every call."""
-    global _default_options
+    global _default_options, _word_before_accurate
+    _word_before_accurate = None
     old, _default_options = _default_options, int(options)
     return old
 
@@ -62,11 +64,22 @@ def set_accurate_smoother(on=True):
       * inference + VJP (n <= 10, <= 2 samples): the one-call kernels on `[chol(P)^-T | c]` records at EVERY batch size
         (SVAE_OPT_LEAN_ON; the default from 1025 sequences) -- factors of balanced magnitude: cond * eps; 1.7 instead of
         0.7 ms per forward + backward at 512 sequences.
-    On a model with cond(J22) = 7.8e7 (the worst of 400 draws of the reference's rand_lds): E[x] 1.4e-9 / 1.7e-9 from a
-    60-digit solve instead of 2.6e-4 / 7e-4, node gradients 3.5e-9 from the reference's instead of 1.2e-4; on well-conditioned
-    models 1e-12 either way ("Conditioning").  Returns the previous default word."""
+    On a model with cond(J22) = 7.8e7 (the worst of 400 draws of the reference's rand_lds; exactly symmetric blocks),
+    normwise from a 50-digit solve (tests/test_lds_truth_hip.py): E-step statistics 2.9e-10 instead of 1.3e-4, training
+    forward 5.5e-10 instead of 1.3e-4, node gradients 2.8e-10 (J) / 3.8e-10 (h) instead of 7.1e-5 / 1.1e-4 -- the
+    reference's own are 5.4e-10, 4.3e-10 and 1.1e-9 / 7.3e-10;
+    on well-conditioned models 1e-12 either way ("Conditioning").  set_accurate_smoother(False) restores
+    the word that the last set_accurate_smoother(True) replaced.  Returns the previous default word."""
+    global _word_before_accurate
     acc = _lib.OPT_TWOEND_FULL | _lib.OPT_LEAN_ON
-    return set_default_options(((_default_options & ~_lib.OPT_LEAN_OFF) | acc) if on else (_default_options & ~acc))
+    saved = _word_before_accurate
+    if on:
+        old = set_default_options((_default_options & ~_lib.OPT_LEAN_OFF) | acc)
+        _word_before_accurate = old if saved is None else saved
+        return old
+    if saved is not None:           # undo the last set_accurate_smoother(True): the word it replaced, bits it cleared included
+        return set_default_options(saved)
+    return set_default_options(_default_options & ~acc)
 
 
 class LDSEStepPlan(object):
@@ -448,6 +461,13 @@ def _host_condition_options(pair_params):
     return (_lib.OPT_TWOEND_FULL | _lib.OPT_LEAN_ON) if worst > CONDITION_GUARD_THRESHOLD else 0
 
 
+def _guarded_plan_options(pair_params, inhomog=False):
+    """`options` of a plan an entry point creates on the spot: None (the default word), or the default word with the
+    accurate kernels' bits when the homogeneous pair blocks are host data and ill-conditioned (_host_condition_options)"""
+    guard = 0 if inhomog else _host_condition_options(pair_params)
+    return ((_default_options & ~_lib.OPT_LEAN_OFF) | guard) if guard else None
+
+
 def _prepare(natparam, node_params, plan):
     """Shape checks / canonical device tensors shared by the E-step, filter and sampler wrappers
     (`_canonical_node_params`, `_canonical_init_params`, lds_inference.py:59-82)."""
@@ -492,9 +512,7 @@ def _prepare(natparam, node_params, plan):
         raise ValueError("pair logZ must have one entry per step")
 
     if plan is None:
-        guard = 0 if inhomog else _host_condition_options(pair_params)
-        plan = LDSEStepPlan(B, T, n, dev, inhomog, pair_batched,
-                            options=((_default_options & ~_lib.OPT_LEAN_OFF) | guard) if guard else None)
+        plan = LDSEStepPlan(B, T, n, dev, inhomog, pair_batched, options=_guarded_plan_options(pair_params, inhomog))
     elif (plan.B, plan.T, plan.n, plan.inhomog) != (B, T, n, inhomog):
         raise ValueError("plan shape mismatch")
     return dict(plan=plan, batched=batched, B=B, T=T, n=n, inhomog=inhomog, pair_batched=pair_batched,
@@ -694,7 +712,7 @@ def natural_lds_inference_general(natparam, node_params, num_samples=None, eps=N
         nh = torch.as_tensor(node_params[1])
         B, T, n = (nh.shape if batched else (1,) + tuple(nh.shape))
         pdim = torch.as_tensor(natparam[1][0]).dim()
-        plan = LDSEStepPlan(B, T, n, "cuda", pdim >= 3, pdim == 4)
+        plan = LDSEStepPlan(B, T, n, "cuda", pdim >= 3, pdim == 4, options=_guarded_plan_options(natparam[1], pdim != 2))
     if eps is None:
         eps = torch.randn(plan.B, plan.T, S, plan.n, dtype=torch.float64, device=plan.device,
                           generator=generator)
@@ -892,9 +910,8 @@ def lds_inference_differentiable(natparam, node_params, eps=None, plan=None, pai
         logZ_pair = logZ_pair.reshape(1).expand(max(T - 1, 0)).contiguous()
         inhomog = True
     if plan is None:
-        guard = 0 if np.ndim(pair_params[0]) != 2 else _host_condition_options(pair_params)
         plan = LDSEStepPlan(B, T, n, dev, inhomog, pair_batched,
-                            options=((_default_options & ~_lib.OPT_LEAN_OFF) | guard) if guard else None)
+                            options=_guarded_plan_options(pair_params, np.ndim(pair_params[0]) != 2))
     elif plan.inhomog != inhomog:
         raise ValueError("plan layout mismatch (pair_stats_grad=True needs a per-step plan: inhomog=True)")
     params = (init_J, init_h, init_logZ, J11, J12, J22, logZ_pair)

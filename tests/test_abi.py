@@ -197,3 +197,23 @@ def test_round4_entry_points_reject_bad_arguments():
     assert lib.svae_ipc_allreduce_f64(4, 4, 0, 17, 1, 0, one, one, one, one, None) == -4
     assert lib.svae_ipc_allreduce_f64(4, 4, 0, 2, 0, 0, one, one, one, one, None) == -5
     assert lib.svae_ipc_allreduce_f64(4, 4, 0, 2, 1, 0, one, one, None, one, None) == -9
+
+
+@pytest.mark.parametrize("name", ["auto", "twoend", "twoend_full", "twoend_seq", "twoend_rpc", "split", "packed"])
+@pytest.mark.parametrize("extra", [0, "lean_off"])
+def test_accurate_smoother_round_trip_restores_the_default_word(name, extra):
+    """set_accurate_smoother(True) then (False) leaves the default kernel word as it was, the bits True cleared included"""
+    from svae_amd import _lib
+    from svae_amd.lds import lds_inference as li
+    word = _lib.KERNEL_OPTIONS[name] | (_lib.OPT_LEAN_OFF if extra else 0)
+    old = li.set_default_options(word)
+    try:
+        li.set_accurate_smoother(True)
+        assert li._default_options & _lib.OPT_TWOEND_FULL and li._default_options & _lib.OPT_LEAN_ON
+        assert li.set_accurate_smoother(True) == li._default_options          # a second True is idempotent
+        li.set_accurate_smoother(False)
+        assert li._default_options == word
+        li.set_accurate_smoother(False)                                       # False without a pending True: bits off
+        assert li._default_options == word & ~(_lib.OPT_TWOEND_FULL | _lib.OPT_LEAN_ON)
+    finally:
+        li.set_default_options(old)

@@ -57,8 +57,8 @@ TOL = 1e-9
 # Cases where the kernels and the compiled reference differ by more than 1e-9 (max over the case's sequences, measured on
 # MI355X; bound = about 3x the measurement).  Every one is a draw whose pivots are ill-conditioned: the "batched" form
 # gives each sequence its own draws and cycles each sequence's steps through three of them, so 64 x 3 models meet the
-# worst of them; n = 13 is the worst single draw of those shapes.  Which side carries the error there has not been
-# arbitrated with an extended-precision solve; the bounds pin today's agreement so that any drift shows.
+# worst of them; n = 13 is the worst single draw of those shapes.  tests/test_lds_truth_hip.py arbitrates every case
+# against an extended-precision solve; the bounds pin today's agreement.
 BOUNDS = {("filter", 10, "batched"): 1.5e-6, ("smoother", 10, "batched"): 4e-6, ("smoother", 13, "homog"): 5e-8,
           ("smoother", 13, "inhomog"): 6e-8, ("smoother", 13, "batched"): 3e-8, ("smoother", 15, "batched"): 3e-9,
           ("sampler", 10, "batched"): 6e-9, ("sampler", 10, "inhomog"): 9e-9, ("sampler", 15, "batched"): 5e-8}

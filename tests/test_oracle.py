@@ -295,3 +295,122 @@ def test_the_60_digit_arbiter_agrees_with_the_restatement_on_a_well_conditioned_
     node = rand_node_potentials((1, T, n), rng, with_logZ=True)
     _, (_, _, En) = lds_numpy.natural_lds_estep_general((init, pair), tuple(x[0] for x in node))
     assert np.max(np.abs(np.asarray(En[1]) - smoothed_means_mp(init, pair, node[0][0], node[1][0]))) < 1e-13
+
+
+# --- oracle/lds_mp.py: the extended-precision yardstick of tests/test_lds_truth_hip.py ---------------------------------------
+
+def _mp_model(n, T, form, seed):
+    """a well-conditioned rand_lds draw; form "inhomog": step t takes the t % 3-th of three draws' pair blocks"""
+    from svae_amd.lds.synthetic_data import rand_lds_natparam, rand_node_potentials
+    rng = np.random.default_rng(seed)
+    init, pair = rand_lds_natparam(n, rng)
+    if form == "inhomog":
+        draws = [pair] + [rand_lds_natparam(n, rng)[1] for _ in range(2)]
+        steps = [draws[t % 3] for t in range(T - 1)]
+        pair = tuple(np.stack([s[k] for s in steps]) if T > 1 else np.zeros((0, n, n)) for k in range(3)) \
+            + (np.array([float(s[3]) for s in steps]),)
+    return rng, (init, pair), rand_node_potentials((T, n), rng, with_logZ=True)
+
+
+def _dist(a, b):
+    """normwise: max|a - b| / max|b| (scalars: relative to max(1, |b|))"""
+    a, b = np.asarray(a, float), np.asarray(b, float)
+    if b.ndim == 0:
+        return float(abs(a - b) / max(1.0, abs(b)))
+    return float(np.max(np.abs(a - b)) / max(np.max(np.abs(b)), 1e-300)) if b.size else 0.0
+
+
+def _stats_dist(got, want):
+    """worst _dist over (lognorm, E_init, E_pair, E_node) arrays (the constant 'ones' entries skipped)"""
+    (lg, (gi, gp, gn)), (lw, (wi, wp, wn)) = got, want
+    pairs = [(lg, lw), (gi[0], wi[0]), (gi[1], wi[1])] + [(gp[k], wp[k]) for k in range(3)] \
+        + [(gn[0], wn[0]), (gn[1], wn[1])]
+    return max(_dist(a, b) for a, b in pairs)
+
+
+MP_DRAWS = [(4, 1, "homog"), (4, 2, "homog"), (4, 25, "homog"), (3, 2, "inhomog"), (3, 25, "inhomog")]
+
+
+@pytest.mark.parametrize("n,T,form", MP_DRAWS)
+def test_mp_estep_matches_the_restatements(n, T, form):
+    from oracle import lds_longdouble
+    from oracle.lds_mp import estep_mp
+    _, natparam, node = _mp_model(n, T, form, 40 + T)
+    truth = estep_mp(natparam, node)
+    assert _stats_dist(lds_numpy.natural_lds_estep_general(natparam, node), truth) < 1e-12
+    assert _stats_dist(lds_longdouble.estep(natparam, node), truth) < 1e-12
+    if T > 1:
+        _, (_, Ep, En) = truth
+        _, Ex, _, ExxnT = lds_numpy.dense_estep(natparam, node)
+        assert _dist(En[1], Ex) < 1e-12
+        assert _dist(Ep[1], ExxnT if form == "inhomog" else ExxnT.sum(0)) < 1e-12
+
+
+@pytest.mark.parametrize("n,T,form", MP_DRAWS)
+def test_mp_message_functions_match_the_restatement(n, T, form):
+    from oracle.lds_mp import filter_mp, sample_on_messages_mp, smoother_on_messages_mp
+    rng, (init, pair), node = _mp_model(n, T, form, 50 + T)
+    msgs, lognorm = lds_numpy.natural_filter_forward_general(init, pair, node)
+    msgs_mp, lognorm_mp = filter_mp(init, pair, node)
+    assert _dist(lognorm, lognorm_mp) < 1e-12
+    for i in range(2):
+        for j in range(2):
+            assert _dist(msgs[i][j], msgs_mp[i][j]) < 1e-12
+    want = smoother_on_messages_mp(msgs, pair)
+    got = lds_numpy.natural_smoother_general(msgs, pair)
+    assert _stats_dist((0., got), (0., want)) < 1e-12
+    eps = rng.standard_normal((T, 3, n))
+    assert _dist(lds_numpy.natural_sample_backward_general(msgs, pair, eps), sample_on_messages_mp(msgs, pair, eps)) < 1e-12
+
+
+def test_mp_identities():
+    """E_pair of a homogeneous model = the sum of its per-step blocks; the h-derivative of lognorm is E[x]"""
+    from oracle.lds_mp import estep_mp, jvp_mp
+    rng, (init, pair), node = _mp_model(3, 6, "homog", 7)
+    ln, (Ei, Ep, En) = estep_mp((init, pair), node)
+    steps = tuple(np.stack([pair[k]] * 5) for k in range(3)) + (np.full(5, float(pair[3])),)
+    ln_s, (Ei_s, Ep_s, En_s) = estep_mp((init, steps), node)
+    assert _dist(ln_s, ln) < 1e-15
+    for k in range(3):
+        assert _dist(Ep_s[k].sum(0), Ep[k]) < 1e-15
+    v = rng.standard_normal(node[1].shape)
+    d_ln = jvp_mp(estep_mp, ((init, pair), node), (None, (None, v, None)))[0]
+    assert abs(d_ln - float(np.sum(En[1] * v))) <= 1e-15 * np.sum(np.abs(En[1] * v))
+
+
+@pytest.mark.parametrize("fname", ["estep", "filter", "smoother", "sampler"])
+def test_mp_jvp_is_exact(fname):
+    """jvp_mp at 40 and 60 digits agree to 1e-15, and with float64 central differences of the restatement to ~1e-6"""
+    from oracle import lds_mp
+    rng, (init, pair), node = _mp_model(3, 8, "homog", 8)
+    msgs, _ = lds_numpy.natural_filter_forward_general(init, pair, node)
+    sym = lambda *s: (lambda a: a + np.swapaxes(a, -1, -2))(rng.standard_normal(s))
+    eps = rng.standard_normal((8, 2, 3))
+    if fname == "estep":
+        f, f64, args = lds_mp.estep_mp, lds_numpy.natural_lds_estep_general, ((init, pair), node)
+        v = (None, (rng.standard_normal((8, 3)), rng.standard_normal((8, 3)), None))
+        flat = lambda out: np.concatenate([np.ravel(out[0])] + [np.ravel(x) for x in out[1][2][:2]] + [np.ravel(out[1][1][1])])
+    elif fname == "filter":
+        f, f64, args = lds_mp.filter_mp, lds_numpy.natural_filter_forward_general, (init, pair, node)
+        v = (None, None, (rng.standard_normal((8, 3)), rng.standard_normal((8, 3)), None))
+        flat = lambda out: np.concatenate([np.ravel(out[1])] + [np.ravel(x) for m in out[0] for x in m])
+    else:
+        v = (((sym(8, 3, 3), rng.standard_normal((8, 3))), (sym(8, 3, 3), rng.standard_normal((8, 3)))), None)
+        if fname == "smoother":
+            f, f64, args = lds_mp.smoother_on_messages_mp, lds_numpy.natural_smoother_general, (msgs, pair)
+            flat = lambda out: np.concatenate([np.ravel(x) for x in (out[0][0], out[0][1], out[1][1], out[2][0], out[2][1])])
+        else:
+            f, f64, args = lds_mp.sample_on_messages_mp, lds_numpy.natural_sample_backward_general, (msgs, pair, eps)
+            v = v + (None,)
+            flat = np.ravel
+    d60, d40 = flat(lds_mp.jvp_mp(f, args, v, dps=60)), flat(lds_mp.jvp_mp(f, args, v, dps=40))
+    assert _dist(d40, d60) < 1e-15
+    s = 1e-6
+
+    def shift(x, d, c):
+        if isinstance(x, (tuple, list)):
+            return type(x)(shift(a, b, c) for a, b in zip(x, d if isinstance(d, (tuple, list)) else [None] * len(x)))
+        return x if d is None else np.asarray(x, float) + c * d
+    fd = (flat(f64(*shift(args, v, s))) - flat(f64(*shift(args, v, -s)))) / (2 * s)
+    assert _dist(fd, d60) < 3e-6
+
