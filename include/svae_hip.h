@@ -29,6 +29,7 @@ extern "C" {
 #define SVAE_HMM_MAX_K 64   /* svae_hmm_estep_f64 / svae_slds_hmm_meanfield_f64: K <= 16 one DPP row per sequence; 17 <= K <= 64 one wavefront per sequence (round 6) */
 #define SVAE_LDS_MAX_N 15   /* register/DPP path: one 16-lane row per sequence, n+1 <= 16 */
 #define SVAE_LDS_TILE_MAX_N 64   /* 16 <= n <= 64: LDS-tiled MFMA path (keep: SVAE_KEEP_SIGMA or 0) */
+#define SVAE_LDS_XL_MAX_N 128   /* 65 <= n <= 128: register-panel MFMA path, svae_lds_xl_* (E-step only) */
 #define SVAE_KEEP_SIGMA 4         /* keep bit of svae_lds_estep_f64, 16 <= n <= 64 only: see svae_lds_tile_sigma_offset_bytes */
 
 /* Library/ABI version (host only, no GPU needed). */
@@ -296,6 +297,42 @@ int svae_lds_natgrad_f64(int n, int T, const double* packed_stats, const double*
  * Homogeneous E_pair layout only. */
 int svae_lds_reduce_stats_f64(int B, int n, const double* E_init, const double* E_pair,
                               const double* lognorm, double* out, void* stream);
+
+/* ---- LDS E-step for latent dimension 65 <= n <= SVAE_LDS_XL_MAX_N (csrc/lds_estep_xl.hip) ---------------------------
+ * Replaces cython_natural_lds_estep_general (svae/lds/lds_inference.py:232-237 of the reference) =
+ *   natural_filter_forward_general  svae/lds/cython_lds_inference.pyx:28-90
+ *   natural_smoother_general        svae/lds/cython_lds_inference.pyx:149-195
+ *   _compute_stats                  svae/lds/cython_lds_inference.pyx:197-210
+ * at the latent sizes above the tiled path.  One workgroup of NB = ceil(n/16) wavefronts per sequence; the step's panel
+ * lives in registers, one 16-row block row per wavefront.
+ *
+ * Workspace bytes for (B, T, n): per (sequence, step) the hand-off record [X_t | P_t^-1 (row-major NP x NP) | c_t (NP)],
+ * NP = 16 ceil(n/16), then the pair parameters re-packed in MFMA fragment order (3 NP^2 doubles per slot; 2 slots when
+ * homogeneous, T-1 per parameter set when `inhomog`, one set per sequence when `pair_batched`; none when T = 1):
+ *   8 (B T (2 NP^2 + NP) + [T >= 2] (pair_batched ? B : 1) (inhomog ? T-1 : 2) 3 NP^2)
+ * n = 128: 263 KB per step and sequence -- B = 512, T = 200 needs 26.9 GB.  0 for B <= 0, T <= 0 or n outside
+ * 65 .. SVAE_LDS_XL_MAX_N. */
+size_t svae_lds_xl_workspace_bytes(int B, int T, int n, int inhomog, int pair_batched);
+
+/* svae_lds_estep_f64's arguments, outputs and error codes for 65 <= n <= SVAE_LDS_XL_MAX_N (any other n: -3).  keep and
+ * options must be 0 (-23 / -24): there is no sampler, VJP or kernel choice at these sizes.  Returns 0; -k for a bad
+ * argument (before any HIP call); -22 workspace NULL or shorter than svae_lds_xl_workspace_bytes; -1000 / -1001 launch
+ * errors; B = 0 returns 0 after the checks of T, n, keep, pair_batched, the shared parameters and options (the
+ * per-sequence arrays and the workspace may then be NULL).  The status word `info` is set as by svae_lds_estep_f64
+ * (non-positive pivot or a NaN log-normaliser). */
+int svae_lds_xl_estep_f64(int B, int T, int n, int inhomog, int pair_batched, int keep, unsigned options,
+                          const double* init_J, const double* init_h, const double* init_logZ,
+                          const double* J11, const double* J12, const double* J22,
+                          const double* logZ_pair,
+                          const double* node_J, const double* node_h, const double* node_logZ,
+                          double* lognorm, double* E_init, double* E_pair,
+                          double* E_node_diagxx, double* E_node_x,
+                          int32_t* info, void* workspace, size_t ws_bytes, void* stream);
+
+/* svae_lds_reduce_stats_f64 (the batch sums all-reduced for svae.py:33-34) for the outputs of svae_lds_xl_estep_f64:
+ * the same fixed-order reduction and output layout, 65 <= n <= SVAE_LDS_XL_MAX_N (else -2). */
+int svae_lds_xl_reduce_stats_f64(int B, int n, const double* E_init, const double* E_pair,
+                                 const double* lognorm, double* out, void* stream);
 
 /* Backward sampling given the forward messages held in `workspace` by the LAST call of
  * svae_lds_estep_f64 with the same (B,T,n) and keep_factor != 0 [natural_sample_backward,

@@ -15,6 +15,7 @@ LIB_PATH = os.environ.get("SVAE_AMD_LIB", os.path.join(_HERE, "libsvae_hip.so"))
 ABI_VERSION = 15
 LDS_MAX_N = 15        # register/DPP path (E-step, sampler, VJP)
 LDS_TILE_MAX_N = 64   # LDS-tiled MFMA path (E-step only)
+LDS_XL_MAX_N = 128    # register-panel MFMA path, svae_lds_xl_* (E-step and batch sums only)
 
 # per-call `options` word of the LDS entry points (include/svae_hip.h, SVAE_OPT_*): 0 = the library's choice
 OPT_DEFAULT, OPT_TWOEND_OFF, OPT_TWOEND_FULL = 0x00, 0x01, 0x02
@@ -38,6 +39,10 @@ SIGNATURES = {
     "svae_lds_tile_sigma_offset_bytes": (ctypes.c_size_t, [ctypes.c_int] * 5),
     "svae_lds_estep_f64": (ctypes.c_int, [ctypes.c_int] * 6 + [ctypes.c_uint] + [_c_double_p] * 15
                            + [_c_int_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]),
+    "svae_lds_xl_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int] * 5),
+    "svae_lds_xl_estep_f64": (ctypes.c_int, [ctypes.c_int] * 6 + [ctypes.c_uint] + [_c_double_p] * 15
+                              + [_c_int_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]),
+    "svae_lds_xl_reduce_stats_f64": (ctypes.c_int, [ctypes.c_int] * 2 + [_c_double_p] * 4 + [ctypes.c_void_p]),
     "svae_lds_filter_f64": (ctypes.c_int, [ctypes.c_int] * 5 + [ctypes.c_uint] + [_c_double_p] * 15
                             + [_c_int_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]),
     "svae_slds_lds_meanfield_lds_bytes": (ctypes.c_size_t, [ctypes.c_int] * 2),

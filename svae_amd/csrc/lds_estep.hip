@@ -434,6 +434,20 @@ int svae_lds_reduce_stats_f64(int B, int n, const double* E_init, const double* 
   return hipGetLastError() == hipSuccess ? 0 : -1000;
 }
 
+int svae_lds_xl_reduce_stats_f64(int B, int n, const double* E_init, const double* E_pair,
+                                 const double* lognorm, double* out, void* stream) {
+  if (B < 0) return -1;
+  if (n <= SVAE_LDS_TILE_MAX_N || n > SVAE_LDS_XL_MAX_N) return -2;
+  if (!E_init) return -3;
+  if (!E_pair) return -4;
+  if (!lognorm) return -5;
+  if (!out) return -6;
+  const int tot = 4 * n * n + n + 1;
+  hipLaunchKernelGGL(svae::lds_reduce_stats_kernel, dim3((tot + 7) / 8), dim3(256), 0,
+                     (hipStream_t)stream, B, n, E_init, E_pair, lognorm, out);
+  return hipGetLastError() == hipSuccess ? 0 : -1000;
+}
+
 }  // extern "C"
 
 extern "C" int svae_lds_sample_f64(int B, int T, int n, int S, unsigned options, const double* eps, double* samples,

@@ -90,9 +90,9 @@ class LDSEStepPlan(object):
     every call of this plan (svae_amd._lib.OPT_*, include/svae_hip.h SVAE_OPT_*; None = set_default_options)."""
 
     def __init__(self, B, T, n, device="cuda", inhomog=False, pair_batched=False, options=None):
-        if not (1 <= n <= _lib.LDS_TILE_MAX_N):
+        if not (1 <= n <= _lib.LDS_XL_MAX_N):
             raise ValueError("latent dimension n=%d outside the supported range (1..%d)"
-                             % (n, _lib.LDS_TILE_MAX_N))
+                             % (n, _lib.LDS_XL_MAX_N))
         if T < 1 or B < 0:
             raise ValueError("need T >= 1 and B >= 0")
         self.lib = _lib.load()
@@ -101,8 +101,12 @@ class LDSEStepPlan(object):
         self.device = torch.device(device)
         f64 = dict(dtype=torch.float64, device=self.device)
         # (n > 15: the workspace also holds the re-packed pair parameters, one set per sequence if batched)
-        self.ws_bytes = int(self.lib.svae_lds_workspace_bytes_ex(max(B, 1), T, n, int(self.inhomog),
-                                                                 int(bool(pair_batched))))
+        if self.xl:
+            self.ws_bytes = int(self.lib.svae_lds_xl_workspace_bytes(max(B, 1), T, n, int(self.inhomog),
+                                                                     int(bool(pair_batched))))
+        else:
+            self.ws_bytes = int(self.lib.svae_lds_workspace_bytes_ex(max(B, 1), T, n, int(self.inhomog),
+                                                                     int(bool(pair_batched))))
         self.ws = torch.empty(self.ws_bytes // 8, **f64)
         self.lognorm = torch.empty(B, **f64)
         self.E_init = torch.empty(B, n * n + n, **f64)
@@ -123,6 +127,15 @@ class LDSEStepPlan(object):
         # remembers the launch it belongs to and refuses to run after the plan has been reused
         self.epoch = 0
 
+    @property
+    def xl(self):
+        """65 <= n <= 128: the E-step runs on svae_lds_xl_estep_f64, which keeps no record for a sampler or a VJP."""
+        return self.n > _lib.LDS_TILE_MAX_N
+
+    def _no_xl(self, what):
+        if self.xl:
+            raise ValueError("%s: latent dimension <= %d (n = %d runs the E-step only)" % (what, _lib.LDS_TILE_MAX_N, self.n))
+
     def launch(self, init_J, init_h, init_logZ, J11, J12, J22, logZ_pair, node_J, node_h,
                node_logZ=None, pair_batched=False, keep_factor=False, keep_cross=False, half=0, keep_sigma=False):
         """Raw launch on the current stream.  All arguments: contiguous float64 device tensors.
@@ -131,6 +144,24 @@ class LDSEStepPlan(object):
         keep_sigma (16 <= n <= 64 only, after `vjp_tail`): the backward half leaves the smoothed covariances in the
         first section of the VJP workspace behind the hand-off (SVAE_KEEP_SIGMA), which saves the VJP its phase 0."""
         p = _lib.ptr
+        if self.xl:
+            # 65 <= n <= 128: E-step only; the plan's options word (kernel choice of the smaller paths) does not apply
+            if half or keep_factor or keep_cross or keep_sigma:
+                self._no_xl("E-step halves and kept records (half=, keep_*)")
+            rc = self.lib.svae_lds_xl_estep_f64(
+                self.B, self.T, self.n, int(self.inhomog), int(pair_batched), 0, 0,
+                p(init_J), p(init_h), p(init_logZ), p(J11), p(J12), p(J22), p(logZ_pair),
+                p(node_J), p(node_h), p(node_logZ),
+                p(self.lognorm), p(self.E_init), p(self.E_pair), p(self.E_node_diagxx),
+                p(self.E_node_x), p(self.info), p(self.ws), self.ws_bytes,
+                _lib.current_stream(self.device))
+            _lib.check(rc, "svae_lds_xl_estep_f64")
+            self.epoch += 1
+            self.has_factor = self.has_cross = False
+            self.lean, self._infer_S = False, None
+            self._J12 = J12
+            self._pair_batched = bool(pair_batched)
+            return
         ev = getattr(self, "_side_event", None)
         if ev is not None:       # work on a helper stream still reads the hand-off this launch overwrites (lds_large.py)
             torch.cuda.current_stream(self.device).wait_event(ev)
@@ -179,6 +210,7 @@ class LDSEStepPlan(object):
         records (csrc/lds_lean_estep.hpp): the same results with a fifth of the hand-off traffic; `sample()` cannot
         follow such a launch (`self.lean`).  keep_vjp=False: forward values only -- no cross-moment record, and lean
         records then also serve per-step / per-sequence pair parameters; `vjp()` cannot follow."""
+        self._no_xl("infer()")
         if self.n > _lib.LDS_MAX_N:
             raise ValueError("infer(): latent dimension <= %d (the tile path runs its stages separately)" % _lib.LDS_MAX_N)
         p = _lib.ptr
@@ -212,6 +244,7 @@ class LDSEStepPlan(object):
         """16 <= n <= 64: the workspace of svae_lds_tile_vjp_f64 for S sample cotangents as a view BEHIND the hand-off in
         the plan's own buffer (grown if necessary -- call it before the launch whose hand-off the VJP will read), at
         svae_lds_tile_sigma_offset_bytes: where a launch with keep_sigma leaves the smoothed covariances."""
+        self._no_xl("vjp_tail()")
         B, T, n = max(self.B, 1), self.T, self.n
         off = int(self.lib.svae_lds_tile_sigma_offset_bytes(B, T, n, int(self.inhomog), int(bool(pair_batched)))) // 8
         nws = int(self.lib.svae_lds_tile_vjp_workspace_doubles(B, T, n, S))
@@ -226,6 +259,7 @@ class LDSEStepPlan(object):
                node_logZ=None, pair_batched=False, J_pred=None, h_pred=None, J_filt=None, h_filt=None):
         """Filter-only launch (svae_lds_filter_f64): lognorm, optional forward messages, and the hand-off
         `sample()` needs."""
+        self._no_xl("filter()")
         p = _lib.ptr
         rc = self.lib.svae_lds_filter_f64(
             self.B, self.T, self.n, int(self.inhomog), int(pair_batched), self.options,
@@ -243,6 +277,7 @@ class LDSEStepPlan(object):
         """Backward sampling from the messages of the last `launch(..., keep_factor=True)`.
         eps: (B,T,S,n) standard-normal draws -> samples (B,T,S,n)
         [natural_sample_backward, cython_lds_inference.pyx:310-355]."""
+        self._no_xl("sample()")
         if eps.dim() != 4 or eps.shape[0] != self.B or eps.shape[1] != self.T or eps.shape[3] != self.n \
                 or eps.shape[2] < 1:
             raise ValueError("eps must be (B,T,S,n) with S >= 1")
@@ -276,6 +311,7 @@ class LDSEStepPlan(object):
         pair parameters, g_E_pair (B,T-1,3,n,n) are the cotangents of the remaining statistics
         (_compute_stats_grad, :212-234) -- what the SLDS-SVAE differentiates.  dense_out (B,T,n,n): also receives
         -2 Pbar_t, the (unsymmetrised) cotangent of a DENSE node potential J_t (svae_lds_estep_vjp_dense_f64)."""
+        self._no_xl("vjp()")
         lean = getattr(self, "lean", False)
         if not (getattr(self, "has_cross", False) and (lean or getattr(self, "has_factor", False))):
             raise RuntimeError("vjp() needs a preceding launch(..., keep_factor=True, keep_cross=True) or infer()")
@@ -339,10 +375,10 @@ class LDSEStepPlan(object):
         if self.inhomog:
             raise ValueError("reduce(): per-step pair statistics (B,T-1,3,n,n) have no batch-summed form here")
         p = _lib.ptr
-        rc = self.lib.svae_lds_reduce_stats_f64(
-            self.B, self.n, p(self.E_init), p(self.E_pair), p(self.lognorm), p(self.reduced),
-            _lib.current_stream(self.device))
-        _lib.check(rc, "svae_lds_reduce_stats_f64")
+        fn = self.lib.svae_lds_xl_reduce_stats_f64 if self.xl else self.lib.svae_lds_reduce_stats_f64
+        rc = fn(self.B, self.n, p(self.E_init), p(self.E_pair), p(self.lognorm), p(self.reduced),
+                _lib.current_stream(self.device))
+        _lib.check(rc, fn.__name__)
         return self.reduced
 
     def check_info(self):
@@ -354,6 +390,14 @@ class LDSEStepPlan(object):
             raise FloatingPointError("LDS E-step: sequence %d hit a non-positive pivot "
                                      "(potentials not positive definite; through models.lds.run_inference also: the "
                                      "global natural parameters are not valid)" % (v - 1))
+
+
+def require_sampler_range(n, what):
+    """The sampler and the VJPs stop at n = 64 (the XL E-step, 65 <= n <= 128, keeps no record for them): ValueError before
+    anything is launched."""
+    if int(n) > _lib.LDS_TILE_MAX_N:
+        raise ValueError("%s: the sampler and the VJPs take latent dimension <= %d (n = %d: E-step only, "
+                         "natural_lds_estep_general)" % (what, _lib.LDS_TILE_MAX_N, int(n)))
 
 
 def _is_dense_nodes(node_params):
@@ -658,6 +702,7 @@ def natural_lds_sample(natparam, node_params, num_samples=1, eps=None, plan=None
     """Filter + backward sampling WITHOUT the smoother: `cython_natural_lds_sample`
     (lds_inference.py:260-264) -> samples (T,S,n) [(B,T,S,n) batched].  `eps` as in
     natural_lds_inference_general."""
+    require_sampler_range(np.shape(node_params[1])[-1], "natural_lds_sample")
     if _is_dense_nodes(node_params):
         if plan is not None:
             raise ValueError("dense node potentials: the plan is built internally")
@@ -696,6 +741,7 @@ def natural_lds_inference_general(natparam, node_params, num_samples=None, eps=N
     The reference draws its noise from the global NumPy RNG inside the sampler
     (cython_lds_inference.pyx:333); here `eps` (B,T,S,n) / (T,S,n) may be passed in, else it is drawn
     from `generator` on the device."""
+    require_sampler_range(np.shape(node_params[1])[-1], "natural_lds_inference_general")
     if _is_dense_nodes(node_params):
         if plan is not None:
             raise ValueError("dense node potentials: the plan is built internally")
@@ -890,6 +936,7 @@ def lds_inference_differentiable(natparam, node_params, eps=None, plan=None, pai
     init_params, pair_params = natparam
     node_J, node_h = node_params[0], node_params[1]
     node_logZ = node_params[2] if len(node_params) == 3 else None
+    require_sampler_range(node_h.shape[-1], "lds_inference_differentiable")
     dev = node_h.device
     if node_h.dim() == 3 and node_J.dim() == 4:
         # DENSE node potentials (the reference's Python path, lds_inference.py:65-82): differentiable since round 6 --

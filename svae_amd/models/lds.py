@@ -20,7 +20,8 @@ import torch
 
 from .. import _lib
 from ..distributions import expfam
-from ..lds.lds_inference import LDSEStepPlan, natural_lds_estep_general, natural_lds_inference_general, reduce_stats
+from ..lds.lds_inference import (LDSEStepPlan, natural_lds_estep_general, natural_lds_inference_general, reduce_stats,
+                                 require_sampler_range)
 from ..parallel import allreduce_lds_stats
 
 
@@ -157,6 +158,7 @@ def run_inference(prior_natparam, global_natparam, nn_potentials, num_samples, e
     batched = node[1].dim() == 3
     nodeb = node if batched else tuple(x[None] for x in node)
     B, T, n = nodeb[1].shape
+    require_sampler_range(n, "run_inference")
     if plan is None:
         plan = LDSEStepPlan(B, T, n, dev)
     # (invalid global parameters raise the PLAN's status word: plan.check_info() / check=True report them)
