@@ -450,6 +450,30 @@ int svae_hmm_estep_f64(int B, int T, int K, int pair_batched,
                        double* logZ, double* E_init, double* E_trans, double* E_states,
                        void* workspace, size_t ws_bytes, void* stream);
 
+/* Batched HMM Viterbi decoding: the most probable state path of B chains with K <= SVAE_HMM_MAX_K states and its
+ * score, on the LOG potentials svae_hmm_estep_f64 takes (entries may be -inf) -- csrc/hmm_viterbi.hip
+ * [hmm_viterbi of the reference, svae/hmm/hmm_inference.py:54-63, delegates to the un-vendored pyhsmm: the arithmetic is
+ *  defined HERE, and reproducible bit for bit by restating it in the same order]:
+ *    delta_0[k] = init[k] + node[0][k];   delta_t[k] = (max_j (delta_{t-1}[j] + pair[j][k])) + node[t][k]   (fp64 adds
+ *    in that order);  psi_t[k] = the LOWEST j attaining the maximum;  z_{T-1} = the lowest k attaining
+ *    max_k delta_{T-1}[k];  z_t = psi_{t+1}[z_{t+1}];  score = delta_{T-1}[z_{T-1}].
+ *  A chain all of whose potentials are -inf at some step has score -inf and the labels the lowest-index rule gives.
+ *  NaN inputs: unspecified labels in 0..K-1, no fault.
+ *  in : init_params (K); pair_params (K,K) [j][k] = j -> k, or (B,K,K) if pair_batched; node_params (B,T,K)
+ *  out: states (B,T) int32; score (B) or NULL
+ *  workspace: svae_hmm_viterbi_workspace_bytes(B,T,K) = B T KP bytes rounded up to a multiple of 8 (one back-pointer
+ *       byte per step and padded state, KP = 16, 32 or 64 for K <= 16, <= 32, <= 64); 0 for B <= 0, T <= 0 or K outside
+ *       1..SVAE_HMM_MAX_K.  16-byte aligned.
+ *  Returns 0, or (decided on the host before any HIP call) -1 B < 0, -2 T < 1, -3 K outside 1..SVAE_HMM_MAX_K,
+ *  -4 pair_batched not 0 or 1, -5 init_params NULL, -6 pair_params NULL, [B = 0 returns 0 here], -7 node_params NULL,
+ *  -8 states NULL, -10 workspace NULL, -11 ws_bytes too small, -12 workspace not 16-byte aligned; -1000 launch error.
+ *  Asynchronous on `stream`, no internal allocation, safe under graph capture. */
+size_t svae_hmm_viterbi_workspace_bytes(int B, int T, int K);
+int svae_hmm_viterbi_f64(int B, int T, int K, int pair_batched,
+                         const double* init_params, const double* pair_params,
+                         const double* node_params, int32_t* states, double* score,
+                         void* workspace, size_t ws_bytes, void* stream);
+
 /* HMM step of the SLDS coordinate ascent on the rows `seq_index` lists (B of `rows`; NULL: rows 0..B-1; negative
  * entries = unused slots, which must follow the live ones -- the list svae_slds_sweep_glue_f64 writes):
  *   hmm_meanfield + get_arhmm_local_nodeparams   /root/reference/svae/models/slds_svae.py:108-115, 131-147

@@ -2,6 +2,7 @@
 
   hmm_estep(natparam) -> (log_normalizer, (E_init, E_trans, E_states))      (:21-41)
   hmm_logZ(natparam)  -> log_normalizer                                      (:12-17, pyx:93-121)
+  hmm_viterbi(natparam) -> most probable state path (and its score)          (:54-63; csrc/hmm_viterbi.hip)
 
 natparam = (init_params (K), pair_params (K,K), node_params (T,K)) are LOG potentials, as in the
 reference.  New: node_params may be (B,T,K) (and pair_params (B,K,K)); outputs then carry a leading
@@ -55,6 +56,49 @@ def hmm_estep(natparam, workspace=None):
 
 def hmm_logZ(natparam):
     return hmm_estep(natparam)[0]
+
+
+def hmm_viterbi(natparam, workspace=None, return_score=False):
+    """Most probable state path under the LOG potentials hmm_estep takes (entries may be -inf):
+    labels torch.int32 (T,), or (B,T) when node_params is (B,T,K); with return_score also the path's score
+    (0-d, or (B)).  The arithmetic is defined in include/svae_hip.h (svae_hmm_viterbi_f64): fp64 additions in a fixed
+    order, ties to the lowest index -- labels and score are reproducible bit for bit.
+    workspace: any contiguous device tensor of at least svae_hmm_viterbi_workspace_bytes(B,T,K) bytes."""
+    init_params, pair_params, node_params = natparam
+    dev = node_params.device if isinstance(node_params, torch.Tensor) and node_params.is_cuda \
+        else torch.device("cuda", torch.cuda.current_device())
+    init_params, pair_params, node = (_dev64(x, dev) for x in (init_params, pair_params, node_params))
+    batched = node.dim() == 3
+    if node.dim() not in (2, 3):
+        raise ValueError("node_params must be (T,K) or (B,T,K)")
+    if not batched:
+        node = node[None]
+    B, T, K = node.shape
+    if not (1 <= K <= HMM_MAX_K):
+        raise ValueError("number of states K=%d outside 1..%d" % (K, HMM_MAX_K))
+    if T < 1:
+        raise ValueError("node_params has no steps")
+    pair_batched = pair_params.dim() == 3
+    if tuple(init_params.shape) != (K,) or tuple(pair_params.shape[-2:]) != (K, K) or pair_params.dim() not in (2, 3) or \
+            (pair_batched and pair_params.shape[0] != B):
+        raise ValueError("init/pair parameter shapes do not match the node potentials")
+    lib = _lib.load()
+    if workspace is None:
+        wsb = int(lib.svae_hmm_viterbi_workspace_bytes(max(B, 1), T, K))
+        ws = torch.empty(wsb, dtype=torch.uint8, device=dev)
+    else:
+        ws = workspace
+        wsb = ws.numel() * ws.element_size()
+    states = torch.empty(B, T, dtype=torch.int32, device=dev)
+    score = torch.empty(B, dtype=torch.float64, device=dev) if return_score else None
+    p = _lib.ptr
+    rc = lib.svae_hmm_viterbi_f64(B, T, K, int(pair_batched), p(init_params), p(pair_params), p(node),
+                                  p(states), p(score), p(ws), wsb, _lib.current_stream(dev))
+    _lib.check(rc, "svae_hmm_viterbi_f64")
+    if not batched:
+        states = states[0]
+        score = score[0] if return_score else None
+    return (states, score) if return_score else states
 
 
 class _HMMLogZ(torch.autograd.Function):

@@ -7,6 +7,8 @@
   initialize_local_meanfield                      (:203-226) one sample of a random-walk LDS posterior
   get_global_stats                                (:229-243)
   run_inference                                   (:289-310)
+  run_inference_withlabels(_differentiable)       (:313-334) the same with the discrete states given
+  viterbi_labels                                  the segmentation: hmm_viterbi (svae_hmm_viterbi_f64) on the converged HMM factor
 
 The reference module is stale as shipped (imports svae.lds.niw/mniw, svae.hmm.dirichlet, lds_svae,
 none of which exist; hmm_estep needs the un-vendored pyhsmm).  Formulas are taken from it with
@@ -28,7 +30,7 @@ import torch
 from .. import _lib
 from ..distributions import expfam
 from ..parallel import allreduce_nested
-from ..hmm.hmm_inference import hmm_estep, hmm_logZ_differentiable
+from ..hmm.hmm_inference import hmm_estep, hmm_logZ_differentiable, hmm_viterbi
 from ..lds.lds_inference import (LDSEStepPlan, lds_inference_differentiable, natural_lds_estep_general,
                                      natural_lds_sample)
 
@@ -697,6 +699,54 @@ def run_inference(prior_natparam, global_natparam, nn_potentials, num_samples, i
     return samples, expected_stats, global_vlb, local_vlb
 
 
+def viterbi_labels(global_natparam, nn_potentials, init_eps=None, generator=None, tol=1e-2, reference_compat=True):
+    """The segmentation of a batch of sequences under the model: the local mean field is optimised as in run_inference,
+    then the most probable discrete path under the converged HMM factor (its init / pair potentials and the node
+    potentials the LDS factor's statistics give) is decoded with hmm_viterbi.
+    -> (labels (B,T) int32, score (B)); the labels are what run_inference_withlabels consumes."""
+    dev = nn_potentials[1].device
+    node = tuple(_dev64(x, dev) for x in nn_potentials)
+    B, T, n = node[1].shape
+    if init_eps is None:
+        init_eps = torch.randn(B, T, 1, n, dtype=torch.float64, device=dev, generator=generator)
+    _, (hmm_nat, _), _, _ = optimize_local_meanfield(global_natparam, node, init_eps, tol, pair_stats=False,
+                                                     reference_compat=reference_compat)
+    return hmm_viterbi(hmm_nat, return_score=True)
+
+
+def run_inference_withlabels(prior_natparam, global_natparam, potentials_and_labels, num_samples, eps=None,
+                             generator=None, group=None, reference_compat=True):
+    """(:313-334) run_inference with the discrete states GIVEN: potentials_and_labels = (nn_potentials, labels (B,T) int).
+    -> (samples (B,T,S,n), expected_stats, global_vlb, local_vlb) with local_vlb = the LDS bound only (no HMM term);
+    forward values only.  Statistics and local_vlb are summed over the ranks of `group` with one all-reduce."""
+    nn_potentials, labels = potentials_and_labels
+    dev = nn_potentials[1].device
+    node = tuple(_dev64(x, dev) for x in nn_potentials)
+    B, T, n = node[1].shape
+    host_params = (_HostParamsLater(global_natparam), _HostParamsLater(prior_natparam))
+    (hmm_stats, _), (_, (lds_init, lds_pair)), _ = optimize_local_meanfield_withlabels(global_natparam, node, labels)
+    # the final E-step + sampler of run_inference, on the per-step parameters the labels give
+    plan = LDSEStepPlan(B, T, n, dev, inhomog=True, pair_batched=True)
+    S = int(num_samples)
+    if eps is None:
+        eps = torch.randn(B, T, S, n, dtype=torch.float64, device=dev, generator=generator)
+    eps = _dev64(eps, dev)
+    if n <= _lib.LDS_MAX_N and S <= 16:
+        lognorm, (Ei, Ep, En) = _lds_estep_batched_init(plan, lds_init, lds_pair, node, keep_factor=True,
+                                                        reference_compat=reference_compat, eps=eps)
+        samples = plan._infer_samples
+    else:
+        lognorm, (Ei, Ep, En) = _lds_estep_batched_init(plan, lds_init, lds_pair, node, keep_factor=True,
+                                                        reference_compat=reference_compat)
+        samples = plan.sample(eps)
+    expected_stats = get_global_stats(hmm_stats, (Ei[0], Ei[1]), plan.E_pair)
+    lds_vlb = lognorm - ((node[0] * En[0]).sum((1, 2)) + (node[1] * En[1]).sum((1, 2)))
+    local_vlb = lds_vlb.sum()
+    expected_stats, local_vlb = allreduce_nested(expected_stats, local_vlb, group)
+    global_vlb = slds_prior_vlb(host_params[0], host_params[1], dev)
+    return samples, expected_stats, global_vlb, local_vlb
+
+
 def _slds_params_on_host(natparam):
     """A nested copy of SLDS global natural parameters on the host.  Host-resident parameters are used as they are; a
     `_HostParamsLater` (device-resident ones on their way, below) is waited for here."""
@@ -764,14 +814,10 @@ def slds_prior_vlb(global_natparam, prior_natparam, dev):
     return (val - (logZ(pd, pmd, plds) - logZ(gd, gmd, glds))).to(out_dev)
 
 
-def final_pass_differentiable(global_natparam, hmm_natparam, lds_natparam, nn_potentials, eps,
-                              reference_compat=True, local_maps=None, expected_states=None):
-    """The part of run_inference that depends on nn_potentials with gradients attached
-    (slds_svae.py:295-307, "recompute terms that depend on nn_potentials at optimum"): the LDS
-    E-step + sampler on the FIXED mean-field natural parameters, the HMM bound evaluated on its
-    statistics, and the local bound.  Returns (samples, (E_init, E_pair) per sequence, local_vlb); with
-    `expected_states` (the HMM marginals of the ascent) a fourth entry: the pair statistics summed with those weights
-    (K,3,n,n) for get_global_stats, or None -- formed by the kernel that also builds the HMM node potentials."""
+def _lds_final_pass_differentiable(lds_natparam, nn_potentials, eps, reference_compat=True):
+    """LDS E-step + sampler on FIXED mean-field natural parameters with gradients attached to nn_potentials = (J, h):
+    -> (lognorm (B), (E diag xx', E x), samples, (E_init, E_pair)); the LDS half of final_pass_differentiable and all of
+    the labelled step's final pass."""
     dev = nn_potentials[1].device
     nJ, nh = nn_potentials[0], nn_potentials[1]
     B, T, n = nh.shape
@@ -787,6 +833,22 @@ def final_pass_differentiable(global_natparam, hmm_natparam, lds_natparam, nn_po
                 (J11.contiguous(), J12.contiguous(), J22.contiguous(), lz.contiguous()))
     lognorm, (dxx, ex), samples, (E_init, E_pair) = lds_inference_differentiable(natparam, (nJ, nh_eff), eps=eps)
     lognorm = lognorm + a0 if reference_compat else lognorm + a0 + b0
+    return lognorm, (dxx, ex), samples, (E_init, E_pair)
+
+
+def final_pass_differentiable(global_natparam, hmm_natparam, lds_natparam, nn_potentials, eps,
+                              reference_compat=True, local_maps=None, expected_states=None):
+    """The part of run_inference that depends on nn_potentials with gradients attached
+    (slds_svae.py:295-307, "recompute terms that depend on nn_potentials at optimum"): the LDS
+    E-step + sampler on the FIXED mean-field natural parameters, the HMM bound evaluated on its
+    statistics, and the local bound.  Returns (samples, (E_init, E_pair) per sequence, local_vlb); with
+    `expected_states` (the HMM marginals of the ascent) a fourth entry: the pair statistics summed with those weights
+    (K,3,n,n) for get_global_stats, or None -- formed by the kernel that also builds the HMM node potentials."""
+    dev = nn_potentials[1].device
+    nJ, nh = nn_potentials[0], nn_potentials[1]
+    B, T, n = nh.shape
+    lognorm, (dxx, ex), samples, (E_init, E_pair) = _lds_final_pass_differentiable(lds_natparam, (nJ, nh), eps,
+                                                                                   reference_compat)
     _, _, dense_init, dense_pair = local_maps if local_maps is not None else global_to_local_maps(global_natparam, dev)
     init_stats = (E_init[:, :n * n].reshape(B, n, n), E_init[:, n * n:])
     pair_stats = (E_pair[:, :, 0], E_pair[:, :, 1], E_pair[:, :, 2])
@@ -827,6 +889,32 @@ def run_inference_differentiable(prior_natparam, global_natparam, nn_potentials,
         hmm_stats[2])
     expected_stats = get_global_stats(hmm_stats, tuple(x.detach() for x in init_stats),
                                       tuple(x.detach() for x in pair_stats), pair_sums)
+    expected_stats, local_vlb = allreduce_nested(expected_stats, local_vlb, group)
+    global_vlb = slds_prior_vlb(host_params[0], host_params[1], dev)
+    return samples, expected_stats, global_vlb, local_vlb
+
+
+def run_inference_withlabels_differentiable(prior_natparam, global_natparam, potentials_and_labels, num_samples,
+                                            eps=None, generator=None, group=None, reference_compat=True):
+    """run_inference_withlabels with torch autograd attached to nn_potentials = (J, h), each (B,T,n): the labelled
+    mean-field step runs on detached values (the reference's `unbox`, :319), the final E-step + sampler is
+    differentiated through the VJP kernels.  The signature make_gradfun calls with `recognize` returning
+    (nn_potentials, labels).  -> (samples (B,T,S,n), expected_stats, global_vlb, local_vlb)."""
+    nn_potentials, labels = potentials_and_labels
+    dev = nn_potentials[1].device
+    node_d = tuple(_dev64(x, dev) for x in nn_potentials)
+    B, T, n = node_d[1].shape
+    host_params = (_HostParamsLater(global_natparam), _HostParamsLater(prior_natparam))
+    (hmm_stats, _), (_, lds_nat), _ = optimize_local_meanfield_withlabels(global_natparam, node_d, labels)
+    if eps is None:
+        eps = torch.randn(B, T, int(num_samples), n, dtype=torch.float64, device=dev, generator=generator)
+    nJ, nh = nn_potentials[0], nn_potentials[1]
+    lognorm, (dxx, ex), samples, (E_init, E_pair) = _lds_final_pass_differentiable(lds_nat, (nJ, nh), _dev64(eps, dev),
+                                                                                   reference_compat)
+    init_stats = (E_init[:, :n * n].reshape(B, n, n).detach(), E_init[:, n * n:].detach())
+    pair_stats = tuple(E_pair[:, :, i].detach() for i in range(3))
+    expected_stats = get_global_stats(hmm_stats, init_stats, pair_stats)
+    local_vlb = (lognorm - ((nJ * dxx).sum((1, 2)) + (nh * ex).sum((1, 2)))).sum()
     expected_stats, local_vlb = allreduce_nested(expected_stats, local_vlb, group)
     global_vlb = slds_prior_vlb(host_params[0], host_params[1], dev)
     return samples, expected_stats, global_vlb, local_vlb
