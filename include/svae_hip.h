@@ -25,7 +25,7 @@
 extern "C" {
 #endif
 
-#define SVAE_HIP_ABI_VERSION 15   /* 15: + svae_gmm_wide_mw_workspace_bytes, svae_gmm_wide_mw_begin, svae_gmm_wide_mw_step_f64, svae_gmm_wide_sample_f64, svae_gmm_wide_local_vjp_f64, svae_gmm_wide_global_step_f64 (the GMM local step for N <= 16; additions only), svae_lds_filter_vjp_f64, svae_lds_smoother_vjp_f64 (+ svae_lds_smoother_vjp_workspace_bytes), svae_lds_sample_vjp_f64 (the reference's three reverse-mode primitives on caller-held forward messages); 14: + svae_lds_estep_vjp_dense_f64 (cotangent of dense node potentials), svae_hmm_* up to K = 64, svae_lds_inference_f64 (E-step + sampler in one call; lean per-step records for large homogeneous batches), svae_lds_inference_is_lean, SVAE_OPT_LEAN_ON / _OFF / SVAE_OPT_INFER_RECORDS; 13: + svae_slds_pair_contract_f64 (the two contractions of the SLDS final pass over the per-step pair statistics in one pass); 12: svae_gmm_global_step_f64 writes kl[0..1] (as spelled | as shipped), svae_ipc_allreduce_f64 takes the mailbox stride and never writes `out` on a timeout, + svae_slds_lds_meanfield options; 11: + svae_lds_global_step_multi_f64 (K parameter sets in one launch: the SLDS global -> local maps), svae_lds_diag_sample_f64 (filter + sampler of an all-diagonal LDS: the SLDS initial path); 10: + svae_ipc_allreduce_f64 / svae_ipc_mailbox_bytes, svae_gmm_sample_f64, svae_gmm_local_vjp_f64, svae_gmm_global_step_f64 (the differentiable tail and the global side of the GMM local step); 9: keep bit SVAE_KEEP_SIGMA of svae_lds_estep_f64 (16 <= n <= 64) + svae_lds_tile_sigma_offset_bytes; 8: step ranges (t_begin, t_end) in svae_lds_tile_vjp_f64 / svae_lds_tile_noise_f64, SVAE_OPT_TILE_FORWARD / _BACKWARD; 7: + svae_slds_path_nodeparams_f64, svae_slds_mix_pair_natparam_f64; 6: per-call `options` word replaces the process-global svae_lds_set_* selectors (re-entrant library), + svae_slds_hmm_meanfield_f64, svae_slds_sweep_glue_f64, g_E_pair in svae_lds_tile_vjp_f64; 5: + svae_lds_set_prod_max_b; 4: + svae_slds_lds_meanfield_f64, svae_gmm_mw_*, svae_lds_global_step_f64, svae_lds_natgrad_f64, svae_lds_tile_vjp_f64; 2: + svae_lds_workspace_bytes_ex, svae_lds_estep_vjp_ex_f64, svae_hmm_*, tiled path (n <= 64) */
+#define SVAE_HIP_ABI_VERSION 15   /* 15: (+ svae_lds_estep_vjp_params_f64, svae_lds_param_vjp_workspace_bytes: cotangents of the init / pair natural parameters, added without a new number -- additions only) + svae_gmm_wide_mw_workspace_bytes, svae_gmm_wide_mw_begin, svae_gmm_wide_mw_step_f64, svae_gmm_wide_sample_f64, svae_gmm_wide_local_vjp_f64, svae_gmm_wide_global_step_f64 (the GMM local step for N <= 16; additions only), svae_lds_filter_vjp_f64, svae_lds_smoother_vjp_f64 (+ svae_lds_smoother_vjp_workspace_bytes), svae_lds_sample_vjp_f64 (the reference's three reverse-mode primitives on caller-held forward messages); 14: + svae_lds_estep_vjp_dense_f64 (cotangent of dense node potentials), svae_hmm_* up to K = 64, svae_lds_inference_f64 (E-step + sampler in one call; lean per-step records for large homogeneous batches), svae_lds_inference_is_lean, SVAE_OPT_LEAN_ON / _OFF / SVAE_OPT_INFER_RECORDS; 13: + svae_slds_pair_contract_f64 (the two contractions of the SLDS final pass over the per-step pair statistics in one pass); 12: svae_gmm_global_step_f64 writes kl[0..1] (as spelled | as shipped), svae_ipc_allreduce_f64 takes the mailbox stride and never writes `out` on a timeout, + svae_slds_lds_meanfield options; 11: + svae_lds_global_step_multi_f64 (K parameter sets in one launch: the SLDS global -> local maps), svae_lds_diag_sample_f64 (filter + sampler of an all-diagonal LDS: the SLDS initial path); 10: + svae_ipc_allreduce_f64 / svae_ipc_mailbox_bytes, svae_gmm_sample_f64, svae_gmm_local_vjp_f64, svae_gmm_global_step_f64 (the differentiable tail and the global side of the GMM local step); 9: keep bit SVAE_KEEP_SIGMA of svae_lds_estep_f64 (16 <= n <= 64) + svae_lds_tile_sigma_offset_bytes; 8: step ranges (t_begin, t_end) in svae_lds_tile_vjp_f64 / svae_lds_tile_noise_f64, SVAE_OPT_TILE_FORWARD / _BACKWARD; 7: + svae_slds_path_nodeparams_f64, svae_slds_mix_pair_natparam_f64; 6: per-call `options` word replaces the process-global svae_lds_set_* selectors (re-entrant library), + svae_slds_hmm_meanfield_f64, svae_slds_sweep_glue_f64, g_E_pair in svae_lds_tile_vjp_f64; 5: + svae_lds_set_prod_max_b; 4: + svae_slds_lds_meanfield_f64, svae_gmm_mw_*, svae_lds_global_step_f64, svae_lds_natgrad_f64, svae_lds_tile_vjp_f64; 2: + svae_lds_workspace_bytes_ex, svae_lds_estep_vjp_ex_f64, svae_hmm_*, tiled path (n <= 64) */
 #define SVAE_HMM_MAX_K 64   /* svae_hmm_estep_f64 / svae_slds_hmm_meanfield_f64: K <= 16 one DPP row per sequence; 17 <= K <= 64 one wavefront per sequence (round 6) */
 #define SVAE_LDS_MAX_N 15   /* register/DPP path: one 16-lane row per sequence, n+1 <= 16 */
 #define SVAE_LDS_TILE_MAX_N 64   /* 16 <= n <= 64: LDS-tiled MFMA path (keep: SVAE_KEEP_SIGMA or 0) */
@@ -430,6 +430,45 @@ int svae_lds_estep_vjp_dense_f64(int B, int T, int n, int S, int inhomog, int pa
                                  double* g_node_J, double* g_node_h, double* g_node_J_dense,
                                  const void* workspace, size_t ws_bytes,
                                  void* vjp_workspace, size_t vjp_ws_bytes, void* stream);
+
+/* Bytes of scratch svae_lds_estep_vjp_params_f64 needs in addition to the E-step and the VJP workspace: the per-step
+ * blocks the second sweep leaves (-2 Pbar_t (B,T,n,n); the two halves of Rbar_t (B,T-1,2,n,n)) and, for homogeneous pair
+ * parameters (inhomog = 0), the per-step batch sums (T-1,3,n,n) of the reduction's first pass.  0 for n outside
+ * 1 .. SVAE_LDS_MAX_N or B, T <= 0. */
+size_t svae_lds_param_vjp_workspace_bytes(int B, int T, int n, int inhomog, int pair_batched);
+
+/* svae_lds_estep_vjp_ex_f64 plus the cotangents of the seven NATURAL PARAMETERS of the model -- the gradients the
+ * reference's Python path has through autograd (/root/reference/svae/lds/lds_inference.py:205-218), which the compiled
+ * path does not offer.  1 <= n <= SVAE_LDS_MAX_N, full (not lean) records.  With P_t = J_pred,t - 2 diag(node_J_t) - 2 J11_t,
+ * R_t = -J12_t, H_t = P_t^-1 [R_t | h_filt,t], [J_pred | h_pred]_{t+1} = [-2 J22_t | 0] - R_t' H_t (info form):
+ *   g_J11_t = -2 Pbar_t (t <= T-2), g_J22_t = -2 Pbar_{t+1}, g_init_J = -2 Pbar_0      -- returned SYMMETRISED
+ *   g_J12_t = -(Bbar_t[:, :n] - H_t [Abar | hbar]_{t+1}')                               -- a full matrix
+ *   g_init_h = hfbar_0 (= g_node_h[:,0]);  g_init_logZ = g_logZ_pair_t = g_lognorm
+ * each summed over what the parameter is shared over, in a fixed order (bit-reproducible; csrc/lds_param_grad.hip):
+ *   out: g_init_J (n,n), g_init_h (n), g_init_logZ (1): summed over the batch
+ *        g_J11, g_J12, g_J22, g_logZ_pair in the layout of the pair parameters: (n,n) / (1) summed over batch and time
+ *        (g_logZ_pair = (T-1) sum_b g_lognorm); (T-1,n,n) / (T-1) summed over the batch; (B,T-1,n,n) / (B,T-1) per sequence
+ *        any of the seven may be NULL (not wanted)
+ *        g_node_J, g_node_h (B,T,n): required, bit-identical to svae_lds_estep_vjp_ex_f64 on the same arguments (the
+ *        sweeps run as they do there; where that second sweep is not the packed one -- batches up to 1024 by default --
+ *        the packed sweep follows as a second pass for the parameter blocks alone)
+ *   param_workspace: svae_lds_param_vjp_workspace_bytes(B,T,n,inhomog,pair_batched)
+ * Returns the codes of svae_lds_estep_vjp_ex_f64 (-1 B, -2 T, -3 n outside 1 .. 15, -4 S, -5 J12, -6 g_lognorm,
+ * -7 pair_batched without inhomog, -8 g_E_pair without its operands -- and lean records under SVAE_OPT_INFER_RECORDS --,
+ * -10 eps / samples, -12 g_node_J, -13 g_node_h, -14 workspace, -16 vjp_workspace, -24 options), -29 param_workspace NULL
+ * or too small, -30 T > 65536; all before any HIP call.  B = 0 returns 0. */
+int svae_lds_estep_vjp_params_f64(int B, int T, int n, int S, int inhomog, int pair_batched, unsigned options,
+                                  const double* J12, const double* g_lognorm,
+                                  const double* g_E_node_diagxx, const double* g_E_node_x,
+                                  const double* g_E_init, const double* g_E_pair,
+                                  const double* g_samples, const double* eps, const double* samples,
+                                  const double* E_pair, const double* E_node_x,
+                                  double* g_node_J, double* g_node_h,
+                                  double* g_init_J, double* g_init_h, double* g_init_logZ,
+                                  double* g_J11, double* g_J12, double* g_J22, double* g_logZ_pair,
+                                  const void* workspace, size_t ws_bytes,
+                                  void* vjp_workspace, size_t vjp_ws_bytes,
+                                  void* param_workspace, size_t param_ws_bytes, void* stream);
 
 /* Batched HMM E-step: log-normaliser and expected statistics of B chains with K <= SVAE_HMM_MAX_K = 64 states
  * (K <= 16: one 16-lane DPP row per sequence, two-ended scaled recursions; 17 <= K <= 64, round 6: one wavefront per

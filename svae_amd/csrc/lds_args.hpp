@@ -119,7 +119,16 @@ struct VjpArgs {
   const double* __restrict__ ws3;        // cross-moment region
   double* __restrict__ adj;              // VJP scratch: vjp_step_doubles(n) per (b,t)
   double* __restrict__ g_P;              // (B,T,n,n) or nullptr: -2 Pbar_t = the cotangent of a DENSE node potential J_t (packed sweep 2 only)
+  // parameter cotangents (svae_lds_estep_vjp_params_f64; packed sweep 2, PGR instantiations, together with g_P):
+  double* __restrict__ g_R;              // (B,T-1,2,n,n) or nullptr: per step [Bbar_t[:, :n] | [Abar | hbar]_{t+1} H_t'], the two halves of
+                                         // Rbar_t = first - second' (lds_param_grad.hip turns them into g_J12 = -Rbar)
+  int pg_only;                           // 1: that launch leaves g_node_J / g_node_h alone (another sweep 2 has written them)
 };
+// extra scratch of svae_lds_estep_vjp_params_f64 (doubles): g_P, g_R, then -- homogeneous pair parameters -- the per-step
+// batch sums [T-1][3][n*n] that the second reduction pass adds up over time
+constexpr long pg_gp_doubles(int B, int T, int n) { return (long)B * T * n * n; }
+constexpr long pg_gr_doubles(int B, int T, int n) { return (long)B * (T - 1) * 2 * n * n; }
+constexpr long pg_part_doubles(int T, int n, int inhomog) { return inhomog ? 0 : (long)(T - 1) * 3 * n * n; }
 // VJP scratch per (b,t), written by sweep 1 and read by sweep 2:
 //   [0, n HS)        G^: the smoother share (two-role launches) or the total -- n rows x ws_h_stride
 //   vjp_vec_off      the sampler share of G^ = sum_s xhat_s [x_{t+1,s}' | 1] as its factors (two-role launches, which

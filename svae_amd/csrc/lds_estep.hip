@@ -564,7 +564,7 @@ static int vjp_impl(int B, int T, int n, int S, int inhomog, int pair_batched, u
                     const double* g_E_init, const double* g_E_pair,
                     const double* g_samples, const double* eps,
                     const double* samples, const double* E_pair,
-                    const double* E_node_x, double* g_node_J, double* g_node_h, double* g_node_J_dense,
+                    const double* E_node_x, double* g_node_J, double* g_node_h, double* g_node_J_dense, double* g_R,
                     const void* workspace, size_t ws_bytes,
                     void* vjp_workspace, size_t vjp_ws_bytes, void* stream) {
   if (B < 0) return -1;
@@ -597,7 +597,8 @@ static int vjp_impl(int B, int T, int n, int S, int inhomog, int pair_batched, u
   a.ws3 = a.ws2 + factor_ws_doubles(B, T, n);
   a.adj = (double*)vjp_workspace;
   a.g_P = g_node_J_dense;
-  if (g_node_J_dense) a.prod_max_b = 0;          /* the packed sweeps write it */
+  a.g_R = g_R; a.pg_only = 0;
+  if (g_node_J_dense && !g_R) a.prod_max_b = 0;  /* the packed sweeps write it (with g_R: launch_vjp adds the packed sweep 2 where the selection is another) */
   if ((options & SVAE_OPT_INFER_RECORDS) && lean_applies(B, T, n, S, inhomog, 1, options)) {
     if (g_E_init || g_E_pair || g_node_J_dense) return -8;        /* lean records: cotangents of the node statistics, lognorm and samples */
     switch (n) {
@@ -640,7 +641,7 @@ extern "C" int svae_lds_estep_vjp_ex_f64(int B, int T, int n, int S, int inhomog
                                          const void* workspace, size_t ws_bytes,
                                          void* vjp_workspace, size_t vjp_ws_bytes, void* stream) {
   return vjp_impl(B, T, n, S, inhomog, pair_batched, options, J12, g_lognorm, g_E_node_diagxx, g_E_node_x, g_E_init, g_E_pair,
-                  g_samples, eps, samples, E_pair, E_node_x, g_node_J, g_node_h, nullptr, workspace, ws_bytes,
+                  g_samples, eps, samples, E_pair, E_node_x, g_node_J, g_node_h, nullptr, nullptr, workspace, ws_bytes,
                   vjp_workspace, vjp_ws_bytes, stream);
 }
 
@@ -656,8 +657,47 @@ extern "C" int svae_lds_estep_vjp_dense_f64(int B, int T, int n, int S, int inho
                                             void* vjp_workspace, size_t vjp_ws_bytes, void* stream) {
   if (!g_node_J_dense) return -27;
   return vjp_impl(B, T, n, S, inhomog, pair_batched, options, J12, g_lognorm, g_E_node_diagxx, g_E_node_x, g_E_init, g_E_pair,
-                  g_samples, eps, samples, E_pair, E_node_x, g_node_J, g_node_h, g_node_J_dense, workspace, ws_bytes,
+                  g_samples, eps, samples, E_pair, E_node_x, g_node_J, g_node_h, g_node_J_dense, nullptr, workspace, ws_bytes,
                   vjp_workspace, vjp_ws_bytes, stream);
+}
+
+extern "C" int svae_lds_param_grad_launch(int B, int T, int n, int inhomog, int pair_batched, const double* g_P,
+                                          const double* g_R, const double* g_node_h, const double* g_lognorm, double* part,
+                                          double* g_init_J, double* g_init_h, double* g_init_logZ, double* g_J11,
+                                          double* g_J12, double* g_J22, double* g_logZ_pair, void* stream);
+
+extern "C" size_t svae_lds_param_vjp_workspace_bytes(int B, int T, int n, int inhomog, int pair_batched) {
+  if (B <= 0 || T <= 0 || n <= 0 || n > SVAE_LDS_MAX_N) return 0;
+  (void)pair_batched;
+  return (size_t)(svae::pg_gp_doubles(B, T, n) + svae::pg_gr_doubles(B, T, n) + svae::pg_part_doubles(T, n, inhomog)) * sizeof(double);
+}
+
+extern "C" int svae_lds_estep_vjp_params_f64(int B, int T, int n, int S, int inhomog, int pair_batched, unsigned options,
+                                             const double* J12, const double* g_lognorm,
+                                             const double* g_E_node_diagxx, const double* g_E_node_x,
+                                             const double* g_E_init, const double* g_E_pair,
+                                             const double* g_samples, const double* eps,
+                                             const double* samples, const double* E_pair,
+                                             const double* E_node_x, double* g_node_J, double* g_node_h,
+                                             double* g_init_J, double* g_init_h, double* g_init_logZ,
+                                             double* g_J11, double* g_J12, double* g_J22, double* g_logZ_pair,
+                                             const void* workspace, size_t ws_bytes,
+                                             void* vjp_workspace, size_t vjp_ws_bytes,
+                                             void* param_workspace, size_t param_ws_bytes, void* stream) {
+  const size_t need = svae_lds_param_vjp_workspace_bytes(B, T, n, inhomog, pair_batched);
+  /* (need == 0: B = 0, or sizes that vjp_impl refuses with their own codes) */
+  if (need > 0 && (!param_workspace || param_ws_bytes < need)) return -29;
+  if (B > 0 && T > 65536) return -30;           /* (one workgroup row per step in the reduction's grid) */
+  double* g_P = (double*)param_workspace;
+  double* g_R = need > 0 ? g_P + svae::pg_gp_doubles(B, T, n) : nullptr;
+  double* part = need > 0 ? g_R + svae::pg_gr_doubles(B, T, n) : nullptr;
+  const int rc = vjp_impl(B, T, n, S, inhomog, pair_batched, options, J12, g_lognorm, g_E_node_diagxx, g_E_node_x, g_E_init, g_E_pair,
+                          g_samples, eps, samples, E_pair, E_node_x, g_node_J, g_node_h, g_P, g_R, workspace, ws_bytes,
+                          vjp_workspace, vjp_ws_bytes, stream);
+  if (rc != 0 || B == 0) return rc;
+  const int rr = svae_lds_param_grad_launch(B, T, n, inhomog, pair_batched, g_P, g_R, g_node_h, g_lognorm, part,
+                                            g_init_J, g_init_h, g_init_logZ, g_J11, g_J12, g_J22, g_logZ_pair, stream);
+  return rr;
 }
 
 extern "C" int svae_lds_estep_vjp_f64(int B, int T, int n, int S, const double* J12,

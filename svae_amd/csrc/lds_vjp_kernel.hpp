@@ -906,8 +906,15 @@ __global__ __launch_bounds__(64 * VJP_S1_WAVES) void lds_vjp_sweep1_prod_kernel(
 // from HBM, ~2 us away, against ~0.9 us of arithmetic; the consumer's registers cannot hold enough steps in flight.
 // The producer can: it keeps PD steps of records in its own registers (it does nothing else), publishes the oldest into
 // an LDS ring of two slots each step, and the consumer reads its operands from LDS.  One s_barrier per step.
-template <int N, bool SAMP, bool SPLIT, bool PROD>
+// PGR (packed launches of svae_lds_estep_vjp_params_f64 only): the step also leaves what the cotangents of the init / pair
+// natural parameters are made of -- -2 Pbar_t in g_P (J11_t, J22_{t-1}, init_J all enter P_t alone) and, for t < T-1, the
+// two halves of Rbar_t = Bbar[:, :n] - H_t [Abar | hbar]_{t+1}' (R_t = -J12_t enters H_t = P^-1 [R | hf] and
+// [Jpred | hpred]_{t+1} = -R' H_t) in g_R: Bbar[:, :n] as it stands and [Abar | hbar]_{t+1} H_t' = the TRANSPOSE of the
+// product (lane c holds row c of H: the product comes out in this orientation without a transposition); lds_param_grad.hip
+// puts them together.  The other instantiations are untouched.
+template <int N, bool SAMP, bool SPLIT, bool PROD, bool PGR = false>
 __device__ __forceinline__ void lds_vjp_sweep2_body(const VjpArgs& a) {
+  static_assert(!(PGR && PROD), "the packed sweep writes the parameter cotangents");
   constexpr int HS = ws_h_stride(N), PS = ws_p_stride(N), WS = ws_step_doubles(N);
   constexpr int AS = vjp_step_doubles(N);
   constexpr int REC = WS + AS;                 // doubles per (sequence, step) in a ring slot
@@ -1062,6 +1069,15 @@ __device__ __forceinline__ void lds_vjp_sweep2_body(const VjpArgs& a) {
     mm_ab<N, N, false>(Bb, Pi, Xc);
     // Pbar = [-P^-1 Pinvbar P^-1: from sweep 1] - Bbar H' - 1/2 g (c c' + P^-1) [+ direct]
     mm_ab<N, N + 1, true>(Pb, Bb, HT);
+    if constexpr (PGR) {
+      if (t < T - 1) {
+        double Rt[N];                                            // [Abar | hbar]_{t+1} H_t'  (Ab: still step t+1's)
+        static_for<0, N>([&](auto i) { Rt[i] = 0.0; });
+        mm_ab<N, N + 1, false>(Rt, Ab, HT);
+        double* gr = a.g_R + ((((long)b * (T - 1) + t) * 2) * N) * N + c;
+        if (valid && col) static_for<0, N>([&](auto i) { gr[i * N] = Bb[i]; gr[(N + i) * N] = Rt[i]; });
+      }
+    }
     double cvs = -0.5 * g * HT[N];
     dpp_fence(cvs);
     static_for<0, N>([&](auto i) {
@@ -1081,7 +1097,7 @@ __device__ __forceinline__ void lds_vjp_sweep2_body(const VjpArgs& a) {
     dpp_fence(Ab);
     static_for<0, N>([&](auto i) { mac_bc<N>(gh, Ab[i], E[i]); });
     if (sink == 1.2345e300) gJ += sink;                        // keeps the touches alive; never true
-    if (valid && col) {
+    if (valid && col && !(PGR && a.pg_only)) {
       a.g_node_J[((long)b * T + t) * N + c] = -2.0 * gJ;
       a.g_node_h[((long)b * T + t) * N + c] = gh;
     }
@@ -1364,9 +1380,9 @@ __global__ __launch_bounds__(128) void lds_vjp_sweep2_s4_kernel(const VjpArgs a)
   }
 }
 
-template <int N, bool SAMP, bool SPLIT>
+template <int N, bool SAMP, bool SPLIT, bool PGR = false>
 __global__ __launch_bounds__(64) void lds_vjp_sweep2_kernel(const VjpArgs a) {
-  lds_vjp_sweep2_body<N, SAMP, SPLIT, false>(a);
+  lds_vjp_sweep2_body<N, SAMP, SPLIT, false, PGR>(a);
 }
 // consumer wavefront + four producer wavefronts
 template <int N, bool SAMP, bool SPLIT>
@@ -1376,10 +1392,17 @@ __global__ __launch_bounds__(320) void lds_vjp_sweep2_prod_kernel(const VjpArgs 
 
 constexpr int VJP_PROD2_MAX_N = 12;     // sweep 2 with producers: beyond, the ring exceeds 64 KB and the consumer spills
 template <int N>
-static int launch_vjp(const VjpArgs& a, hipStream_t stream) {
+static int launch_vjp(const VjpArgs& a_in, hipStream_t stream) {
+  VjpArgs a = a_in;
   dim3 grid((a.B + 3) / 4), grid2(2 * ((a.B + 3) / 4)), block(64);
   const bool statc = a.g_E_init || a.g_E_pair;
-  if (a.g_P && a.prod_max_b > 0) return -1001;       // (the dispatcher asks for the packed sweeps: only they write g_P)
+  // Parameter cotangents (g_R, with g_P): sweep 1 and sweep 2 run exactly as they would without them, so g_node_J /
+  // g_node_h keep their bits; where that sweep 2 is not the packed one (producer / one-sequence launches of small
+  // batches), the packed sweep follows as a second pass that writes g_P / g_R only.
+  const bool pg = a.g_R != nullptr;
+  if (pg && !a.g_P) return -1002;
+  if (pg) a.g_P = a.g_R = nullptr;          // (the ordinary launches below; the PGR launch takes a_in)
+  if (!pg && a.g_P && a.prod_max_b > 0) return -1001;       // (the dispatcher asks for the packed sweeps: only they write g_P)
   // two roles while 2 wavefronts per 4 sequences still find idle SIMDs (the sampler role hands its share of G^ to
   // sweep 2 as per-sample factors: room for VJP_SPLIT_MAX_S of them in the scratch record)
   const bool split = a.B <= 2048 && a.S <= VJP_SPLIT_MAX_S;
@@ -1401,7 +1424,15 @@ static int launch_vjp(const VjpArgs& a, hipStream_t stream) {
         done2 = true;
       }
     }
-    if (done2) {}
+    if (pg) {
+      // parameter cotangents: the packed sweep 2 in its PGR form -- alone where the launch above would have been the
+      // packed one, else as a second pass that leaves the node gradients of the first alone
+      VjpArgs q = a_in;
+      q.pg_only = done2 ? 1 : 0;
+      if (split) hipLaunchKernelGGL((lds_vjp_sweep2_kernel<N, true, true, true>), grid, block, 0, stream, q);
+      else hipLaunchKernelGGL((lds_vjp_sweep2_kernel<N, true, false, true>), grid, block, 0, stream, q);
+    }
+    else if (done2) {}
     else if (split) hipLaunchKernelGGL((lds_vjp_sweep2_kernel<N, true, true>), grid, block, 0, stream, a);
     else hipLaunchKernelGGL((lds_vjp_sweep2_kernel<N, true, false>), grid, block, 0, stream, a);
   } else {
@@ -1422,7 +1453,12 @@ static int launch_vjp(const VjpArgs& a, hipStream_t stream) {
         done2 = true;
       }
     }
-    if (!done2) hipLaunchKernelGGL((lds_vjp_sweep2_kernel<N, false, false>), grid, block, 0, stream, a);
+    if (pg) {
+      VjpArgs q = a_in;
+      q.pg_only = done2 ? 1 : 0;
+      hipLaunchKernelGGL((lds_vjp_sweep2_kernel<N, false, false, true>), grid, block, 0, stream, q);
+    }
+    else if (!done2) hipLaunchKernelGGL((lds_vjp_sweep2_kernel<N, false, false>), grid, block, 0, stream, a);
   }
   return hipGetLastError() == hipSuccess ? 0 : -1000;
 }

@@ -302,7 +302,7 @@ class LDSEStepPlan(object):
         return out
 
     def vjp(self, g_lognorm, g_E_node_diagxx=None, g_E_node_x=None, g_samples=None, eps=None,
-            samples=None, g_E_init=None, g_E_pair=None, dense_out=None):
+            samples=None, g_E_init=None, g_E_pair=None, dense_out=None, param_out=False):
         """Vector-Jacobian product w.r.t. the node potentials of the last
         `launch(..., keep_factor=True, keep_cross=True)` [+ `sample`]: returns (g_node_J, g_node_h)
         (B,T,n) each; g_node_logZ[b,t] = g_lognorm[b].  Replaces the reference's natural_filter_grad /
@@ -310,9 +310,21 @@ class LDSEStepPlan(object):
         (cython_lds_inference.pyx:92-145, 236-306, 357-409).  g_E_init (B, n*n+n) and, with per-step
         pair parameters, g_E_pair (B,T-1,3,n,n) are the cotangents of the remaining statistics
         (_compute_stats_grad, :212-234) -- what the SLDS-SVAE differentiates.  dense_out (B,T,n,n): also receives
-        -2 Pbar_t, the (unsymmetrised) cotangent of a DENSE node potential J_t (svae_lds_estep_vjp_dense_f64)."""
+        -2 Pbar_t, the (unsymmetrised) cotangent of a DENSE node potential J_t (svae_lds_estep_vjp_dense_f64).
+        param_out=True (n <= 15, full records): returns (g_node_J, g_node_h, (g_init_J, g_init_h, g_init_logZ, g_J11,
+        g_J12, g_J22, g_logZ_pair)) -- the cotangents of the natural parameters in the layout of the launch, summed over
+        what each is shared over; g_init_J / g_J11 / g_J22 symmetrised, g_J12 full (svae_lds_estep_vjp_params_f64).  The
+        node gradients are the same bits as without it."""
         self._no_xl("vjp()")
         lean = getattr(self, "lean", False)
+        if param_out:
+            if self.n > _lib.LDS_MAX_N:
+                raise ValueError("parameter gradients: latent dimension <= %d (n = %d)" % (_lib.LDS_MAX_N, self.n))
+            if lean:
+                raise ValueError("parameter gradients need the full per-step records: the last forward pass of this plan "
+                                 "kept lean ones (make the plan with options | OPT_LEAN_OFF)")
+            if dense_out is not None:
+                raise ValueError("param_out and dense_out are separate calls")
         if not (getattr(self, "has_cross", False) and (lean or getattr(self, "has_factor", False))):
             raise RuntimeError("vjp() needs a preceding launch(..., keep_factor=True, keep_cross=True) or infer()")
         if lean and (g_E_init is not None or g_E_pair is not None):
@@ -337,21 +349,47 @@ class LDSEStepPlan(object):
         if S > 16:
             # the kernels take 16 sample cotangents per launch; the VJP is linear in the cotangents: the first chunk
             # travels with all the others, the remaining chunks alone
-            gJ, gh = self.vjp(g_lognorm, g_E_node_diagxx, g_E_node_x, g_samples[:, :, :16], eps[:, :, :16],
-                              samples[:, :, :16], g_E_init, g_E_pair)
+            first = self.vjp(g_lognorm, g_E_node_diagxx, g_E_node_x, g_samples[:, :, :16], eps[:, :, :16],
+                             samples[:, :, :16], g_E_init, g_E_pair, param_out=param_out)
+            gJ, gh = first[0], first[1]
             zero = torch.zeros_like(g_lognorm)
             for s0 in range(16, S, 16):
-                aJ, ah = self.vjp(zero, None, None, g_samples[:, :, s0:s0 + 16], eps[:, :, s0:s0 + 16],
-                                  samples[:, :, s0:s0 + 16])
-                gJ += aJ
-                gh += ah
-            return gJ, gh
+                more = self.vjp(zero, None, None, g_samples[:, :, s0:s0 + 16], eps[:, :, s0:s0 + 16],
+                                samples[:, :, s0:s0 + 16], param_out=param_out)
+                gJ += more[0]
+                gh += more[1]
+                if param_out:
+                    for x, y in zip(first[2], more[2]):
+                        x += y
+            return (gJ, gh, first[2]) if param_out else (gJ, gh)
         if not hasattr(self, "vjp_ws"):
             self.vjp_ws_bytes = int(self.lib.svae_lds_vjp_workspace_bytes(max(self.B, 1), self.T, self.n))
             self.vjp_ws = torch.empty(self.vjp_ws_bytes // 8, **f64)
         gJ = torch.empty(self.B, self.T, self.n, **f64)
         gh = torch.empty(self.B, self.T, self.n, **f64)
         p = _lib.ptr
+        if param_out:
+            B, T, n = self.B, self.T, self.n
+            pb = bool(self._pair_batched)
+            if not hasattr(self, "param_ws"):
+                self.param_ws_bytes = int(self.lib.svae_lds_param_vjp_workspace_bytes(max(B, 1), T, n, int(self.inhomog), int(pb)))
+                self.param_ws = torch.empty(self.param_ws_bytes // 8, **f64)
+            lead = ((B, max(T - 1, 0)) if pb else (max(T - 1, 0),)) if self.inhomog else ()
+            out = (torch.empty(n, n, **f64), torch.empty(n, **f64), torch.empty(1, **f64),
+                   torch.empty(*lead, n, n, **f64), torch.empty(*lead, n, n, **f64), torch.empty(*lead, n, n, **f64),
+                   torch.empty(*lead, **f64) if self.inhomog else torch.empty(1, **f64))
+            rc = self.lib.svae_lds_estep_vjp_params_f64(
+                B, T, n, S, int(self.inhomog), int(pb), options,
+                p(self._J12), p(g_lognorm), p(g_E_node_diagxx), p(g_E_node_x), p(g_E_init), p(g_E_pair),
+                p(g_samples), p(eps), p(samples), p(self.E_pair), p(self.E_node_x), p(gJ), p(gh),
+                *[p(x) for x in out],
+                p(self.ws), self.ws_bytes, p(self.vjp_ws), self.vjp_ws_bytes, p(self.param_ws), self.param_ws_bytes,
+                _lib.current_stream(self.device))
+            _lib.check(rc, "svae_lds_estep_vjp_params_f64")
+            if B == 0:
+                for x in out:
+                    x.zero_()
+            return gJ, gh, out
         if dense_out is not None:
             if S > 16 or lean:
                 raise ValueError("dense node-potential cotangents: at most 16 sample cotangents, full records")
@@ -857,6 +895,37 @@ class _LDSInference(torch.autograd.Function):
         return gJ, gh, gz, None, None, None, None
 
 
+class _LDSInferenceParams(torch.autograd.Function):
+    """_LDSInference with the seven natural parameters (init_J, init_h, init_logZ, J11, J12, J22, logZ_pair) as
+    differentiable inputs too -- the gradients the reference's Python path has through autograd (lds_inference.py:205-218).
+    Forward: the same launches; backward: the same sweeps plus the parameter blocks of the packed second sweep and their
+    deterministic reduction (svae_lds_estep_vjp_params_f64).  n <= 15, full records."""
+
+    @staticmethod
+    def forward(ctx, node_J, node_h, node_logZ, eps, plan, pair_batched, *params):
+        ctx.param_shapes = [tuple(x.shape) for x in params]
+        return _LDSInference.forward(ctx, node_J, node_h, node_logZ, eps, plan, tuple(x.detach() for x in params), pair_batched)
+
+    @staticmethod
+    def backward(ctx, g_lognorm, g_dxx, g_x, g_samples, g_init, g_pair):
+        plan = ctx.plan
+        if plan.epoch != ctx.epoch:
+            raise RuntimeError("LDSEStepPlan was launched again before backward(): the hand-off workspace of "
+                               "this forward pass is gone (use one plan per live autograd graph, or call "
+                               "backward before the next forward)")
+        eps, samples = ctx.saved_tensors
+        g_lognorm = torch.zeros_like(plan.lognorm) if g_lognorm is None else g_lognorm
+        gs = g_samples if (ctx.has_samples and g_samples is not None) else None
+        if not plan.inhomog:
+            g_init = g_pair = None
+        gJ, gh, gp = plan.vjp(g_lognorm, g_dxx, g_x, gs, eps if gs is not None else None,
+                              samples if gs is not None else None, g_init, g_pair, param_out=True)
+        gz = g_lognorm[:, None].expand(plan.B, plan.T).clone() if ctx.has_logZ else None
+        need = ctx.needs_input_grad[6:]
+        gp = tuple(g.reshape(shape) if want else None for g, shape, want in zip(gp, ctx.param_shapes, need))
+        return (gJ, gh, gz, None, None, None) + gp
+
+
 class _LDSInferenceDense(torch.autograd.Function):
     """E-step + sampler with DENSE node potentials J (B,T,n,n) -- the reference's Python path, differentiable end to end
     there (lds_inference.py:65-82, 205-218) -- differentiable w.r.t. (J, h[, logZ]).  Forward: the off-diagonal part of
@@ -918,7 +987,64 @@ def _dense_inference_differentiable(natparam, node_params, eps):
     return lognorm, (ExxT, ex), (samples if eps is not None else None), (E_init, E_pair)
 
 
-def lds_inference_differentiable(natparam, node_params, eps=None, plan=None, pair_stats_grad=False):
+def _natparam_inference_differentiable(natparam, node_params, eps, plan, pair_stats_grad):
+    """lds_inference_differentiable(..., natparam_grad=True): the parameters stay in the autograd graph on their way to
+    the kernels' layout (device, float64, contiguous; the init logZ terms summed; (n,n) blocks repeated over time for
+    pair_stats_grad), so the cotangents the kernels return in that layout reach the caller's tensors through torch."""
+    init_params, pair_params = natparam
+    node_J, node_h = node_params[0], node_params[1]
+    node_logZ = node_params[2] if len(node_params) == 3 else None
+    if not (isinstance(node_h, torch.Tensor) and isinstance(node_J, torch.Tensor)) or node_h.dim() != 3 \
+            or node_J.shape != node_h.shape:
+        raise ValueError("natparam_grad=True: diagonal node potentials J, h of shape (B,T,n)")
+    B, T, n = node_h.shape
+    if n > _lib.LDS_MAX_N:
+        raise ValueError("natparam_grad=True: latent dimension <= %d (n = %d)" % (_lib.LDS_MAX_N, n))
+    dev = node_h.device
+
+    def keep(x):
+        if not isinstance(x, torch.Tensor):
+            x = torch.as_tensor(x, dtype=torch.float64)
+        return x.to(device=dev, dtype=torch.float64)
+    init_J, init_h = keep(init_params[0]), keep(init_params[1])
+    init_logZ = sum(keep(z).reshape(()) for z in init_params[2:]) if len(init_params) > 2 \
+        else torch.zeros((), dtype=torch.float64, device=dev)
+    init_logZ = init_logZ.reshape(1)
+    if tuple(init_J.shape) != (n, n) or tuple(init_h.shape) != (n,):
+        raise ValueError("init_params shapes do not match the node potentials")
+    J11, J12, J22 = (keep(x) for x in pair_params[:3])
+    logZ_pair = keep(pair_params[3]).reshape(-1)
+    inhomog, pair_batched = J11.dim() >= 3, J11.dim() == 4
+    want = {2: (n, n), 3: (T - 1, n, n), 4: (B, T - 1, n, n)}.get(J11.dim())
+    if want is None or any(tuple(x.shape) != want for x in (J11, J12, J22)):
+        raise ValueError("pair_params must be (n,n), (T-1,n,n) or (B,T-1,n,n)")
+    if logZ_pair.numel() != (1 if not inhomog else (B * (T - 1) if pair_batched else T - 1)):
+        raise ValueError("pair logZ must have one entry per pair block")
+    sum_pairs = bool(pair_stats_grad) and not inhomog
+    if sum_pairs:
+        J11, J12, J22 = (x.expand(max(T - 1, 0), n, n) for x in (J11, J12, J22))
+        logZ_pair = logZ_pair.expand(max(T - 1, 0))
+        inhomog = True
+    if plan is None:
+        word = _guarded_plan_options(pair_params, np.ndim(pair_params[0]) != 2)
+        word = _default_options if word is None else word
+        plan = LDSEStepPlan(B, T, n, dev, inhomog, pair_batched, options=(word & ~_lib.OPT_LEAN_ON) | _lib.OPT_LEAN_OFF)
+    elif (plan.B, plan.T, plan.n, plan.inhomog) != (B, T, n, inhomog):
+        raise ValueError("plan shape / layout mismatch (pair_stats_grad=True needs a per-step plan: inhomog=True)")
+    S = 0 if eps is None else int(eps.shape[2])
+    if S <= 16 and plan.lib.svae_lds_inference_is_lean(B, T, n, S, int(inhomog), 1, plan.options):
+        raise ValueError("natparam_grad=True needs the full per-step records: this plan's options keep lean ones for this "
+                         "shape (make the plan with options | OPT_LEAN_OFF)")
+    cont = lambda x: None if x is None else x.to(torch.float64).contiguous()
+    params = tuple(x.contiguous() for x in (init_J, init_h, init_logZ, J11, J12, J22, logZ_pair))
+    out = _LDSInferenceParams.apply(cont(node_J), cont(node_h), cont(node_logZ), cont(eps), plan, pair_batched, *params)
+    lognorm, dxx, ex, samples, E_init, E_pair = out
+    if sum_pairs:
+        E_pair = E_pair.sum(1)
+    return lognorm, (dxx, ex), (samples if eps is not None else None), (E_init, E_pair)
+
+
+def lds_inference_differentiable(natparam, node_params, eps=None, plan=None, pair_stats_grad=False, natparam_grad=False):
     """(lognorm (B), (E_node_diagxx, E_node_x) (B,T,n), samples (B,T,S,n) | None, (E_init, E_pair)):
     differentiable w.r.t. node_params = (J (B,T,n), h (B,T,n)[, logZ (B,T)]) through torch autograd.
     Dense node potentials J (B,T,n,n) (the reference's Python path) are accepted too: the first statistic is then the full
@@ -932,7 +1058,17 @@ def lds_inference_differentiable(natparam, node_params, eps=None, plan=None, pai
     uses the per-step layout with the (n,n) parameters repeated over time (T-1 copies, L2-resident), and the
     sum over time is a torch reduction whose backward broadcasts the cotangent to the per-step blocks the
     VJP kernel consumes.  Costs the per-step statistics' HBM traffic, so it is opt-in (no model of the
-    reference differentiates these: svae.py:21 keeps them in `saved.stats`)."""
+    reference differentiates these: svae.py:21 keeps them in `saved.stats`).
+
+    natparam_grad=True (n <= 15) lets autograd flow into the natural parameters as well: whichever of init_J, init_h, the
+    init logZ terms, J11, J12, J22 and the pair logZ are tensors that require grad receive their gradient -- a shared
+    (n,n) parameter the sum over batch and time, a (T-1,n,n) one the sum over the batch.  The gradients of init_J / J11 /
+    J22 are symmetric matrices (the forward pass reads the symmetric part), that of J12 is a full one.  The call runs on
+    the full per-step records: a plan made here has the lean records switched off; a caller's plan that would keep lean
+    records raises ValueError.  The node gradients and (up to 1024 sequences) the forward outputs are the same bits as
+    without the flag."""
+    if natparam_grad:
+        return _natparam_inference_differentiable(natparam, node_params, eps, plan, pair_stats_grad)
     init_params, pair_params = natparam
     node_J, node_h = node_params[0], node_params[1]
     node_logZ = node_params[2] if len(node_params) == 3 else None
