@@ -770,6 +770,84 @@ int svae_lds_sample_vjp_f64(int B, int T, int n, int S, int inhomog, int pair_ba
                             double* g_J_pred, double* g_h_pred, double* g_J_filt, double* g_h_filt,
                             int32_t* info, void* stream);
 
+/* ---- Variable-length sequences in one batch: per-sequence lengths, n <= SVAE_LDS_MAX_N (csrc/lds_estep.hip) -----------
+ * The reference runs one sequence per call (natural_filter_forward_general svae/lds/cython_lds_inference.pyx:28-90,
+ * natural_smoother_general + _compute_stats :149-210, natural_sample_backward :310-355), so every sequence there has its
+ * own length; these entries give the batch axis the same freedom: `lengths` (B) int32 on the device, sequence b occupying
+ * steps 0 .. lengths[b]-1 of its (T, n) rows.  Pair and init parameters shared by the batch ((n,n) blocks; `inhomog` and
+ * `pair_batched` must be 0), diagonal node potentials (B,T,n).
+ *
+ * Sequence b of length L runs as a chain of T steps whose pairs t <= L-2 carry the real (J11, J12, J22, logZ) and whose
+ * pairs t >= L-1 carry the decoupling set Q = (0, 0, -1/2 I, 0), with zero node potentials from step L on: the tail is a
+ * chain of independent standard normals, detached from the real steps -- the last real node sees no J11 term, every tail
+ * step adds exactly 0 to the log-normaliser -- so all rows of a wavefront keep one trip count.  (Padding with zero node
+ * potentials and the REAL pair parameters is not exact: an expected-statistics pair potential is no normalised conditional.)
+ * The kernels are the ragged instantiations of the packed one-directional E-step, samplers and VJP sweeps: the pair blocks
+ * come from two-entry tables [real | Q], entry (t <= lengths[b]-2 ? 0 : 1) per row; one route at every batch size.
+ *
+ * Contract, per sequence b with L = lengths[b]: lognorm[b], E_init[b], E_pair[b] (3,n,n: the sums over the sequence's own
+ * L-1 pairs; all zero for L = 1), E_node_*[b,:L], samples[b,:L] (for eps[b,:L]) and g_node_*[b,:L] are those of the
+ * sequence truncated to L steps; every output and gradient at t >= L is 0; node_*[b,L:], eps[b,L:] and the cotangents at
+ * t >= L are never used (they may be NaN); no result of sequence b depends on another sequence's length.
+ * A length outside 1..T is device data: it raises the status word `info` (b+1, like a non-positive pivot) and is clamped
+ * to 1..T for addressing.
+ *
+ * Workspace: the layout of svae_lds_workspace_bytes(B,T,n), then (256-byte aligned) the pair tables, 6 n^2 doubles. */
+size_t svae_lds_ragged_workspace_bytes(int B, int T, int n);
+
+/* svae_lds_estep_f64 with per-sequence lengths.  keep: bit 0 the factor region (sampler), bit 1 the cross moments (VJP).
+ * options: a valid SVAE_OPT_* word (-24 otherwise); it selects nothing here.  Returns 0, or before any HIP call: -1 B,
+ * -2 T, -3 n outside 1..SVAE_LDS_MAX_N, -32 inhomog / pair_batched, -31 lengths NULL, -23 keep, -6.. -21 NULL pointers as
+ * svae_lds_estep_f64, -24 options, -22 workspace NULL or shorter than svae_lds_ragged_workspace_bytes; B = 0 returns 0
+ * after the checks up to options. */
+int svae_lds_ragged_estep_f64(int B, int T, int n, int inhomog, int pair_batched, int keep, unsigned options,
+                              const double* init_J, const double* init_h, const double* init_logZ,
+                              const double* J11, const double* J12, const double* J22, const double* logZ_pair,
+                              const double* node_J, const double* node_h, const double* node_logZ,
+                              const int32_t* lengths,
+                              double* lognorm, double* E_init, double* E_pair,
+                              double* E_node_diagxx, double* E_node_x,
+                              int32_t* info, void* workspace, size_t ws_bytes, void* stream);
+
+/* svae_lds_inference_f64 with per-sequence lengths: the ragged E-step keeping the factor (S > 0) and, keep_vjp = 1, the
+ * cross moments, then the ragged sampler.  Full per-step records at every batch size.  Error codes of
+ * svae_lds_ragged_estep_f64; -4 for S < 0 or S > 0 without eps / samples; -23 keep_vjp outside {0, 1}. */
+int svae_lds_ragged_inference_f64(int B, int T, int n, int S, int inhomog, int pair_batched, int keep_vjp, unsigned options,
+                                  const double* init_J, const double* init_h, const double* init_logZ,
+                                  const double* J11, const double* J12, const double* J22, const double* logZ_pair,
+                                  const double* node_J, const double* node_h, const double* node_logZ,
+                                  const int32_t* lengths, const double* eps, double* samples,
+                                  double* lognorm, double* E_init, double* E_pair,
+                                  double* E_node_diagxx, double* E_node_x,
+                                  int32_t* info, void* workspace, size_t ws_bytes, void* stream);
+
+/* The VJP sweeps (svae_lds_estep_vjp_ex_f64) w.r.t. the node potentials on the records of the last
+ * svae_lds_ragged_estep_f64 (keep = 3) / svae_lds_ragged_inference_f64 (keep_vjp = 1) call with the same (B,T,n) and
+ * `lengths`; the J12 table is read from `workspace`.  Cotangents of lognorm (B), E_node_diagxx / E_node_x (B,T,n or NULL)
+ * and samples (B,T,S,n or NULL, S <= 16, with eps and samples).  g_node_logZ[b,t] = g_lognorm[b] for t < lengths[b], else 0
+ * (host side).  Returns 0, or before any HIP call: -1, -2, -3, -32, -31 as above, -4 S, -6 g_lognorm, -10 eps / samples,
+ * -12 / -13 outputs, -24 options, -14 workspace short, -16 vjp_workspace shorter than svae_lds_vjp_workspace_bytes. */
+int svae_lds_ragged_vjp_f64(int B, int T, int n, int S, int inhomog, int pair_batched, unsigned options,
+                            const double* g_lognorm, const double* g_E_node_diagxx, const double* g_E_node_x,
+                            const double* g_samples, const double* eps, const double* samples,
+                            const int32_t* lengths, double* g_node_J, double* g_node_h,
+                            const void* workspace, size_t ws_bytes,
+                            void* vjp_workspace, size_t vjp_ws_bytes, void* stream);
+
+/* svae_lds_reduce_stats_f64 for a ragged batch: the same fixed-order sums and one more slot, the number of pairs behind the
+ * E_pair sums (the uniform consumers derive it as count (T-1), which is wrong here):
+ *   out (4 n^2 + n + 3) = [sum_b E_init | sum_b E_pair | sum_b lognorm | B | sum_b (lengths[b] - 1)]
+ * (lengths clamped to 1..T; integer sum, exact).  -1 B, -7 T, -2 n outside 1..SVAE_LDS_MAX_N, -3.. -6 NULL pointers as
+ * svae_lds_reduce_stats_f64, -31 lengths NULL. */
+int svae_lds_ragged_reduce_stats_f64(int B, int T, int n, const double* E_init, const double* E_pair,
+                                     const double* lognorm, const int32_t* lengths, double* out, void* stream);
+
+/* svae_lds_natgrad_f64 on the (all-reduced) buffer of svae_lds_ragged_reduce_stats_f64: the MNIW count is the buffer's
+ * last slot, not count (T-1). */
+int svae_lds_ragged_natgrad_f64(int n, const double* packed_stats, const double* prior_flat,
+                                const double* params_flat, double num_batches, double scale,
+                                double* natgrad_flat, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

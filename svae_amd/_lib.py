@@ -130,6 +130,19 @@ SIGNATURES = {
     "svae_gmm_mw_fixed_point_f64": (ctypes.c_int, [ctypes.c_int] * 3 + [_c_double_p] * 5
                                     + [ctypes.c_double, ctypes.c_int] + [_c_double_p] * 8
                                     + [_c_int_p] * 3 + [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]),
+    # per-sequence lengths (n <= 15, shared pair parameters, diagonal node potentials)
+    "svae_lds_ragged_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int] * 3),
+    "svae_lds_ragged_estep_f64": (ctypes.c_int, [ctypes.c_int] * 6 + [ctypes.c_uint] + [_c_double_p] * 10 + [_c_int_p]
+                                  + [_c_double_p] * 5 + [_c_int_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]),
+    "svae_lds_ragged_inference_f64": (ctypes.c_int, [ctypes.c_int] * 7 + [ctypes.c_uint] + [_c_double_p] * 10 + [_c_int_p]
+                                      + [_c_double_p] * 7 + [_c_int_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]),
+    "svae_lds_ragged_vjp_f64": (ctypes.c_int, [ctypes.c_int] * 6 + [ctypes.c_uint] + [_c_double_p] * 6 + [_c_int_p]
+                                + [_c_double_p] * 2 + [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_size_t,
+                                                       ctypes.c_void_p]),
+    "svae_lds_ragged_reduce_stats_f64": (ctypes.c_int, [ctypes.c_int] * 3 + [_c_double_p] * 3 + [_c_int_p, _c_double_p,
+                                                                                              ctypes.c_void_p]),
+    "svae_lds_ragged_natgrad_f64": (ctypes.c_int, [ctypes.c_int] + [_c_double_p] * 3 + [ctypes.c_double] * 2
+                                    + [_c_double_p, ctypes.c_void_p]),
 }
 
 _lib = None

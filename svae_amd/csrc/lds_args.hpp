@@ -84,6 +84,9 @@ struct LdsArgs {
   double* __restrict__ sig_out;
   // tiled path (n > 15): 0 = whole E-step, 1 = forward half only, 2 = backward half only (SVAE_OPT_TILE_FORWARD / _BACKWARD)
   int tile_half;
+  // ragged launches (svae_lds_ragged_*): (B) per-sequence lengths; J11 / J12 / J22 then point at two-entry tables
+  // [real | decoupling set Q] and pair t of row b reads entry (t <= lengths[b] - 2 ? 0 : 1).  nullptr otherwise.
+  const int32_t* __restrict__ lengths = nullptr;
 };
 
 struct SampleArgs {
@@ -93,6 +96,7 @@ struct SampleArgs {
   double* __restrict__ samples;       // (B, T, S, n)
   const double* __restrict__ ws;      // main region (G~' rows, c, P^-1)
   const double* __restrict__ ws2;     // factor region
+  const int32_t* __restrict__ lengths = nullptr;   // ragged launches: (B) per-sequence lengths (eps read, samples written as 0 beyond)
 };
 
 // reverse-mode sweeps (lds_vjp_kernel.hpp)
@@ -123,6 +127,7 @@ struct VjpArgs {
   double* __restrict__ g_R;              // (B,T-1,2,n,n) or nullptr: per step [Bbar_t[:, :n] | [Abar | hbar]_{t+1} H_t'], the two halves of
                                          // Rbar_t = first - second' (lds_param_grad.hip turns them into g_J12 = -Rbar)
   int pg_only;                           // 1: that launch leaves g_node_J / g_node_h alone (another sweep 2 has written them)
+  const int32_t* __restrict__ lengths = nullptr;   // ragged launches: (B) per-sequence lengths; J12 is then the two-entry table [real | 0]
 };
 // extra scratch of svae_lds_estep_vjp_params_f64 (doubles): g_P, g_R, then -- homogeneous pair parameters -- the per-step
 // batch sums [T-1][3][n*n] that the second reduction pass adds up over time

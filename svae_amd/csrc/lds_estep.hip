@@ -22,7 +22,10 @@ extern "C" {
   int svae_lds_sample_n##NN(const svae::SampleArgs*, void*);                   \
   int svae_lds_vjp_n##NN(const svae::VjpArgs*, void*);                         \
   int svae_lds_infer_lean_n##NN(const svae::LdsArgs*, const svae::LeanSample*, int, void*); \
-  int svae_lds_vjp_lean_n##NN(const svae::VjpArgs*, void*);
+  int svae_lds_vjp_lean_n##NN(const svae::VjpArgs*, void*);                    \
+  int svae_lds_launch_ragged_n##NN(const svae::LdsArgs*, void*);               \
+  int svae_lds_sample_ragged_n##NN(const svae::SampleArgs*, void*);            \
+  int svae_lds_vjp_ragged_n##NN(const svae::VjpArgs*, void*);
 #define SVAE_DECL(NN) SVAE_DECL_(NN)
 #ifdef SVAE_ONLY_N   /* experimental single-n builds (tools/build_variant.sh) */
 SVAE_DECL(SVAE_ONLY_N)
@@ -712,4 +715,210 @@ extern "C" int svae_lds_estep_vjp_f64(int B, int T, int n, int S, const double* 
                                            g_node_J, g_node_h, workspace, ws_bytes, vjp_workspace,
                                            vjp_ws_bytes, stream);
   return rc == -12 ? -12 : rc;
+}
+
+// ---- per-sequence lengths (svae_lds_ragged_*) ----------------------------------------------------------------------
+// Sequence b of length L = lengths[b] inside the padded length T is the chain whose pairs t <= L-2 carry the real pair
+// parameters and whose pairs t >= L-1 carry the decoupling set Q = (0, 0, -1/2 I, 0), with zero node potentials from step L
+// on (lds_estep_kernel.hpp, RAG).  The kernels read the pair blocks from two-entry tables [real | Q] that a one-workgroup
+// kernel leaves behind the workspace of the uniform entry points; the VJP finds its J12 table there.  One route at every
+// batch size: the packed one-directional E-step (full records), the packed samplers and the packed sweeps.
+namespace svae {
+
+// tab = [J11 | 0] [J12 | 0] [J22 | -1/2 I]  (6 n^2 doubles); T = 1: no pair parameters (NULL), the real entries are 0
+__global__ __launch_bounds__(256) void lds_ragged_tables_kernel(int n, const double* J11, const double* J12,
+                                                                 const double* J22, double* tab) {
+  const int nn = n * n;
+  for (int e = threadIdx.x; e < nn; e += blockDim.x) {
+    tab[e] = J11 ? J11[e] : 0.0;
+    tab[nn + e] = 0.0;
+    tab[2 * nn + e] = J12 ? J12[e] : 0.0;
+    tab[3 * nn + e] = 0.0;
+    tab[4 * nn + e] = J22 ? J22[e] : 0.0;
+    tab[5 * nn + e] = (e / n == e % n) ? -0.5 : 0.0;
+  }
+}
+
+// out[slot] = sum_b (clamp(lengths[b], 1, T) - 1): integer partial sums in a fixed tree, exact in any order
+__global__ __launch_bounds__(256) void lds_ragged_pair_count_kernel(int B, int T, const int32_t* lengths, double* out) {
+  __shared__ long long red[256];
+  long long acc = 0;
+  for (int b = threadIdx.x; b < B; b += 256) {
+    const int l = lengths[b];
+    acc += (l < 1 ? 1 : (l > T ? T : l)) - 1;
+  }
+  red[threadIdx.x] = acc;
+  __syncthreads();
+  for (int s = 128; s > 0; s >>= 1) {
+    if ((int)threadIdx.x < s) red[threadIdx.x] += red[threadIdx.x + s];
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) out[0] = (double)red[0];
+}
+
+}  // namespace svae
+
+static size_t ragged_table_offset_bytes(int B, int T, int n) { return (svae_lds_workspace_bytes(B, T, n) + 255) / 256 * 256; }
+
+extern "C" size_t svae_lds_ragged_workspace_bytes(int B, int T, int n) {
+  if (B <= 0 || T <= 0 || n <= 0 || n > SVAE_LDS_MAX_N) return 0;
+  return ragged_table_offset_bytes(B, T, n) + (size_t)6 * n * n * sizeof(double);
+}
+
+#define SVAE_RAGGED_SWITCH(FN, ...)                                                                      \
+  switch (n) {                                                                                           \
+    case 1: return FN##1(__VA_ARGS__);   case 2: return FN##2(__VA_ARGS__);   case 3: return FN##3(__VA_ARGS__);    \
+    case 4: return FN##4(__VA_ARGS__);   case 5: return FN##5(__VA_ARGS__);   case 6: return FN##6(__VA_ARGS__);    \
+    case 7: return FN##7(__VA_ARGS__);   case 8: return FN##8(__VA_ARGS__);   case 9: return FN##9(__VA_ARGS__);    \
+    case 10: return FN##10(__VA_ARGS__); case 11: return FN##11(__VA_ARGS__); case 12: return FN##12(__VA_ARGS__);  \
+    case 13: return FN##13(__VA_ARGS__); case 14: return FN##14(__VA_ARGS__); case 15: return FN##15(__VA_ARGS__);  \
+  }
+
+#ifndef SVAE_ONLY_N
+extern "C" int svae_lds_ragged_estep_f64(int B, int T, int n, int inhomog, int pair_batched, int keep, unsigned options,
+                                         const double* init_J, const double* init_h, const double* init_logZ,
+                                         const double* J11, const double* J12, const double* J22, const double* logZ_pair,
+                                         const double* node_J, const double* node_h, const double* node_logZ,
+                                         const int32_t* lengths,
+                                         double* lognorm, double* E_init, double* E_pair,
+                                         double* E_node_diagxx, double* E_node_x,
+                                         int32_t* info, void* workspace, size_t ws_bytes, void* stream) {
+  if (B < 0) return -1;
+  if (T < 1) return -2;
+  if (n < 1 || n > SVAE_LDS_MAX_N) return -3;
+  if (inhomog || pair_batched) return -32;       /* pair parameters shared by the batch and by the steps */
+  if (!lengths) return -31;
+  if ((keep & ~3) != 0) return -23;
+  if (!init_J) return -6;
+  if (!init_h) return -7;
+  if (!init_logZ) return -8;
+  if (T > 1 && (!J11 || !J12 || !J22 || !logZ_pair)) return -9;
+  if (!node_J) return -13;
+  if (!node_h) return -14;
+  if (!lognorm) return -16;
+  if (!E_init) return -17;
+  if (!E_pair) return -18;
+  if (!E_node_diagxx) return -19;
+  if (!E_node_x) return -20;
+  if (!info) return -21;
+  Selection sel;
+  if (!decode_options(options, B, &sel)) return -24;      /* (a valid word; the ragged dispatcher has one route) */
+  if (B == 0) return 0;
+  if (!workspace || ws_bytes < svae_lds_ragged_workspace_bytes(B, T, n)) return -22;
+  double* tab = (double*)((char*)workspace + ragged_table_offset_bytes(B, T, n));
+  hipLaunchKernelGGL(svae::lds_ragged_tables_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, n, J11, J12, J22, tab);
+  if (hipGetLastError() != hipSuccess) return -1000;
+  const long nn = (long)n * n;
+  svae::LdsArgs a;
+  a.tile_half = 0;
+  a.B = B; a.T = T;
+  a.init_J = init_J; a.init_h = init_h; a.init_logZ = init_logZ;
+  a.J11 = tab; a.J12 = tab + 2 * nn; a.J22 = tab + 4 * nn; a.logZ_pair = logZ_pair;
+  a.node_J = node_J; a.node_h = node_h; a.node_logZ = node_logZ;
+  a.lognorm = lognorm; a.E_init = E_init; a.E_pair = E_pair;
+  a.E_node_diagxx = E_node_diagxx; a.E_node_x = E_node_x;
+  a.info = info; a.ws = (double*)workspace;
+  a.ws2 = (keep & 1) ? (double*)workspace + main_ws_doubles(B, T, n) : nullptr;
+  a.ws3 = (keep & 2) ? (double*)workspace + main_ws_doubles(B, T, n) + factor_ws_doubles(B, T, n) : nullptr;
+  a.pair_seq_stride = 0;
+  a.msg_Jp = a.msg_hp = a.msg_Jf = a.msg_hf = nullptr;
+  a.mix_w = nullptr; a.mix_out = nullptr; a.seq_index = nullptr; a.mix_K = 0; a.lds_keep = 0;
+  a.sig_out = nullptr;
+  a.lengths = lengths;
+  SVAE_RAGGED_SWITCH(svae_lds_launch_ragged_n, &a, stream)
+  return -3;
+}
+
+static int ragged_sample(int B, int T, int n, int S, const double* eps, double* samples, const int32_t* lengths,
+                         const void* workspace, void* stream) {
+  svae::SampleArgs a;
+  a.B = B; a.T = T; a.S = S; a.eps = eps; a.samples = samples;
+  a.prod_max_b = 0;
+  a.ws = (const double*)workspace;
+  a.ws2 = (const double*)workspace + main_ws_doubles(B, T, n);
+  a.lengths = lengths;
+  SVAE_RAGGED_SWITCH(svae_lds_sample_ragged_n, &a, stream)
+  return -3;
+}
+
+extern "C" int svae_lds_ragged_inference_f64(int B, int T, int n, int S, int inhomog, int pair_batched, int keep_vjp,
+                                             unsigned options,
+                                             const double* init_J, const double* init_h, const double* init_logZ,
+                                             const double* J11, const double* J12, const double* J22, const double* logZ_pair,
+                                             const double* node_J, const double* node_h, const double* node_logZ,
+                                             const int32_t* lengths, const double* eps, double* samples,
+                                             double* lognorm, double* E_init, double* E_pair,
+                                             double* E_node_diagxx, double* E_node_x,
+                                             int32_t* info, void* workspace, size_t ws_bytes, void* stream) {
+  if (n < 1 || n > SVAE_LDS_MAX_N) return -3;
+  if (S < 0 || (S > 0 && (!eps || !samples))) return -4;
+  if (keep_vjp != 0 && keep_vjp != 1) return -23;
+  const int rc = svae_lds_ragged_estep_f64(B, T, n, inhomog, pair_batched, keep_vjp ? 3 : (S > 0 ? 1 : 0), options, init_J, init_h,
+                                           init_logZ, J11, J12, J22, logZ_pair, node_J, node_h, node_logZ, lengths, lognorm,
+                                           E_init, E_pair, E_node_diagxx, E_node_x, info, workspace, ws_bytes, stream);
+  if (rc != 0 || S == 0 || B == 0) return rc;
+  return ragged_sample(B, T, n, S, eps, samples, lengths, workspace, stream);
+}
+
+extern "C" int svae_lds_ragged_vjp_f64(int B, int T, int n, int S, int inhomog, int pair_batched, unsigned options,
+                                       const double* g_lognorm, const double* g_E_node_diagxx, const double* g_E_node_x,
+                                       const double* g_samples, const double* eps, const double* samples,
+                                       const int32_t* lengths, double* g_node_J, double* g_node_h,
+                                       const void* workspace, size_t ws_bytes,
+                                       void* vjp_workspace, size_t vjp_ws_bytes, void* stream) {
+  if (B < 0) return -1;
+  if (T < 1) return -2;
+  if (n < 1 || n > SVAE_LDS_MAX_N) return -3;
+  if (inhomog || pair_batched) return -32;
+  if (!lengths) return -31;
+  if (g_samples && (S < 1 || S > 16)) return -4;
+  if (!g_lognorm) return -6;
+  if (g_samples && (!eps || !samples)) return -10;
+  if (!g_node_J) return -12;
+  if (!g_node_h) return -13;
+  Selection sel;
+  if (!decode_options(options, B, &sel)) return -24;
+  if (B == 0) return 0;
+  if (!workspace || ws_bytes < svae_lds_ragged_workspace_bytes(B, T, n)) return -14;
+  if (!vjp_workspace || vjp_ws_bytes < svae_lds_vjp_workspace_bytes(B, T, n)) return -16;
+  const long nn = (long)n * n;
+  svae::VjpArgs a;
+  a.B = B; a.T = T; a.S = g_samples ? S : 0;
+  a.prod_max_b = 0;
+  a.J12 = (const double*)((const char*)workspace + ragged_table_offset_bytes(B, T, n)) + 2 * nn;   /* [real | 0], left by the forward pass */
+  a.g_lognorm = g_lognorm; a.g_diagxx = g_E_node_diagxx; a.g_x = g_E_node_x;
+  a.pair_t_stride = 0; a.pair_seq_stride = 0;
+  a.g_E_init = nullptr; a.g_E_pair = nullptr; a.E_pair = nullptr; a.E_node_x = nullptr;
+  a.g_samples = g_samples; a.eps = eps; a.samples = samples;
+  a.g_node_J = g_node_J; a.g_node_h = g_node_h;
+  a.ws = (const double*)workspace;
+  a.ws2 = a.ws + main_ws_doubles(B, T, n);
+  a.ws3 = a.ws2 + factor_ws_doubles(B, T, n);
+  a.adj = (double*)vjp_workspace;
+  a.g_P = nullptr; a.g_R = nullptr; a.pg_only = 0;
+  a.lengths = lengths;
+  SVAE_RAGGED_SWITCH(svae_lds_vjp_ragged_n, &a, stream)
+  return -3;
+}
+#endif  /* !SVAE_ONLY_N */
+#undef SVAE_RAGGED_SWITCH
+
+// [sum E_init | sum E_pair | sum lognorm | B | sum_b (lengths[b] - 1)]: the uniform layout with one more slot, the number
+// of pairs behind the E_pair sums (what the uniform consumers derive as count (T-1))
+extern "C" int svae_lds_ragged_reduce_stats_f64(int B, int T, int n, const double* E_init, const double* E_pair,
+                                                const double* lognorm, const int32_t* lengths, double* out, void* stream) {
+  if (B < 0) return -1;
+  if (T < 1) return -7;
+  if (n < 1 || n > SVAE_LDS_MAX_N) return -2;
+  if (!E_init) return -3;
+  if (!E_pair) return -4;
+  if (!lognorm) return -5;
+  if (!lengths) return -31;
+  if (!out) return -6;
+  const int tot = 4 * n * n + n + 1;
+  hipLaunchKernelGGL(svae::lds_reduce_stats_kernel, dim3((tot + 7) / 8), dim3(256), 0,
+                     (hipStream_t)stream, B, n, E_init, E_pair, lognorm, out);
+  hipLaunchKernelGGL(svae::lds_ragged_pair_count_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, B, T, lengths,
+                     out + tot + 1);
+  return hipGetLastError() == hipSuccess ? 0 : -1000;
 }

@@ -182,9 +182,17 @@ __device__ __forceinline__ void load_row(const double* __restrict__ p, double (&
 // FILT: filter only (natural_filter_forward_general, cython_lds_inference.pyx:28-90): stops after the
 // log-normaliser, keeps the hand-off and the factor region for the sampler (cython_natural_lds_sample,
 // lds_inference.py:260-264) and, on request, writes the forward messages in the reference's scaling.
-template <int N, bool INHOMOG, bool CHOL, bool FILT = false>
+// RAG: per-sequence lengths (svae_lds_ragged_*).  Sequence b of length L = lengths[b] runs as a chain of T steps whose pairs
+// t <= L-2 read the real pair parameters and whose pairs t >= L-1 read the decoupling set Q = (0, 0, -1/2 I, 0) -- entry 0
+// / 1 of the two-entry tables a.J11 / a.J12 / a.J22 point at -- with zero node potentials from step L on: the tail is a chain
+// of independent standard normals that adds exactly 0 to the log-normaliser and leaves the last real node without a J11 term,
+// so every DPP row keeps the uniform trip count.  Node potentials at t >= L are never used (select, not multiply: they may be
+// NaN), the node statistics there are written as 0, and the pair sums run over the row's own L-1 pairs.
+template <int N, bool INHOMOG, bool CHOL, bool FILT = false, bool RAG = false>
 __global__ __launch_bounds__(64) void lds_estep_kernel(const LdsArgs a) {
   static_assert(N >= 1 && N <= SVAE_LDS_MAX_N, "n+1 lanes must fit a 16-lane DPP row");
+  static_assert(!(RAG && (INHOMOG || FILT)), "ragged launches: shared pair parameters, whole E-step");
+  constexpr bool PERSTEP = INHOMOG || RAG;      // the pair blocks are (re)loaded every step
   constexpr int IL = SVAE_IL;
   constexpr int HS = ws_h_stride(N), PS = ws_p_stride(N), WS = ws_step_doubles(N);
   // Above n = 10 the register tiles no longer fit 256 VGPRs: keep fewer constants resident (reload
@@ -201,6 +209,18 @@ __global__ __launch_bounds__(64) void lds_estep_kernel(const LdsArgs a) {
   const bool sth = valid && c <= N;
   const int cc = col ? c : 0;
   const int T = a.T;
+  // RAG: the row's length, clamped for addressing (a value outside 1..T raises the status word below)
+  int len = T;
+  bool len_bad = false;
+  if constexpr (RAG) {
+    const int l = a.lengths[b];
+    len_bad = l < 1 || l > T;
+    len = l < 1 ? 1 : (l > T ? T : l);
+  }
+  auto pair_off = [&](int t) -> long {
+    if constexpr (RAG) return t <= len - 2 ? 0 : N * N;
+    else return INHOMOG ? (long)t * N * N : 0;
+  };
 
   // identity tile: E[i][c] = (c == i), EN[c] = (c == N).  Per-lane selects are done arithmetically
   // with it (x*E, exact) instead of v_cndmask: on gfx950 v_cndmask throughput is shared by the whole
@@ -217,8 +237,8 @@ __global__ __launch_bounds__(64) void lds_estep_kernel(const LdsArgs a) {
   const double* pJ12 = a.J12 + (long)b * a.pair_seq_stride;
   const double* pJ22 = a.J22 + (long)b * a.pair_seq_stride;
   auto load_pair = [&](int t, bool with_next_J11) {   // pair t (and J11 of pair t+1)
-    const long o = INHOMOG ? (long)t * N * N : 0;
-    const long o1 = INHOMOG ? (long)(t + 1) * N * N : 0;
+    const long o = pair_off(t);
+    const long o1 = pair_off(t + 1);
     static_for<0, N>([&](auto i) {      // unconditional loads, selected afterwards
       const double r12t = pJ12[o + cc * N + i], r22 = pJ22[o + i * N + cc], r12 = pJ12[o + i * N + cc];
       const double r11 = with_next_J11 ? pJ11[o1 + i * N + cc] : 0.0;
@@ -227,14 +247,14 @@ __global__ __launch_bounds__(64) void lds_estep_kernel(const LdsArgs a) {
       Cc[i] = col ? -2.0 * (r22 + r11) : 0.0;
     });
   };
-  if (!INHOMOG && T > 1) { load_pair(0, true); dpp_fence(NJ12T); }
+  if (!PERSTEP && T > 1) { load_pair(0, true); dpp_fence(NJ12T); }
 
   // ---- forward filter --------------------------------------------------------------------------
   // An: lanes < N = pivot block of the current step without the node diagonal (J_pred + J11; J_pred
   // alone at t = T-1); lane N = h_pred (column layout: register i holds component i).
   double An[N];
   static_for<0, N>([&](auto i) {
-    const double ij = a.init_J[i * N + cc], ih = a.init_h[i], j11 = T > 1 ? pJ11[i * N + cc] : 0.0;
+    const double ij = a.init_J[i * N + cc], ih = a.init_h[i], j11 = T > 1 ? pJ11[(RAG ? pair_off(0) : 0) + i * N + cc] : 0.0;
     An[i] = col ? -2.0 * (ij + j11) : ((c == N) ? ih : 0.0);
   });
 
@@ -267,13 +287,14 @@ __global__ __launch_bounds__(64) void lds_estep_kernel(const LdsArgs a) {
 #endif
   for (int t = 0; t < T; ++t) {
     const bool last = (t == T - 1);
-    const double Jo = -2.0 * Jo_n;     // scaled one step AFTER its load was issued (see below)
+    double Jo = -2.0 * Jo_n;           // scaled one step AFTER its load was issued (see below)
     double ho = ho_n;
+    if constexpr (RAG) { Jo = t < len ? Jo : 0.0; ho = t < len ? ho : 0.0; }
     if (!last) {
       Jo_n = nJ[(long)(t + 1) * N];
       ho_n = nh[(long)(t + 1) * N];
     }
-    if (INHOMOG && !last) { load_pair(t, t + 1 < T - 1); dpp_fence(NJ12T); }
+    if (PERSTEP && !last) { load_pair(t, t + 1 < T - 1); dpp_fence(NJ12T); }
 
     // condition on the node potential: P = A + diag(J_node); right-hand sides X = [J12 | h_filt]
     // (h_filt = h_pred + h_node lands in lane N, register i <- lane i of the row-layout h_node)
@@ -284,7 +305,7 @@ __global__ __launch_bounds__(64) void lds_estep_kernel(const LdsArgs a) {
       static_for<0, N>([&](auto i) { X[i] = EN * An[i]; });
     } else {
       if constexpr (LOWREG) {
-        const long o = INHOMOG ? (long)t * N * N : 0;
+        const long o = pair_off(t);
         static_for<0, N>([&](auto i) { const double r = pJ12[o + i * N + cc]; X[i] = __builtin_fma(EN, An[i], col ? -r : 0.0); });
       } else {
         static_for<0, N>([&](auto i) { X[i] = __builtin_fma(EN, An[i], J12c[i]); });
@@ -326,7 +347,7 @@ __global__ __launch_bounds__(64) void lds_estep_kernel(const LdsArgs a) {
     if (!last) {
       // next pivot block  A' = (J22 + J11) - J12' P^-1 J12  (lanes < N),  h_pred' = -J12' c  (lane N)
       const bool next_last = (t + 1 == T - 1);
-      if (!INHOMOG && next_last) {
+      if (!PERSTEP && next_last) {
         asm volatile("; next step is the last: its pivot block has no J11 term");   // keep a branch
         static_for<0, N>([&](auto i) { const double r = pJ22[i * N + cc]; An[i] = col ? -2.0 * r : 0.0; });
       } else {
@@ -338,26 +359,30 @@ __global__ __launch_bounds__(64) void lds_estep_kernel(const LdsArgs a) {
     TICK(3)
   }
 
+  // RAG: what the later phases address by the row index is formed AFTER the forward loop, from an opaque copy of it: hipcc
+  // otherwise keeps those addresses live across the loop, which at n = 10 then exceeds 256 VGPRs (AGPR moves: see LOWREG)
+  int bq = b;
+  if constexpr (RAG) asm volatile("" : "+v"(bq));
   // ---- log-normaliser --------------------------------------------------------------------------
   {
     double z = 0.0;
     if (a.node_logZ) {
-      for (int t = c; t < T; t += 16) z += a.node_logZ[(long)b * T + t];
+      for (int t = c; t < (RAG ? len : T); t += 16) z += a.node_logZ[(long)bq * T + t];
     }
     if (INHOMOG) {
-      const double* lz = a.logZ_pair + (a.pair_seq_stride ? (long)b * (T - 1) : 0);
+      const double* lz = a.logZ_pair + (a.pair_seq_stride ? (long)bq * (T - 1) : 0);
       for (int t = c; t < T - 1; t += 16) z += lz[t];
     }
     double total = row_sum16(__builtin_fma(0.5, qacc * EN, z));
     total += a.init_logZ[0];
-    if (!INHOMOG && T > 1) total += (double)(T - 1) * a.logZ_pair[0];
+    if (!INHOMOG && T > 1) total += (double)((RAG ? len : T) - 1) * a.logZ_pair[0];
     total -= 0.5 * (::log(ldM) + (double)ldE * 0.6931471805599453094);
-    if (valid && c == 0) a.lognorm[b] = total;
-    const bool bad = !(pmin > 0.0) || !(total == total);
+    if (valid && c == 0) a.lognorm[bq] = total;
+    const bool bad = !(pmin > 0.0) || !(total == total) || len_bad;
     if (bad && valid && c == 0) {   // rare path: keep the smallest failing index (+1); 0 = ok
       int old = *(volatile int32_t*)a.info;
-      while (old == 0 || old > b + 1) {
-        const int seen = atomicCAS(a.info, old, b + 1);
+      while (old == 0 || old > bq + 1) {
+        const int seen = atomicCAS(a.info, old, bq + 1);
         if (seen == old) break;
         old = seen;
       }
@@ -365,7 +390,7 @@ __global__ __launch_bounds__(64) void lds_estep_kernel(const LdsArgs a) {
   }
 
 #ifdef SVAE_PHASE_TIMING
-  if (valid && c == 0) { for (int q = 0; q < 4; ++q) a.E_init[(long)b * (N * N + N) + q] = (double)tm[q]; }
+  if (valid && c == 0) { for (int q = 0; q < 4; ++q) a.E_init[(long)bq * (N * N + N) + q] = (double)tm[q]; }
   return;
 #endif
   if constexpr (FILT) return;
@@ -377,13 +402,15 @@ __global__ __launch_bounds__(64) void lds_estep_kernel(const LdsArgs a) {
   static_for<0, N + 1>([&](auto i) { S[i] = 0.0; });
   S[N] = EN;
   dpp_fence(S);
-  double sumA[N], sumW[N], Slast[LOWREG ? 1 : N];   // LOWREG: S~_{T-1} waits in its output slot
+  constexpr bool SLAST_MEM = LOWREG || RAG;        // S~_{T-1} (RAG: S~_{len-1}) waits in its output slot
+  constexpr bool ONEBUF = LOWREG || (RAG && N > 9);  // backward loads not double-buffered (RAG, n = 10: 7 registers short of it)
+  double sumA[N], sumW[N], Slast[SLAST_MEM ? 1 : N];
   static_for<0, N>([&](auto i) { sumA[i] = 0.0; sumW[i] = 0.0; });
-  if constexpr (!LOWREG) static_for<0, N>([&](auto i) { Slast[i] = 0.0; });
+  if constexpr (!SLAST_MEM) static_for<0, N>([&](auto i) { Slast[i] = 0.0; });
 
-  double* oEx = a.E_node_x + ((long)b * T) * N + cc;
-  double* oExx = a.E_node_diagxx + ((long)b * T) * N + cc;
-  double* oPair = INHOMOG ? a.E_pair + ((long)b * (T - 1)) * 3 * N * N + cc : nullptr;
+  double* oEx = a.E_node_x + ((long)bq * T) * N + cc;
+  double* oExx = a.E_node_diagxx + ((long)bq * T) * N + cc;
+  double* oPair = INHOMOG ? a.E_pair + ((long)bq * (T - 1)) * 3 * N * N + cc : nullptr;
 
   // lane c < N reads ROW c of H (-> H[k] = H[c][k], the transposition G -> G') and row c of the
   // symmetric P^-1, both contiguous and 16-byte aligned.
@@ -403,7 +430,7 @@ __global__ __launch_bounds__(64) void lds_estep_kernel(const LdsArgs a) {
   // one backward step: consumes (H, Pi) of step t, prefetches step t-1 into (Hn, Pin)
   auto step = [&](int tt, double (&H)[N + 1], double (&Pi)[N], double (&Hn)[N + 1], double (&Pin)[N]) {
     const int t = tt < 0 ? -1 - tt : tt;
-    if constexpr (!LOWREG) load_step(t > 1 ? 1 : 0, Hn, Pin);    // unconditional prefetch of step t-1 (t = 0: re-reads record 0, unused)
+    if constexpr (!ONEBUF) load_step(t > 1 ? 1 : 0, Hn, Pin);    // unconditional prefetch of step t-1 (t = 0: re-reads record 0, unused)
     dpp_fence(H);   // not a DPP source, but keeps the loads' consumers behind this point
 
     // W~ = S~_{t+1} G~'   (W[i][c] = E[x~_{t+1,i} x~_{t,c}])
@@ -411,7 +438,7 @@ __global__ __launch_bounds__(64) void lds_estep_kernel(const LdsArgs a) {
     static_for<0, N + 1>([&](auto i) { W[i] = 0.0; });
     static_for<0, (N + 1 + IL - 1) / IL>([&](auto g) { rows_src_bcast<IL, g * IL, N + 1, N>(W, S, H); });
     if (a.ws3) {   // VJP mode: keep W~_t (rows 0..N, lanes 0..N)
-      double* w3 = a.ws3 + ((long)b * T + t) * (N + 1) * HS + c;
+      double* w3 = a.ws3 + ((long)bq * T + t) * (N + 1) * HS + c;
       if (sth) static_for<0, N + 1>([&](auto i) { w3[i * HS] = W[i]; });
     }
     // S~_t = G~ W~ + diag(P^-1, 0), computed through its transpose (S~ symmetric):
@@ -427,7 +454,7 @@ __global__ __launch_bounds__(64) void lds_estep_kernel(const LdsArgs a) {
         if (t < T - 1) {
           double* o = oPair + (long)t * 3 * N * N;
           static_for<0, N>([&](auto i) { o[i * N] = S[i]; });
-          double* o2 = a.E_pair + (((long)b * (T - 1) + t) * 3 + 1) * N * N + (long)cc * N;
+          double* o2 = a.E_pair + (((long)bq * (T - 1) + t) * 3 + 1) * N * N + (long)cc * N;
           static_for<0, N>([&](auto i) { o2[i] = W[i]; });
         }
         if (t > 0) {
@@ -435,10 +462,16 @@ __global__ __launch_bounds__(64) void lds_estep_kernel(const LdsArgs a) {
           static_for<0, N>([&](auto i) { o[i * N] = S[i]; });
         }
       }
+    } else if constexpr (RAG) {
+      // the row's own pairs t <= len-2 under a 0/1 factor (the tail's moments are finite: I, 0); S~_{len-1} waits in its
+      // output slot (the registers of a resident copy push n = 9, 10 beyond 256 VGPRs)
+      const double mp = t <= len - 2 ? 1.0 : 0.0;
+      static_for<0, N>([&](auto i) { sumA[i] = __builtin_fma(mp, S[i], sumA[i]); sumW[i] = __builtin_fma(mp, W[i], sumW[i]); });
+      if (st && t == len - 1) static_for<0, N>([&](auto i) { a.E_pair[(long)bq * 3 * N * N + 2 * N * N + i * N + cc] = S[i]; });
     } else {
       if (t < T - 1) static_for<0, N>([&](auto i) { sumA[i] += S[i]; sumW[i] += W[i]; });
       else {
-        if constexpr (LOWREG) { if (st) static_for<0, N>([&](auto i) { a.E_pair[(long)b * 3 * N * N + 2 * N * N + i * N + cc] = S[i]; }); }
+        if constexpr (LOWREG) { if (st) static_for<0, N>([&](auto i) { a.E_pair[(long)bq * 3 * N * N + 2 * N * N + i * N + cc] = S[i]; }); }
         else static_for<0, N>([&](auto i) { Slast[i] = S[i]; });
       }
     }
@@ -449,12 +482,17 @@ __global__ __launch_bounds__(64) void lds_estep_kernel(const LdsArgs a) {
       if constexpr (i % 2 == 0) dg = __builtin_fma(E[i], S[i], dg); else dg1 = __builtin_fma(E[i], S[i], dg1);
     });
     if (st) {
-      oEx[(long)t * N] = S[N];
-      oExx[(long)t * N] = dg + dg1;
+      if constexpr (RAG) {
+        oEx[(long)t * N] = t < len ? S[N] : 0.0;
+        oExx[(long)t * N] = t < len ? dg + dg1 : 0.0;
+      } else {
+        oEx[(long)t * N] = S[N];
+        oExx[(long)t * N] = dg + dg1;
+      }
     }
   };
 
-  if constexpr (LOWREG) {
+  if constexpr (ONEBUF) {
     double Ha[N + 1], Pia[N];
     for (int t = T - 1; t >= 0; --t) {
       load_step(1, Ha, Pia);
@@ -473,15 +511,15 @@ __global__ __launch_bounds__(64) void lds_estep_kernel(const LdsArgs a) {
 
   // ---- global statistics -----------------------------------------------------------------------
   if (st) {
-    double* ei = a.E_init + (long)b * (N * N + N);
+    double* ei = a.E_init + (long)bq * (N * N + N);
     static_for<0, N>([&](auto i) { ei[i * N + cc] = S[i]; });   // E[x0 x0']
     ei[N * N + cc] = S[N];                                      // E[x0]
     if (!INHOMOG) {
-      double* ep = a.E_pair + (long)b * 3 * N * N;
+      double* ep = a.E_pair + (long)bq * 3 * N * N;
       static_for<0, N>([&](auto i) {
         ep[i * N + cc] = sumA[i];                               // sum_{t<T-1} E[x_t x_t']
         ep[N * N + cc * N + i] = sumW[i];                       // sum_t E[x_t x_{t+1}'] = (sum_t W_t)'
-        const double sl = LOWREG ? ep[2 * N * N + i * N + cc] : Slast[LOWREG ? 0 : (int)i];
+        const double sl = SLAST_MEM ? ep[2 * N * N + i * N + cc] : Slast[SLAST_MEM ? 0 : (int)i];
         ep[2 * N * N + i * N + cc] = (sumA[i] - S[i]) + sl;      // sum_{t>=1} E[x_t x_t']
       });
     }
@@ -500,6 +538,15 @@ static int launch_estep(const LdsArgs& a, bool inhomog, hipStream_t stream) {
     hipLaunchKernelGGL((lds_estep_kernel<N, false, true>), grid, block, 0, stream, a);
   else
     hipLaunchKernelGGL((lds_estep_kernel<N, false, false>), grid, block, 0, stream, a);
+  return hipGetLastError() == hipSuccess ? 0 : -1000;
+}
+
+// per-sequence lengths (a.lengths, two-entry pair tables): the packed kernel at every batch size
+template <int N>
+static int launch_estep_ragged(const LdsArgs& a, hipStream_t stream) {
+  dim3 grid((a.B + 3) / 4), block(64);
+  if (a.ws2 != nullptr) hipLaunchKernelGGL((lds_estep_kernel<N, false, true, false, true>), grid, block, 0, stream, a);
+  else hipLaunchKernelGGL((lds_estep_kernel<N, false, false, false, true>), grid, block, 0, stream, a);
   return hipGetLastError() == hipSuccess ? 0 : -1000;
 }
 
@@ -575,7 +622,9 @@ __device__ __forceinline__ void gather_publish(const GStage<KT>& sg, double* slo
 // substitution.  Layout: one DPP row per sequence as in the E-step, but lanes are SAMPLES (16 per
 // pass) and the vector index lives in the register number: every coefficient is then a
 // row_newbcast operand, so one v_fmac_f64_dpp advances 16 samples of 4 sequences.
-template <int N>
+// RAG (a.lengths): eps at t >= lengths[b] is never used (it may be NaN) and the samples there are written as 0 -- on the
+// records of a ragged E-step the tail's draw would be eps itself, detached from the real steps.
+template <int N, bool RAG = false>
 __global__ __launch_bounds__(64) void lds_sample_kernel(const SampleArgs a) {
   constexpr int HS = ws_h_stride(N), WS = ws_step_doubles(N);
   const int lane = threadIdx.x;
@@ -586,6 +635,8 @@ __global__ __launch_bounds__(64) void lds_sample_kernel(const SampleArgs a) {
   const bool col = c < N;
   const int cc = col ? c : 0;
   const int T = a.T, S = a.S;
+  int len = T;
+  if constexpr (RAG) { const int l = a.lengths[b]; len = l < 1 ? 1 : (l > T ? T : l); }
   const double* wsb = a.ws + (long)b * ws_seq_doubles(N, T) + ws_zpage_doubles(N);
   const double* ws2b = a.ws2 + ((long)b * T) * (N * N + N) + cc;
 
@@ -611,7 +662,7 @@ __global__ __launch_bounds__(64) void lds_sample_kernel(const SampleArgs a) {
     for (int t = T - 1; t >= 0; --t) {
       double H[N + 1], R[N], Y[N];
       static_for<0, N + 1>([&](auto k) { H[k] = col ? Hn[k] : 0.0; });
-      static_for<0, N>([&](auto k) { R[k] = col ? Rn[k] : 0.0; Y[k] = Yn[k]; });
+      static_for<0, N>([&](auto k) { R[k] = col ? Rn[k] : 0.0; Y[k] = (!RAG || t < len) ? Yn[k] : 0.0; });
       const double pv = col ? pvn : 1.0;
       fetch(t > 0 ? t - 1 : 0);                // (unconditional: see load_step)
       double dis = rsqrt_nr(pv);               // lane k: D_k^-1/2
@@ -635,7 +686,7 @@ __global__ __launch_bounds__(64) void lds_sample_kernel(const SampleArgs a) {
       });
       if (sv) {
         double* o = a.samples + (((long)b * T + t) * S + s) * N;
-        static_for<0, N>([&](auto k) { o[k] = Y[k]; });
+        static_for<0, N>([&](auto k) { o[k] = (!RAG || t < len) ? Y[k] : 0.0; });
       }
       static_for<0, N>([&](auto k) { Xn[k] = Y[k]; });
     }
@@ -648,7 +699,7 @@ __global__ __launch_bounds__(64) void lds_sample_kernel(const SampleArgs a) {
 // factor read transposed by the addressing: lane c loads row c of the stored factor block = column c of L);
 // the mean term with x_{t+1}[j] as the broadcast operand.  ~25 instructions per step and sample instead of
 // ~165 for a 16-sample pass whose lanes would be mostly idle.
-template <int N>
+template <int N, bool RAG = false>
 __global__ __launch_bounds__(64) void lds_sample_vec_kernel(const SampleArgs a) {
   constexpr int HS = ws_h_stride(N), WS = ws_step_doubles(N);
   constexpr int SMAX = 4;
@@ -660,6 +711,8 @@ __global__ __launch_bounds__(64) void lds_sample_vec_kernel(const SampleArgs a) 
   const bool col = c < N;
   const int cc = col ? c : 0;
   const int T = a.T, S = a.S;
+  int len = T;                                 // RAG: see lds_sample_kernel
+  if constexpr (RAG) { const int l = a.lengths[b]; len = l < 1 ? 1 : (l > T ? T : l); }
   const double* wsb = a.ws + (long)b * ws_seq_doubles(N, T) + ws_zpage_doubles(N);
   const double* ws2b = a.ws2 + ((long)b * T) * (N * N + N);
   const bool st = valid && col;
@@ -688,7 +741,7 @@ __global__ __launch_bounds__(64) void lds_sample_vec_kernel(const SampleArgs a) 
         static_for<0, N + 1>([&](auto k) { H[k] = col ? ring[q].H[k] : 0.0; });
         static_for<0, N>([&](auto i) { Lc[i] = (c < i && col) ? ring[q].L[i] : 0.0; });   // L[i][c] below the diagonal only
         const double dis = rsqrt_nr(col ? ring[q].pv : 1.0);
-        static_for<0, SMAX>([&](auto s) { Y[s] = col ? dis * ring[q].E[s] : 0.0; });
+        static_for<0, SMAX>([&](auto s) { Y[s] = (col && (!RAG || t < len)) ? dis * ring[q].E[s] : 0.0; });
         fetch(ring[q], t - NST > 0 ? t - NST : 0);
         dpp_fence(X);
         dpp_fence(Y);
@@ -705,7 +758,7 @@ __global__ __launch_bounds__(64) void lds_sample_vec_kernel(const SampleArgs a) 
               if constexpr (j % 2 == 0) mac_bc<j, true>(acc0, X[s], H[j]); else mac_bc<j, true>(acc1, X[s], H[j]);
             });
             const double xt = acc0 + acc1;
-            if (st) a.samples[(((long)b * T + t) * S + s) * N + c] = xt;
+            if (st) a.samples[(((long)b * T + t) * S + s) * N + c] = (!RAG || t < len) ? xt : 0.0;
             X[s] = xt;
           }
         });
@@ -843,6 +896,14 @@ __global__ __launch_bounds__(320) void lds_sample_vec_prod_kernel(const SampleAr
       }
     });
   }
+}
+
+// per-sequence lengths (a.lengths): the packed kernels at every batch size
+template <int N>
+static int launch_sample_ragged(const SampleArgs& a, hipStream_t stream) {
+  if (a.S <= 4) hipLaunchKernelGGL((lds_sample_vec_kernel<N, true>), dim3((a.B + 3) / 4), dim3(64), 0, stream, a);
+  else hipLaunchKernelGGL((lds_sample_kernel<N, true>), dim3((a.B + 3) / 4), dim3(64), 0, stream, a);
+  return hipGetLastError() == hipSuccess ? 0 : -1000;
 }
 
 template <int N>

@@ -71,3 +71,12 @@ extern "C" int SVAE_CAT(svae_lds_launch_filter_split_n, SVAE_N)(const svae::LdsA
 extern "C" int SVAE_CAT(svae_lds_infer_lean_n, SVAE_N)(const svae::LdsArgs* a, const svae::LeanSample* ls, int inhomog, void* stream) {
   return svae::launch_infer_lean<SVAE_N>(*a, *ls, inhomog != 0, (hipStream_t)stream);
 }
+
+// per-sequence lengths (svae_lds_ragged_*): the packed E-step and samplers in their ragged instantiations
+extern "C" int SVAE_CAT(svae_lds_launch_ragged_n, SVAE_N)(const svae::LdsArgs* a, void* stream) {
+  return svae::launch_estep_ragged<SVAE_N>(*a, (hipStream_t)stream);
+}
+
+extern "C" int SVAE_CAT(svae_lds_sample_ragged_n, SVAE_N)(const svae::SampleArgs* a, void* stream) {
+  return svae::launch_sample_ragged<SVAE_N>(*a, (hipStream_t)stream);
+}

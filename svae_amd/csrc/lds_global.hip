@@ -304,6 +304,7 @@ __device__ __forceinline__ void lds_global_body(const GlobalArgs& a, const int p
 // svae.py:33-34 on the packed statistics of svae_lds_reduce_stats_f64 ([sum E_init (n^2+n) | sum E_pair (3n^2) |
 // . | count]):  natgrad = -scale * (prior + num_batches * stats - params)  over the flat global parameter
 // [NIW dense (n+2)^2 | A | B | C | d], stats = (pack_dense(sum ExxT0, sum Ex0, count, count), (E_pair sums, count (T-1))).
+// T < 1 (svae_lds_ragged_natgrad_f64): the buffer of svae_lds_ragged_reduce_stats_f64, whose last slot IS the pair count.
 __global__ __launch_bounds__(256) void lds_natgrad_kernel(int n, int T, const double* packed, const double* prior,
                                                           const double* params, double num_batches, double scale,
                                                           double* out) {
@@ -320,7 +321,7 @@ __global__ __launch_bounds__(256) void lds_natgrad_kernel(int n, int T, const do
     } else if (e < D * D + 3 * nn) {
       st = packed[nn + n + (e - D * D)];
     } else {
-      st = cnt * (double)(T - 1);
+      st = T >= 1 ? cnt * (double)(T - 1) : packed[4 * nn + n + 2];
     }
     out[e] = -scale * (prior[e] + num_batches * st - params[e]);
   }
@@ -408,5 +409,19 @@ extern "C" int svae_lds_natgrad_f64(int n, int T, const double* packed_stats, co
   const int tot = (n + 2) * (n + 2) + 3 * n * n + 1;
   hipLaunchKernelGGL(svae::lds_natgrad_kernel, dim3((tot + 255) / 256), dim3(256), 0, (hipStream_t)stream,
                      n, T, packed_stats, prior_flat, params_flat, num_batches, scale, natgrad_flat);
+  return hipGetLastError() == hipSuccess ? 0 : -1000;
+}
+
+extern "C" int svae_lds_ragged_natgrad_f64(int n, const double* packed_stats, const double* prior_flat,
+                                           const double* params_flat, double num_batches, double scale,
+                                           double* natgrad_flat, void* stream) {
+  if (n < 1 || n > svae::GL_MAX_N) return -1;
+  if (!packed_stats) return -3;
+  if (!prior_flat) return -4;
+  if (!params_flat) return -5;
+  if (!natgrad_flat) return -8;
+  const int tot = (n + 2) * (n + 2) + 3 * n * n + 1;
+  hipLaunchKernelGGL(svae::lds_natgrad_kernel, dim3((tot + 255) / 256), dim3(256), 0, (hipStream_t)stream,
+                     n, 0, packed_stats, prior_flat, params_flat, num_batches, scale, natgrad_flat);
   return hipGetLastError() == hipSuccess ? 0 : -1000;
 }

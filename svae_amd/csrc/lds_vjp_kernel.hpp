@@ -406,9 +406,13 @@ __device__ __forceinline__ void s1_role0_pair_consumer(const VjpArgs& a, const d
 }
 
 // grp: index of the workgroup's group of four sequences
-template <int N, bool SAMP, bool STATC, bool SPLIT, bool PROD, int ROLE>
+// RAG (a.lengths; packed one-workgroup form only): the cotangents, eps and x_{t+1} of steps t >= lengths[b] are never used
+// (select, not multiply: they may be NaN), so the adjoint records of the tail stay finite and those of the real steps are
+// the truncated chain's.
+template <int N, bool SAMP, bool STATC, bool SPLIT, bool PROD, int ROLE, bool RAG = false>
 __device__ __forceinline__ void lds_vjp_sweep1_body(const VjpArgs& a, double* tabs, double* ring, double* mail,
                                                     const int grp) {
+  static_assert(!RAG || (!STATC && !SPLIT && !PROD && ROLE == 2), "ragged launches: the packed sweep");
   constexpr int HS = ws_h_stride(N), PS = ws_p_stride(N), WS = ws_step_doubles(N);
   constexpr int AS = vjp_step_doubles(N);
   constexpr int W3 = (N + 1) * HS, R1 = N * HS + N * N + N;
@@ -605,6 +609,8 @@ __device__ __forceinline__ void lds_vjp_sweep1_body(const VjpArgs& a, double* ta
   const int b = valid ? brow : a.B - 1;
   const bool col = c < N, colN = c <= N;
   const int T = a.T, S = a.S;
+  int len = T;
+  if constexpr (RAG) { const int l = a.lengths[b]; len = l < 1 ? 1 : (l > T ? T : l); }
   double E[N];
   static_for<0, N>([&](auto i) { E[i] = (c == i) ? 1.0 : 0.0; });
   const double EN = (c == N) ? 1.0 : 0.0;
@@ -665,8 +671,8 @@ __device__ __forceinline__ void lds_vjp_sweep1_body(const VjpArgs& a, double* ta
     double WT[N + 1], Gc[N + 1], Pir[N], gx = 0.0, gd = 0.0, gsv[SAMP ? N : 1];
     if (do0) {
       if constexpr (!PROD) static_for<0, N + 1>([&](auto k) { WT[k] = colN ? 2.0 * WTn[k] : 0.0; });      // 2 W~'
-      gx = col ? 0.5 * gxn : 0.0;              // direct cotangents, symmetrised
-      gd = col ? gdn : 0.0;
+      gx = (col && (!RAG || t < len)) ? 0.5 * gxn : 0.0;              // direct cotangents, symmetrised
+      gd = (col && (!RAG || t < len)) ? gdn : 0.0;
       if constexpr (!PROD) static_for<0, N>([&](auto i) { Pir[i] = w[N * HS + i * PS + ccl]; });
     }
     if constexpr (SAMP) static_for<0, N>([&](auto k) { gsv[k] = gsn[k]; });
@@ -785,7 +791,7 @@ __device__ __forceinline__ void lds_vjp_sweep1_body(const VjpArgs& a, double* ta
       if (do1) {
       // xhat_t = g_samples_t - X_{t-1}' xhat_{t-1}   (register k, lane = sample)
       double xn[N];
-      static_for<0, N>([&](auto k) { xn[k] = sv ? gsv[k] : 0.0; });
+      static_for<0, N>([&](auto k) { xn[k] = (sv && (!RAG || t < len)) ? gsv[k] : 0.0; });
       // the LDL' factor of the step (needed two product stages further down)
       const double* w2 = PROD ? w + N * HS : a.ws2 + ((long)b * T + t) * (N * N + N);
       const double* x1rec = PROD ? w + R1 + SN : a.samples + ((long)b * T + (t + 1 < T ? t + 1 : t)) * SN;   // x_{t+1}, per sample
@@ -827,7 +833,7 @@ __device__ __forceinline__ void lds_vjp_sweep1_body(const VjpArgs& a, double* ta
         double v = EN;
         if (t + 1 < T) {
           const double x1 = (s < SPRE) ? x1r[s < SPRE ? (int)s : 0] : x1rec[s * N + ccl];
-          v += col ? x1 : 0.0;
+          v += (col && (!RAG || t + 1 < len)) ? x1 : 0.0;
         }
         asm volatile("s_nop 1");   // block entry after the branch: two wait states before the DPP reads (audit rule)
         static_for<0, N>([&](auto i) { mac_bc<s>(Gb[i], xh[i], v); });
@@ -853,7 +859,7 @@ __device__ __forceinline__ void lds_vjp_sweep1_body(const VjpArgs& a, double* ta
       dpp_fence(z);
       for_samples<0>(S, [&](auto s) {
         const double e1 = (s < SPRE) ? epr[s < SPRE ? (int)s : 0] : eprec[s * N + ccl];
-        const double ev = col ? e1 : 0.0;
+        const double ev = (col && (!RAG || t < len)) ? e1 : 0.0;
         asm volatile("s_nop 1");   // block entry (audit rule)
         static_for<0, N>([&](auto j) { mac_bc<s>(ET[j], z[j], ev); });         // ET[j][c] = E[c][j]
       });
@@ -873,10 +879,12 @@ __device__ __forceinline__ void lds_vjp_sweep1_body(const VjpArgs& a, double* ta
 }
 
 template <int N> constexpr int vjp_s1_ring_doubles() { return 3 * 4 * vjp_s1_pieces<N>() * 64; }
-template <int N, bool SAMP, bool STATC, bool SPLIT>
+template <int N, bool SAMP, bool STATC, bool SPLIT, bool RAG = false>
 __global__ __launch_bounds__(64) void lds_vjp_sweep1_kernel(const VjpArgs a) {
   __shared__ double tabs[4 * 256];
-  if constexpr (SAMP && SPLIT) {
+  if constexpr (RAG) {
+    lds_vjp_sweep1_body<N, SAMP, STATC, SPLIT, false, 2, true>(a, tabs, nullptr, nullptr, blockIdx.x);
+  } else if constexpr (SAMP && SPLIT) {
     if ((blockIdx.x & 1) == 0) lds_vjp_sweep1_body<N, SAMP, STATC, SPLIT, false, 0>(a, tabs, nullptr, nullptr, blockIdx.x >> 1);
     else lds_vjp_sweep1_body<N, SAMP, STATC, SPLIT, false, 1>(a, tabs, nullptr, nullptr, blockIdx.x >> 1);
   } else {
@@ -912,9 +920,13 @@ __global__ __launch_bounds__(64 * VJP_S1_WAVES) void lds_vjp_sweep1_prod_kernel(
 // [Jpred | hpred]_{t+1} = -R' H_t) in g_R: Bbar[:, :n] as it stands and [Abar | hbar]_{t+1} H_t' = the TRANSPOSE of the
 // product (lane c holds row c of H: the product comes out in this orientation without a transposition); lds_param_grad.hip
 // puts them together.  The other instantiations are untouched.
-template <int N, bool SAMP, bool SPLIT, bool PROD, bool PGR = false>
+// RAG (a.lengths; packed form only): J12 of pair t is entry (t <= lengths[b] - 2 ? 0 : 1) of the two-entry table [real | 0]
+// -- the tail's adjoint reaches the last real step through a zero block -- and the gradients at t >= lengths[b] are written
+// as 0 (the tail's own, g_lognorm E[x_t^2] = g_lognorm, belongs to a potential that does not exist).
+template <int N, bool SAMP, bool SPLIT, bool PROD, bool PGR = false, bool RAG = false>
 __device__ __forceinline__ void lds_vjp_sweep2_body(const VjpArgs& a) {
   static_assert(!(PGR && PROD), "the packed sweep writes the parameter cotangents");
+  static_assert(!RAG || (!SPLIT && !PROD && !PGR), "ragged launches: the packed sweep");
   constexpr int HS = ws_h_stride(N), PS = ws_p_stride(N), WS = ws_step_doubles(N);
   constexpr int AS = vjp_step_doubles(N);
   constexpr int REC = WS + AS;                 // doubles per (sequence, step) in a ring slot
@@ -973,6 +985,8 @@ __device__ __forceinline__ void lds_vjp_sweep2_body(const VjpArgs& a) {
   const bool valid = brow < a.B;
   const int b = valid ? brow : a.B - 1;
   const bool col = c < N, colN = c <= N;
+  int len = T;
+  if constexpr (RAG) { const int l = a.lengths[b]; len = l < 1 ? 1 : (l > T ? T : l); }
   double E[N];
   static_for<0, N>([&](auto i) { E[i] = (c == i) ? 1.0 : 0.0; });
   const double EN = (c == N) ? 1.0 : 0.0;
@@ -980,7 +994,7 @@ __device__ __forceinline__ void lds_vjp_sweep2_body(const VjpArgs& a) {
   double J12c[N];                                             // info form: J12 = -natJ12
   const double* pJ12 = a.J12 + (long)b * a.pair_seq_stride;
   static_for<0, N>([&](auto i) { J12c[i] = 0.0; });
-  if (T > 1 && a.pair_t_stride == 0)
+  if (!RAG && T > 1 && a.pair_t_stride == 0)
     static_for<0, N>([&](auto i) { const double v = pJ12[i * N + (col ? c : 0)]; J12c[i] = col ? -v : 0.0; });
   const double g = a.g_lognorm[b];
 
@@ -1052,8 +1066,8 @@ __device__ __forceinline__ void lds_vjp_sweep2_body(const VjpArgs& a) {
     }
     // [Xbar | cbar] -= J12_t [Abar | hbar]_{t+1}
     if (t < T - 1) {
-      if (a.pair_t_stride != 0) {
-        const double* pj = pJ12 + (long)t * a.pair_t_stride;
+      if (RAG || a.pair_t_stride != 0) {
+        const double* pj = RAG ? pJ12 + (t <= len - 2 ? 0 : N * N) : pJ12 + (long)t * a.pair_t_stride;
         static_for<0, N>([&](auto i) { const double v = pj[i * N + (col ? c : 0)]; J12c[i] = col ? -v : 0.0; });
         dpp_fence(J12c);
       }
@@ -1098,8 +1112,8 @@ __device__ __forceinline__ void lds_vjp_sweep2_body(const VjpArgs& a) {
     static_for<0, N>([&](auto i) { mac_bc<N>(gh, Ab[i], E[i]); });
     if (sink == 1.2345e300) gJ += sink;                        // keeps the touches alive; never true
     if (valid && col && !(PGR && a.pg_only)) {
-      a.g_node_J[((long)b * T + t) * N + c] = -2.0 * gJ;
-      a.g_node_h[((long)b * T + t) * N + c] = gh;
+      a.g_node_J[((long)b * T + t) * N + c] = (!RAG || t < len) ? -2.0 * gJ : 0.0;
+      a.g_node_h[((long)b * T + t) * N + c] = (!RAG || t < len) ? gh : 0.0;
     }
     if (a.g_P) {
       // dense node potentials (the reference's Python path, lds_inference.py:65-82): J_node,t enters P_t alone, so its
@@ -1380,9 +1394,9 @@ __global__ __launch_bounds__(128) void lds_vjp_sweep2_s4_kernel(const VjpArgs a)
   }
 }
 
-template <int N, bool SAMP, bool SPLIT, bool PGR = false>
+template <int N, bool SAMP, bool SPLIT, bool PGR = false, bool RAG = false>
 __global__ __launch_bounds__(64) void lds_vjp_sweep2_kernel(const VjpArgs a) {
-  lds_vjp_sweep2_body<N, SAMP, SPLIT, false, PGR>(a);
+  lds_vjp_sweep2_body<N, SAMP, SPLIT, false, PGR, RAG>(a);
 }
 // consumer wavefront + four producer wavefronts
 template <int N, bool SAMP, bool SPLIT>
@@ -1390,7 +1404,21 @@ __global__ __launch_bounds__(320) void lds_vjp_sweep2_prod_kernel(const VjpArgs 
   lds_vjp_sweep2_body<N, SAMP, SPLIT, true>(a);
 }
 
-constexpr int VJP_PROD2_MAX_N = 12;     // sweep 2 with producers: beyond, the ring exceeds 64 KB and the consumer spills
+// per-sequence lengths (a.lengths, J12 a two-entry table): the packed sweeps at every batch size
+template <int N>
+static int launch_vjp_ragged(const VjpArgs& a, hipStream_t stream) {
+  dim3 grid((a.B + 3) / 4), block(64);
+  if (a.g_samples) {
+    hipLaunchKernelGGL((lds_vjp_sweep1_kernel<N, true, false, false, true>), grid, block, 0, stream, a);
+    hipLaunchKernelGGL((lds_vjp_sweep2_kernel<N, true, false, false, true>), grid, block, 0, stream, a);
+  } else {
+    hipLaunchKernelGGL((lds_vjp_sweep1_kernel<N, false, false, false, true>), grid, block, 0, stream, a);
+    hipLaunchKernelGGL((lds_vjp_sweep2_kernel<N, false, false, false, true>), grid, block, 0, stream, a);
+  }
+  return hipGetLastError() == hipSuccess ? 0 : -1000;
+}
+
+constexpr int VJP_PROD2_MAX_N = 12;    // sweep 2 with producers: beyond, the ring exceeds 64 KB and the consumer spills
 template <int N>
 static int launch_vjp(const VjpArgs& a_in, hipStream_t stream) {
   VjpArgs a = a_in;

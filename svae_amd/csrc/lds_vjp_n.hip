@@ -23,3 +23,8 @@ extern "C" int SVAE_CAT(svae_lds_vjp_n, SVAE_N)(const svae::VjpArgs* a, void* st
 extern "C" int SVAE_CAT(svae_lds_vjp_lean_n, SVAE_N)(const svae::VjpArgs* a, void* stream) {
   return svae::launch_vjp_lean<SVAE_N>(*a, (hipStream_t)stream);
 }
+
+// per-sequence lengths (svae_lds_ragged_vjp_f64): the packed sweeps in their ragged instantiations
+extern "C" int SVAE_CAT(svae_lds_vjp_ragged_n, SVAE_N)(const svae::VjpArgs* a, void* stream) {
+  return svae::launch_vjp_ragged<SVAE_N>(*a, (hipStream_t)stream);
+}

@@ -82,6 +82,30 @@ def set_accurate_smoother(on=True):
     return set_default_options(_default_options & ~acc)
 
 
+def _shape_of(x):
+    return tuple(x.shape) if hasattr(x, "shape") else tuple(np.shape(x))
+
+
+def _ragged_precheck(natparam, node_params, lengths, what):
+    """`lengths=` (per-sequence lengths of one batch): every limit of the ragged kernels as a ValueError, from shapes alone
+    -- before anything touches the device.  -> (B, T, n)"""
+    if _is_dense_nodes(node_params):
+        raise ValueError("%s(lengths=): diagonal node potentials J, h of shape (B,T,n) only -- dense (B,T,n,n) ones are "
+                         "folded into per-step pair parameters, which the ragged kernels do not take" % what)
+    shp = _shape_of(node_params[1])
+    if len(shp) != 3 or _shape_of(node_params[0]) != shp:
+        raise ValueError("%s(lengths=): batched node potentials J, h of shape (B,T,n) -- one sequence has one length, T" % what)
+    B, T, n = shp
+    if n > _lib.LDS_MAX_N:
+        raise ValueError("%s(lengths=): latent dimension <= %d (n = %d)" % (what, _lib.LDS_MAX_N, n))
+    if len(_shape_of(natparam[1][0])) != 2:
+        raise ValueError("%s(lengths=): pair parameters shared by the batch and by the steps, (n,n) blocks -- per-step "
+                         "(T-1,n,n) or per-sequence (B,T-1,n,n) ones are not supported with lengths" % what)
+    if _shape_of(lengths) != (B,):
+        raise ValueError("%s(lengths=): lengths must have shape (B,) = (%d,), got %s" % (what, B, _shape_of(lengths)))
+    return B, T, n
+
+
 class LDSEStepPlan(object):
     """Pre-allocated buffers for repeated E-steps of one shape (B, T, n): the launch itself does no
     allocation, no host<->device copy and no synchronisation.  The sampler and the VJP read the
@@ -126,6 +150,34 @@ class LDSEStepPlan(object):
         # launch counter: the sampler / VJP read the workspace of the LAST launch, so an autograd node
         # remembers the launch it belongs to and refuses to run after the plan has been reused
         self.epoch = 0
+        self._lengths = None     # (B,) int32 device tensor while the records of the last launch are ragged ones
+
+    def _ragged(self, lengths, what, pair_batched=False):
+        """Checks of a launch with per-sequence lengths (ValueError before anything is launched) -> (B,) int32 device
+        tensor (a host `lengths` is copied once, a device one used as it is); grows the workspace by the pair tables."""
+        if self.n > _lib.LDS_MAX_N:
+            raise ValueError("%s(lengths=): latent dimension <= %d (n = %d)" % (what, _lib.LDS_MAX_N, self.n))
+        if self.inhomog or pair_batched:
+            raise ValueError("%s(lengths=): pair parameters shared by the batch and by the steps, (n,n) blocks -- per-step "
+                             "or per-sequence ones are not supported with lengths" % what)
+        if _shape_of(lengths) != (self.B,):
+            raise ValueError("%s(lengths=): lengths must have shape (B,) = (%d,), got %s" % (what, self.B, _shape_of(lengths)))
+        if not (isinstance(lengths, torch.Tensor) and lengths.device == self.device and lengths.dtype == torch.int32
+                and lengths.is_contiguous()):
+            if isinstance(lengths, torch.Tensor) and lengths.is_floating_point():
+                raise ValueError("%s(lengths=): an integer array or tensor" % what)
+            lengths = torch.as_tensor(np.asarray(lengths) if not isinstance(lengths, torch.Tensor) else lengths)
+            lengths = lengths.to(device=self.device, dtype=torch.int32).contiguous()
+        need = int(self.lib.svae_lds_ragged_workspace_bytes(max(self.B, 1), self.T, self.n))
+        if self.ws_bytes < need:
+            self.ws = torch.empty(need // 8, dtype=torch.float64, device=self.device)
+            self.ws_bytes = self.ws.numel() * 8
+        return lengths
+
+    def _set_ragged(self, lengths):
+        self._lengths = lengths
+        # E_pair's fourth entry: the sequence's own number of pairs
+        self.pair_counts = (lengths.clamp(1, self.T) - 1).to(torch.float64)
 
     @property
     def xl(self):
@@ -137,13 +189,38 @@ class LDSEStepPlan(object):
             raise ValueError("%s: latent dimension <= %d (n = %d runs the E-step only)" % (what, _lib.LDS_TILE_MAX_N, self.n))
 
     def launch(self, init_J, init_h, init_logZ, J11, J12, J22, logZ_pair, node_J, node_h,
-               node_logZ=None, pair_batched=False, keep_factor=False, keep_cross=False, half=0, keep_sigma=False):
+               node_logZ=None, pair_batched=False, keep_factor=False, keep_cross=False, half=0, keep_sigma=False,
+               lengths=None):
         """Raw launch on the current stream.  All arguments: contiguous float64 device tensors.
+        lengths (B,) int array / tensor (n <= 15, shared pair parameters): sequence b occupies steps 0 .. lengths[b]-1;
+        svae_lds_ragged_estep_f64 -- statistics, records and gradients of every sequence are those of the sequence
+        truncated to its length, everything at t >= lengths[b] is 0 and the inputs there are never used.
         half (16 <= n <= 64 only): 1 = the forward half of the E-step (filter, hand-off, lognorm), 2 = the backward half
         (smoother + statistics from the hand-off of a preceding half=1 launch); 0 = both.
         keep_sigma (16 <= n <= 64 only, after `vjp_tail`): the backward half leaves the smoothed covariances in the
         first section of the VJP workspace behind the hand-off (SVAE_KEEP_SIGMA), which saves the VJP its phase 0."""
         p = _lib.ptr
+        if lengths is not None:
+            if half or keep_sigma:
+                raise ValueError("launch(lengths=): no E-step halves / keep_sigma (latent dimension <= %d)" % _lib.LDS_MAX_N)
+            lengths = self._ragged(lengths, "launch", pair_batched)
+            keep = int(bool(keep_factor)) | (2 if keep_cross else 0)
+            rc = self.lib.svae_lds_ragged_estep_f64(
+                self.B, self.T, self.n, 0, 0, keep, self.options,
+                p(init_J), p(init_h), p(init_logZ), p(J11), p(J12), p(J22), p(logZ_pair),
+                p(node_J), p(node_h), p(node_logZ), p(lengths),
+                p(self.lognorm), p(self.E_init), p(self.E_pair), p(self.E_node_diagxx),
+                p(self.E_node_x), p(self.info), p(self.ws), self.ws_bytes,
+                _lib.current_stream(self.device))
+            _lib.check(rc, "svae_lds_ragged_estep_f64")
+            self.epoch += 1
+            self.has_factor, self.has_cross = bool(keep_factor), bool(keep_cross)
+            self.lean, self._infer_S = False, None
+            self._J12 = J12
+            self._pair_batched = False
+            self._set_ragged(lengths)
+            return
+        self._lengths = None
         if self.xl:
             # 65 <= n <= 128: E-step only; the plan's options word (kernel choice of the smaller paths) does not apply
             if half or keep_factor or keep_cross or keep_sigma:
@@ -203,13 +280,15 @@ class LDSEStepPlan(object):
         self.E_node_x = torch.empty(B, T, n, **f64)
 
     def infer(self, init_J, init_h, init_logZ, J11, J12, J22, logZ_pair, node_J, node_h, node_logZ=None,
-              pair_batched=False, eps=None, out=None, keep_vjp=True):
+              pair_batched=False, eps=None, out=None, keep_vjp=True, lengths=None):
         """E-step + backward sampler in ONE call (svae_lds_inference_f64 = cython_natural_lds_inference_general,
         lds_inference.py:196-202), keeping what `vjp()` needs.  eps (B,T,S,n) or None (no sampling) -> samples or None.
         For large homogeneous batches (n <= 10, S <= 2, B > 2048, or OPT_LEAN_ON) the library keeps LEAN per-step
         records (csrc/lds_lean_estep.hpp): the same results with a fifth of the hand-off traffic; `sample()` cannot
         follow such a launch (`self.lean`).  keep_vjp=False: forward values only -- no cross-moment record, and lean
-        records then also serve per-step / per-sequence pair parameters; `vjp()` cannot follow."""
+        records then also serve per-step / per-sequence pair parameters; `vjp()` cannot follow.
+        lengths (B,): per-sequence lengths as in `launch` (svae_lds_ragged_inference_f64: full records at every batch size,
+        any number of samples); eps[b, lengths[b]:] is never used and the samples there are 0."""
         self._no_xl("infer()")
         if self.n > _lib.LDS_MAX_N:
             raise ValueError("infer(): latent dimension <= %d (the tile path runs its stages separately)" % _lib.LDS_MAX_N)
@@ -223,6 +302,24 @@ class LDSEStepPlan(object):
             S = eps.shape[2]
             if out is None:
                 out = torch.empty_like(eps)
+        if lengths is not None:
+            lengths = self._ragged(lengths, "infer", pair_batched)
+            rc = self.lib.svae_lds_ragged_inference_f64(
+                self.B, self.T, self.n, S, 0, 0, int(bool(keep_vjp)), self.options,
+                p(init_J), p(init_h), p(init_logZ), p(J11), p(J12), p(J22), p(logZ_pair),
+                p(node_J), p(node_h), p(node_logZ), p(lengths), p(eps), p(out),
+                p(self.lognorm), p(self.E_init), p(self.E_pair), p(self.E_node_diagxx), p(self.E_node_x),
+                p(self.info), p(self.ws), self.ws_bytes, _lib.current_stream(self.device))
+            _lib.check(rc, "svae_lds_ragged_inference_f64")
+            self.epoch += 1
+            self.lean, self._infer_S = False, None
+            self.has_factor = bool(keep_vjp) or S > 0
+            self.has_cross = bool(keep_vjp)
+            self._J12 = J12
+            self._pair_batched = False
+            self._set_ragged(lengths)
+            return out if eps is not None else None
+        self._lengths = None
         rc = self.lib.svae_lds_inference_f64(
             self.B, self.T, self.n, S, int(self.inhomog), int(pair_batched), int(bool(keep_vjp)), self.options,
             p(init_J), p(init_h), p(init_logZ), p(J11), p(J12), p(J22), p(logZ_pair),
@@ -268,6 +365,7 @@ class LDSEStepPlan(object):
             p(self.info), p(self.ws), self.ws_bytes, _lib.current_stream(self.device))
         _lib.check(rc, "svae_lds_filter_f64")
         self.epoch += 1
+        self._lengths = None
         self.has_factor, self.has_cross = True, False
         self.lean, self._infer_S = False, None
         self._J12 = J12
@@ -287,6 +385,8 @@ class LDSEStepPlan(object):
             if self.epoch == 0:
                 raise RuntimeError("sample() needs a preceding launch()")
             return sample_from_handoff(self, eps.to(device=self.device, dtype=torch.float64))
+        if self._lengths is not None:
+            raise RuntimeError("sample(): the last launch had per-sequence lengths -- draw the samples in that call, infer(..., eps, lengths=)")
         if getattr(self, "lean", False):
             raise RuntimeError("sample(): the last launch was infer() on lean records -- its samples were drawn there")
         if not getattr(self, "has_factor", False):
@@ -302,7 +402,7 @@ class LDSEStepPlan(object):
         return out
 
     def vjp(self, g_lognorm, g_E_node_diagxx=None, g_E_node_x=None, g_samples=None, eps=None,
-            samples=None, g_E_init=None, g_E_pair=None, dense_out=None, param_out=False):
+            samples=None, g_E_init=None, g_E_pair=None, dense_out=None, param_out=False, lengths=None):
         """Vector-Jacobian product w.r.t. the node potentials of the last
         `launch(..., keep_factor=True, keep_cross=True)` [+ `sample`]: returns (g_node_J, g_node_h)
         (B,T,n) each; g_node_logZ[b,t] = g_lognorm[b].  Replaces the reference's natural_filter_grad /
@@ -314,8 +414,22 @@ class LDSEStepPlan(object):
         param_out=True (n <= 15, full records): returns (g_node_J, g_node_h, (g_init_J, g_init_h, g_init_logZ, g_J11,
         g_J12, g_J22, g_logZ_pair)) -- the cotangents of the natural parameters in the layout of the launch, summed over
         what each is shared over; g_init_J / g_J11 / g_J22 symmetrised, g_J12 full (svae_lds_estep_vjp_params_f64).  The
-        node gradients are the same bits as without it."""
+        node gradients are the same bits as without it.
+        lengths: after a launch with per-sequence lengths the sweeps are the ragged ones (svae_lds_ragged_vjp_f64) with the
+        lengths of that launch -- passing them again is optional (they must be the same); the cotangents at
+        t >= lengths[b] are never used, the gradients there are 0.  No statistics cotangents, dense_out or param_out."""
         self._no_xl("vjp()")
+        ragged = self._lengths is not None
+        if lengths is not None and not ragged:
+            raise ValueError("vjp(lengths=): the last launch of this plan had no per-sequence lengths")
+        if ragged:
+            if lengths is not None and _shape_of(lengths) != (self.B,):
+                raise ValueError("vjp(lengths=): lengths must have shape (B,) = (%d,), got %s" % (self.B, _shape_of(lengths)))
+            if param_out or dense_out is not None:
+                raise ValueError("vjp() after a launch with lengths: no parameter gradients (param_out / natparam_grad) and "
+                                 "no dense node-potential cotangents")
+            if g_E_init is not None or g_E_pair is not None:
+                raise ValueError("vjp() after a launch with lengths: no cotangents of E_init / E_pair (pair_stats_grad)")
         lean = getattr(self, "lean", False)
         if param_out:
             if self.n > _lib.LDS_MAX_N:
@@ -368,6 +482,14 @@ class LDSEStepPlan(object):
         gJ = torch.empty(self.B, self.T, self.n, **f64)
         gh = torch.empty(self.B, self.T, self.n, **f64)
         p = _lib.ptr
+        if ragged:
+            rc = self.lib.svae_lds_ragged_vjp_f64(
+                self.B, self.T, self.n, S, 0, 0, self.options,
+                p(g_lognorm), p(g_E_node_diagxx), p(g_E_node_x), p(g_samples), p(eps), p(samples), p(self._lengths),
+                p(gJ), p(gh), p(self.ws), self.ws_bytes, p(self.vjp_ws), self.vjp_ws_bytes,
+                _lib.current_stream(self.device))
+            _lib.check(rc, "svae_lds_ragged_vjp_f64")
+            return gJ, gh
         if param_out:
             B, T, n = self.B, self.T, self.n
             pb = bool(self._pair_batched)
@@ -409,10 +531,20 @@ class LDSEStepPlan(object):
         return gJ, gh
 
     def reduce(self):
-        """Deterministic batch sums [sum E_init | sum E_pair | sum lognorm | B] (homogeneous)."""
+        """Deterministic batch sums [sum E_init | sum E_pair | sum lognorm | B] (homogeneous); after a launch with
+        per-sequence lengths one more slot, sum_b (lengths[b] - 1): the pair count, which is not B (T-1) then."""
         if self.inhomog:
             raise ValueError("reduce(): per-step pair statistics (B,T-1,3,n,n) have no batch-summed form here")
         p = _lib.ptr
+        if self._lengths is not None:
+            # [sum E_init | sum E_pair | sum lognorm | B | sum_b (lengths[b] - 1)]: one more slot, the pair count
+            if not hasattr(self, "reduced_ragged"):
+                self.reduced_ragged = torch.empty(4 * self.n * self.n + self.n + 3, dtype=torch.float64, device=self.device)
+            rc = self.lib.svae_lds_ragged_reduce_stats_f64(self.B, self.T, self.n, p(self.E_init), p(self.E_pair),
+                                                           p(self.lognorm), p(self._lengths), p(self.reduced_ragged),
+                                                           _lib.current_stream(self.device))
+            _lib.check(rc, "svae_lds_ragged_reduce_stats_f64")
+            return self.reduced_ragged
         fn = self.lib.svae_lds_xl_reduce_stats_f64 if self.xl else self.lib.svae_lds_reduce_stats_f64
         rc = fn(self.B, self.n, p(self.E_init), p(self.E_pair), p(self.lognorm), p(self.reduced),
                 _lib.current_stream(self.device))
@@ -427,7 +559,8 @@ class LDSEStepPlan(object):
             self.info.zero_()
             raise FloatingPointError("LDS E-step: sequence %d hit a non-positive pivot "
                                      "(potentials not positive definite; through models.lds.run_inference also: the "
-                                     "global natural parameters are not valid)" % (v - 1))
+                                     "global natural parameters are not valid; with lengths= also: a length outside 1..T)"
+                                     % (v - 1))
 
 
 def require_sampler_range(n, what):
@@ -601,7 +734,8 @@ def _prepare(natparam, node_params, plan):
                 args=(init_J, init_h, init_logZ, J11, J12, J22, logZ_pair, node_J, node_h, node_logZ))
 
 
-def natural_lds_estep_general(natparam, node_params, plan=None, check=False, keep_factor=False, _infer_eps=None):
+def natural_lds_estep_general(natparam, node_params, plan=None, check=False, keep_factor=False, _infer_eps=None,
+                              lengths=None):
     """E-step = filter + smoother (lds_inference.py:223-237).
 
     natparam = (init_params, pair_params); init_params = (-1/2 J0, h0, logZ...) and
@@ -620,7 +754,15 @@ def natural_lds_estep_general(natparam, node_params, plan=None, check=False, kee
     the device-side status word and raises FloatingPointError for potentials that are not positive
     definite (the reference ignores LAPACK `info`, cython_gaussian_grads.pxd:54-76); `plan.check_info()`
     does the same later.  The returned tensors are views of the plan's buffers: valid until its next launch.
+
+    lengths (B,) int array / tensor: sequences of different lengths in one batch (n <= 15, (n,n) pair parameters, diagonal
+    node potentials (B,T,n)): sequence b occupies steps 0 .. lengths[b]-1.  lognorm, E_init, E_pair and E_node[:, :L] of
+    every sequence are those of the sequence truncated to its length L (E_pair: sums over its own L-1 pairs, fourth entry
+    L-1); the node statistics at t >= L are 0 (the constant 1 included) and node_params[b, L:] are never used (they may
+    be NaN).  A length outside 1..T raises the status word (`check=True` / `plan.check_info()`).
     """
+    if lengths is not None:
+        _ragged_precheck(natparam, node_params, lengths, "natural_lds_estep_general")
     if _is_dense_nodes(node_params):
         if plan is not None:
             raise ValueError("dense node potentials: the plan is built internally (per-step, per-sequence pair layout)")
@@ -632,9 +774,9 @@ def natural_lds_estep_general(natparam, node_params, plan=None, check=False, kee
     dev = plan.device
     if _infer_eps is not None:
         # (natural_lds_inference_general: E-step + sampler in one call -- lean records for large homogeneous batches)
-        plan._infer_samples = plan.infer(*q["args"], q["pair_batched"], _infer_eps, keep_vjp=False)
+        plan._infer_samples = plan.infer(*q["args"], q["pair_batched"], _infer_eps, keep_vjp=False, lengths=lengths)
     else:
-        plan.launch(*q["args"], q["pair_batched"], keep_factor)
+        plan.launch(*q["args"], q["pair_batched"], keep_factor, lengths=lengths)
     if check:
         plan.check_info()
 
@@ -645,6 +787,10 @@ def natural_lds_estep_general(natparam, node_params, plan=None, check=False, kee
     else:
         Ep = (plan.E_pair[:, 0], plan.E_pair[:, 1], plan.E_pair[:, 2], plan.ones_pair)
     En = (plan.E_node_diagxx, plan.E_node_x, plan.ones_BT)
+    if lengths is not None:
+        live = (torch.arange(T, device=dev)[None, :] < plan._lengths[:, None]).to(torch.float64)
+        Ep = Ep[:3] + (plan.pair_counts,)
+        En = (plan.E_node_diagxx, plan.E_node_x, live)
     Ei = (ExxT0, Ex0, plan.ones_B, plan.ones_B)
     lognorm = plan.lognorm
     if not batched:
@@ -736,11 +882,16 @@ def natural_sample_backward(forward_messages, pair_params, num_samples, eps=None
     return natural_lds_sample(natparam, nodes, num_samples, eps=eps, generator=generator)
 
 
-def natural_lds_sample(natparam, node_params, num_samples=1, eps=None, plan=None, generator=None):
+def natural_lds_sample(natparam, node_params, num_samples=1, eps=None, plan=None, generator=None, lengths=None):
     """Filter + backward sampling WITHOUT the smoother: `cython_natural_lds_sample`
     (lds_inference.py:260-264) -> samples (T,S,n) [(B,T,S,n) batched].  `eps` as in
-    natural_lds_inference_general."""
-    require_sampler_range(np.shape(node_params[1])[-1], "natural_lds_sample")
+    natural_lds_inference_general.  lengths (B,): as in natural_lds_inference_general (the ragged kernels have no
+    filter-only form: this is that call with the statistics dropped)."""
+    require_sampler_range(_shape_of(node_params[1])[-1], "natural_lds_sample")
+    if lengths is not None:
+        _ragged_precheck(natparam, node_params, lengths, "natural_lds_sample")
+        return natural_lds_inference_general(natparam, node_params, num_samples=num_samples, eps=eps, plan=plan,
+                                             generator=generator, lengths=lengths)[0]
     if _is_dense_nodes(node_params):
         if plan is not None:
             raise ValueError("dense node potentials: the plan is built internally")
@@ -772,14 +923,18 @@ cython_natural_lds_sample = natural_lds_sample
 
 
 def natural_lds_inference_general(natparam, node_params, num_samples=None, eps=None, plan=None,
-                                  generator=None):
+                                  generator=None, lengths=None):
     """E-step + backward sampling: (samples, expected_stats, lognorm), mirroring
     `cython_natural_lds_inference_general` (lds_inference.py:196-202).  samples: (T,S,n), or (T,n) when
     num_samples is None as in the Python path (:109-124); batched nodes add a leading B axis.
     The reference draws its noise from the global NumPy RNG inside the sampler
     (cython_lds_inference.pyx:333); here `eps` (B,T,S,n) / (T,S,n) may be passed in, else it is drawn
-    from `generator` on the device."""
-    require_sampler_range(np.shape(node_params[1])[-1], "natural_lds_inference_general")
+    from `generator` on the device.
+    lengths (B,): per-sequence lengths as in natural_lds_estep_general; samples[b, :L] are the truncated sequence's for
+    eps[b, :L], samples[b, L:] are 0 and eps[b, L:] is never used."""
+    require_sampler_range(_shape_of(node_params[1])[-1], "natural_lds_inference_general")
+    if lengths is not None:
+        _ragged_precheck(natparam, node_params, lengths, "natural_lds_inference_general")
     if _is_dense_nodes(node_params):
         if plan is not None:
             raise ValueError("dense node potentials: the plan is built internally")
@@ -803,9 +958,10 @@ def natural_lds_inference_general(natparam, node_params, num_samples=None, eps=N
     else:
         eps = torch.as_tensor(eps, dtype=torch.float64)
         eps = eps if batched else eps[None]
-    if plan.n <= _lib.LDS_MAX_N and eps.dim() == 4 and eps.shape[2] <= 16:
+    if plan.n <= _lib.LDS_MAX_N and eps.dim() == 4 and (eps.shape[2] <= 16 or lengths is not None):
         # ONE call (svae_lds_inference_f64 = the reference's composite, lds_inference.py:196-202)
-        lognorm, stats = natural_lds_estep_general(natparam, node_params, plan=plan, keep_factor=True, _infer_eps=eps)
+        lognorm, stats = natural_lds_estep_general(natparam, node_params, plan=plan, keep_factor=True, _infer_eps=eps,
+                                                   lengths=lengths)
         samples = plan._infer_samples
     else:
         lognorm, stats = natural_lds_estep_general(natparam, node_params, plan=plan, keep_factor=True)
@@ -843,8 +999,9 @@ class _LDSInference(torch.autograd.Function):
     E_init and the per-step E_pair carry gradients too."""
 
     @staticmethod
-    def forward(ctx, node_J, node_h, node_logZ, eps, plan, params, pair_batched):
+    def forward(ctx, node_J, node_h, node_logZ, eps, plan, params, pair_batched, lengths=None):
         init_J, init_h, init_logZ, J11, J12, J22, logZ_pair = params
+        ctx.ragged = lengths is not None
         # Large batches, eager: the launch writes into FRESH output tensors that are handed to autograd as they are (the
         # copies out of the plan's buffers are 0.3 ms of a 3 ms step at 4096 x 200 x 10).  Small batches and anything
         # under stream capture keep the copies: a captured step must write into buffers that outlive the capture, and
@@ -853,10 +1010,10 @@ class _LDSInference(torch.autograd.Function):
         _copy_out = plan.B <= 1024 or torch.cuda.is_current_stream_capturing()
         if not _copy_out:
             plan.fresh_outputs()
-        if eps is None or eps.shape[2] <= 16:
+        if eps is None or eps.shape[2] <= 16 or lengths is not None:
             # one call: E-step + sampler (lean per-step records for large homogeneous batches)
             samples = plan.infer(init_J, init_h, init_logZ, J11, J12, J22, logZ_pair, node_J, node_h, node_logZ,
-                                 pair_batched, eps)
+                                 pair_batched, eps, lengths=lengths)
             if samples is None:
                 samples = torch.zeros(0, dtype=torch.float64, device=plan.device)
         else:
@@ -892,6 +1049,11 @@ class _LDSInference(torch.autograd.Function):
         gJ, gh = plan.vjp(g_lognorm, g_dxx, g_x, gs, eps if gs is not None else None,
                           samples if gs is not None else None, g_init, g_pair)
         gz = g_lognorm[:, None].expand(plan.B, plan.T).clone() if ctx.has_logZ else None
+        if ctx.ragged:
+            if gz is not None:      # (select: the cotangent of a sequence that does not exist is not propagated)
+                live = torch.arange(plan.T, device=plan.device)[None, :] < plan._lengths[:, None]
+                gz = torch.where(live, gz, torch.zeros_like(gz))
+            return gJ, gh, gz, None, None, None, None, None
         return gJ, gh, gz, None, None, None, None
 
 
@@ -1044,7 +1206,8 @@ def _natparam_inference_differentiable(natparam, node_params, eps, plan, pair_st
     return lognorm, (dxx, ex), (samples if eps is not None else None), (E_init, E_pair)
 
 
-def lds_inference_differentiable(natparam, node_params, eps=None, plan=None, pair_stats_grad=False, natparam_grad=False):
+def lds_inference_differentiable(natparam, node_params, eps=None, plan=None, pair_stats_grad=False, natparam_grad=False,
+                                 lengths=None):
     """(lognorm (B), (E_node_diagxx, E_node_x) (B,T,n), samples (B,T,S,n) | None, (E_init, E_pair)):
     differentiable w.r.t. node_params = (J (B,T,n), h (B,T,n)[, logZ (B,T)]) through torch autograd.
     Dense node potentials J (B,T,n,n) (the reference's Python path) are accepted too: the first statistic is then the full
@@ -1066,7 +1229,19 @@ def lds_inference_differentiable(natparam, node_params, eps=None, plan=None, pai
     J22 are symmetric matrices (the forward pass reads the symmetric part), that of J12 is a full one.  The call runs on
     the full per-step records: a plan made here has the lean records switched off; a caller's plan that would keep lean
     records raises ValueError.  The node gradients and (up to 1024 sequences) the forward outputs are the same bits as
-    without the flag."""
+    without the flag.
+
+    lengths (B,) int array / tensor (n <= 15, (n,n) pair parameters, diagonal node potentials): per-sequence lengths as in
+    natural_lds_estep_general.  Outputs and gradients of sequence b up to its length L are the truncated sequence's;
+    every output and every gradient at t >= L is 0, and node_params[b, L:], eps[b, L:] and the cotangents arriving at
+    t >= L are never used (they may be NaN).  Not with natparam_grad or pair_stats_grad."""
+    if lengths is not None:
+        if natparam_grad:
+            raise ValueError("lds_inference_differentiable(lengths=): no parameter gradients (natparam_grad=True) with lengths")
+        if pair_stats_grad:
+            raise ValueError("lds_inference_differentiable(lengths=): no gradients of the pair statistics "
+                             "(pair_stats_grad=True) with lengths")
+        _ragged_precheck(natparam, node_params, lengths, "lds_inference_differentiable")
     if natparam_grad:
         return _natparam_inference_differentiable(natparam, node_params, eps, plan, pair_stats_grad)
     init_params, pair_params = natparam
@@ -1102,7 +1277,11 @@ def lds_inference_differentiable(natparam, node_params, eps=None, plan=None, pai
     fn = _LDSInference
     if n > _lib.LDS_MAX_N:
         from .lds_large import LDSInferenceLarge as fn     # tile-kernel forward, tile VJP kernels backward
-    out = fn.apply(cont(node_J), cont(node_h), cont(node_logZ), cont(eps), plan, params, pair_batched)
+    if lengths is not None:
+        lengths = plan._ragged(lengths, "lds_inference_differentiable", pair_batched)      # (checks; one host -> device copy)
+        out = fn.apply(cont(node_J), cont(node_h), cont(node_logZ), cont(eps), plan, params, pair_batched, lengths)
+    else:
+        out = fn.apply(cont(node_J), cont(node_h), cont(node_logZ), cont(eps), plan, params, pair_batched)
     lognorm, dxx, ex, samples, E_init, E_pair = out
     if sum_pairs:
         E_pair = E_pair.sum(1)                     # (B,3,n,n), differentiable

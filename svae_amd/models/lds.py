@@ -114,9 +114,12 @@ def global_step(global_natparam, prior_natparam=None, info=None):
 
 class PackedLDSStats(tuple):
     """(niw_stats, mniw_stats) as the reference returns them, carrying the packed all-reduced buffer of
-    svae_lds_reduce_stats_f64 they were unpacked from (`.packed`, `.T`): the natural-gradient kernel reads it."""
+    svae_lds_reduce_stats_f64 they were unpacked from (`.packed`, `.T`): the natural-gradient kernel reads it.
+    `.ragged`: the buffer is svae_lds_ragged_reduce_stats_f64's (run_inference(..., lengths=)) -- its last slot is the
+    pair count, which natural_gradient then takes instead of count (T-1)."""
     packed = None
     T = None
+    ragged = False
 
 
 def natural_gradient(prior_natparam, global_natparam, stats, num_batches, scale):
@@ -130,9 +133,14 @@ def natural_gradient(prior_natparam, global_natparam, stats, num_batches, scale)
     n = stats[0].shape[-1] - 2
     out = torch.empty_like(params)
     p = _lib.ptr
-    rc = _lib.load().svae_lds_natgrad_f64(n, int(stats.T), p(stats.packed), p(prior), p(params), float(num_batches),
-                                          float(scale), p(out), _lib.current_stream(dev))
-    _lib.check(rc, "svae_lds_natgrad_f64")
+    if stats.ragged:
+        rc = _lib.load().svae_lds_ragged_natgrad_f64(n, p(stats.packed), p(prior), p(params), float(num_batches),
+                                                     float(scale), p(out), _lib.current_stream(dev))
+        _lib.check(rc, "svae_lds_ragged_natgrad_f64")
+    else:
+        rc = _lib.load().svae_lds_natgrad_f64(n, int(stats.T), p(stats.packed), p(prior), p(params), float(num_batches),
+                                              float(scale), p(out), _lib.current_stream(dev))
+        _lib.check(rc, "svae_lds_natgrad_f64")
     D2, nn = (n + 2) * (n + 2), n * n
     return out[:D2].view(n + 2, n + 2), (out[D2:D2 + nn].view(n, n), out[D2 + nn:D2 + 2 * nn].view(n, n),
                                           out[D2 + 2 * nn:D2 + 3 * nn].view(n, n), out[D2 + 3 * nn])
@@ -149,10 +157,28 @@ def _globals_on_device(prior_natparam, global_natparam, dev, info=None):
     return local_natparam, lds_prior_kl(g, p, global_es)
 
 
+def _ragged_model_checks(nn_potentials, lengths, what):
+    """run_inference(..., lengths=): the limits of the ragged kernels as ValueErrors, from shapes alone"""
+    from ..lds.lds_inference import _ragged_precheck
+    _ragged_precheck(((None, None), (torch.empty(0, 0),)), nn_potentials, lengths, what)     # (the model's pair blocks are (n,n))
+
+
+def _sanitised(nodeb, lengths_dev, T):
+    """the node potentials with zeros at t >= lengths[b] (select: what is stored there may be NaN), and the mask"""
+    live = torch.arange(T, device=lengths_dev.device)[None, :] < lengths_dev[:, None]
+    out = tuple(torch.where(live[..., None] if x.dim() == 3 else live, x, torch.zeros_like(x)) for x in nodeb)
+    return out, live
+
+
 def run_inference(prior_natparam, global_natparam, nn_potentials, num_samples, eps=None,
-                  plan=None, generator=None, group=None):
+                  plan=None, generator=None, group=None, lengths=None):
     """lds.py:35-52.  Returns (samples, global_expected_stats, global_kl, local_kl); with B sequences,
-    samples is (B,T,S,n) and the statistics / local_kl are sums over the (global) batch."""
+    samples is (B,T,S,n) and the statistics / local_kl are sums over the (global) batch.
+    lengths (B,) int array / tensor (n <= 15): sequences of different lengths in one batch -- sequence b occupies steps
+    0 .. lengths[b]-1 of its rows; samples beyond are 0, the statistics are the sums over the sequences as they are (MNIW
+    count: sum_b (lengths[b]-1), through the one all-reduce), and nothing stored at t >= lengths[b] reaches a result."""
+    if lengths is not None:
+        _ragged_model_checks(nn_potentials, lengths, "run_inference")
     dev = torch.device("cuda", torch.cuda.current_device())
     node = tuple(_dev64(x, dev) for x in nn_potentials)
     batched = node[1].dim() == 3
@@ -161,6 +187,8 @@ def run_inference(prior_natparam, global_natparam, nn_potentials, num_samples, e
     require_sampler_range(n, "run_inference")
     if plan is None:
         plan = LDSEStepPlan(B, T, n, dev)
+    if lengths is not None:
+        lengths = plan._ragged(lengths, "run_inference")
     # (invalid global parameters raise the PLAN's status word: plan.check_info() / check=True report them)
     local_natparam, global_kl = _globals_on_device(prior_natparam, global_natparam, dev, plan.info)
     S = 1 if num_samples is None else int(num_samples)
@@ -171,7 +199,10 @@ def run_inference(prior_natparam, global_natparam, nn_potentials, num_samples, e
         eps = eps if batched else eps[None]
     # E-step + sampler as the reference's composite (cython_natural_lds_inference_general, lds_inference.py:196-202): one
     # library call for n <= 15 (lean per-step records above 1024 sequences)
-    samples, (Ei, Ep, En), lognorm = natural_lds_inference_general(local_natparam, nodeb, num_samples=S, eps=eps, plan=plan)
+    samples, (Ei, Ep, En), lognorm = natural_lds_inference_general(local_natparam, nodeb, num_samples=S, eps=eps, plan=plan,
+                                                                   lengths=lengths)
+    if lengths is not None:
+        nodeb, _ = _sanitised(nodeb, lengths, T)       # (the contraction below must not see the padding: NaN * 0 = NaN)
     # local KL: <nn_potentials, E_node> - lognorm  (lds.py:40), summed over the batch
     local_kl = (nodeb[0] * En[0]).sum() + (nodeb[1] * En[1]).sum() - lognorm.sum()
     if len(nodeb) == 3:
@@ -186,18 +217,23 @@ def run_inference(prior_natparam, global_natparam, nn_potentials, num_samples, e
 def _exchange(plan, local_kl, n, T, group):
     """Batch reduction on the device, the ONE collective, and the statistics as the reference nests them
     (carrying the packed buffer for natural_gradient)."""
-    niw_stats, mniw_stats, local_kl, packed = allreduce_lds_stats(plan.reduce(), local_kl, n, T, group, return_packed=True)
+    ragged = plan._lengths is not None
+    niw_stats, mniw_stats, local_kl, packed = allreduce_lds_stats(plan.reduce(), local_kl, n, T, group, return_packed=True,
+                                                                  ragged=ragged)
     stats = PackedLDSStats((niw_stats, mniw_stats))
-    stats.packed, stats.T = packed, T
+    stats.packed, stats.T, stats.ragged = packed, T, ragged
     return stats, local_kl
 
 
 def run_inference_differentiable(prior_natparam, global_natparam, nn_potentials, num_samples,
-                                 eps=None, plan=None, generator=None, group=None):
+                                 eps=None, plan=None, generator=None, group=None, lengths=None):
     """run_inference with gradients w.r.t. nn_potentials = (J (B,T,n), h (B,T,n)[, logZ (B,T)]) flowing
     into `samples` and `local_kl` through the HIP VJP kernels (the reference differentiates exactly
-    these two, svae.py:21-24; the statistics go to `saved.stats` undifferentiated)."""
+    these two, svae.py:21-24; the statistics go to `saved.stats` undifferentiated).  lengths (B,): as in run_inference;
+    the gradients w.r.t. nn_potentials[b, lengths[b]:] are 0."""
     from ..lds.lds_inference import lds_inference_differentiable
+    if lengths is not None:
+        _ragged_model_checks(nn_potentials, lengths, "run_inference_differentiable")
     dev = nn_potentials[1].device
     node = tuple(x.to(torch.float64) for x in nn_potentials)
     batched = node[1].dim() == 3
@@ -212,7 +248,11 @@ def run_inference_differentiable(prior_natparam, global_natparam, nn_potentials,
     if plan is None:
         plan = LDSEStepPlan(B, T, n, dev)
     local_natparam, global_kl = _globals_on_device(prior_natparam, global_natparam, dev, plan.info)
-    lognorm, (dxx, ex), samples, _ = lds_inference_differentiable(local_natparam, nodeb, eps=eps, plan=plan)
+    if lengths is not None:
+        lengths = plan._ragged(lengths, "run_inference_differentiable")
+    lognorm, (dxx, ex), samples, _ = lds_inference_differentiable(local_natparam, nodeb, eps=eps, plan=plan, lengths=lengths)
+    if lengths is not None:
+        nodeb, _ = _sanitised(nodeb, lengths, T)       # (the contraction below must not see the padding)
     local_kl = (nodeb[0] * dxx).sum() + (nodeb[1] * ex).sum() - lognorm.sum()
     if len(nodeb) == 3:
         local_kl = local_kl + nodeb[2].sum()

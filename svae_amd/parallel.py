@@ -88,7 +88,7 @@ def allreduce_nested(struct, scalar=None, group=None):
     return out, scalar
 
 
-def allreduce_lds_stats(reduced, local_kl, n, T, group=None, return_packed=False):
+def allreduce_lds_stats(reduced, local_kl, n, T, group=None, return_packed=False, ragged=False):
     """The exchange step of the LDS model (svae/models/lds.py:35-52 with B sequences per rank).
 
     `reduced` is this rank's buffer from svae_lds_reduce_stats_f64, [sum E_init (n^2+n) | sum E_pair (3n^2)
@@ -96,16 +96,24 @@ def allreduce_lds_stats(reduced, local_kl, n, T, group=None, return_packed=False
     ships both (the sum-lognorm slot carries the local KL).  Returns (niw_stats dense-packed (n+2,n+2),
     mniw_stats (4-tuple), local_kl) with the statistics and the VALUE of local_kl summed over all ranks;
     if local_kl is on the autograd tape its gradient stays this rank's (each rank differentiates its own
-    shard, gradients are averaged by the caller's DDP)."""
+    shard, gradients are averaged by the caller's DDP).
+
+    ragged=True: `reduced` is the buffer of svae_lds_ragged_reduce_stats_f64 (sequences of different lengths in one
+    batch), which carries one more slot behind the count: sum_b (lengths[b] - 1), the number of pairs behind the E_pair
+    sums.  It travels through the same all-reduce and IS the MNIW count -- count (T-1) would be wrong; `T` is not used."""
     from .distributions import expfam
-    packed = reduced.clone()
-    packed[-2] = local_kl.detach()
-    allreduce_global_stats(packed, group)
     nn_ = n * n
     o = nn_ + n
-    cnt = packed[-1]
+    kl_slot = o + 3 * nn_                      # the sum-lognorm slot, then the count [, then the pair count]
+    if reduced.numel() != kl_slot + (3 if ragged else 2):
+        raise ValueError("allreduce_lds_stats: %d doubles for n = %d (%s layout: %d)"
+                         % (reduced.numel(), n, "ragged" if ragged else "uniform", kl_slot + (3 if ragged else 2)))
+    packed = reduced.clone()
+    packed[kl_slot] = local_kl.detach()
+    allreduce_global_stats(packed, group)
+    cnt = packed[kl_slot + 1]
     niw_stats = expfam.pack_dense(packed[:nn_].reshape(n, n), packed[nn_:o], cnt, cnt)
     mniw_stats = (packed[o:o + nn_].reshape(n, n), packed[o + nn_:o + 2 * nn_].reshape(n, n),
-                  packed[o + 2 * nn_:o + 3 * nn_].reshape(n, n), cnt * (T - 1))
-    kl = local_kl + (packed[-2] - local_kl.detach())
+                  packed[o + 2 * nn_:o + 3 * nn_].reshape(n, n), packed[kl_slot + 2] if ragged else cnt * (T - 1))
+    kl = local_kl + (packed[kl_slot] - local_kl.detach())
     return (niw_stats, mniw_stats, kl, packed) if return_packed else (niw_stats, mniw_stats, kl)
