@@ -29,6 +29,12 @@ struct HmmArgs {
   double* __restrict__ node_out;          // (rows,T,K) or nullptr: the node potentials used
   int redo_only;                          // hmm_estep_kernel behind hmm_estep2_kernel: only wavefronts with a flagged sequence run
 };
+// per-sequence lengths (svae_hmm_ragged_estep_f64): sequence b occupies steps 0 .. lengths[b]-1 of its (T, K) block; the
+// arrays and the workspace records keep stride T.  A separate type: the uniform kernels' arguments stay what they are.
+struct HmmRaggedArgs : HmmArgs {
+  const int32_t* __restrict__ lengths;    // (B) device data, clamped to [1, T] for addressing and trip counts
+  int32_t* __restrict__ info;             // status word: bit 0 = a length outside 1..T
+};
 // wide kernel (17 <= K <= 64, one wavefront per sequence): workspace record per (sequence, step) =
 // [alpha^_t or log alpha_t (KP) | normaliser c_t | REDO flag of the sequence (first record only)]
 constexpr int HMM_WIDE_MAX_K = 64;

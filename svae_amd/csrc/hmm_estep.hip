@@ -28,6 +28,8 @@
 #include <stdint.h>
 
 #include "../../include/svae_hip.h"
+#include <type_traits>
+
 #include "dpp.hpp"
 #include "hmm_args.hpp"
 
@@ -60,8 +62,18 @@ __device__ __forceinline__ double row_max16(double x) {
   return x;
 }
 
-template <int K, bool FUSED = false>
-__global__ __launch_bounds__(64) void hmm_estep_kernel(const HmmArgs a) {
+// RAG (svae_hmm_ragged_estep_f64; never with FUSED): the four rows of a wavefront have their own lengths.  The trip count
+// is the longest of them (wave-uniform) and every row runs under its own mask, by SELECTS, not by a neutral tail (an
+// identity transition would have to replace the register-resident P / PT per row and step): the row's loads are clamped
+// to its last step L-1 -- nothing stored at t >= L is read --, a step at t >= L is computed on that clamped data and
+// dropped (alpha, the logZ accumulators and their renormalisation, the `tiny` test and every workspace store are
+// conditional on t < L, so a row's results depend on its own length and data only), the backward pass leaves beta = 1
+// and the xi sums alone while t >= L-1, and E_states from L on is zeroed after the last cross-lane operation.  The
+// log-space steps stay inline, so a ragged call is one launch.  All of it is `if constexpr`: the uniform instantiations
+// compile to what they were.
+template <int K, bool FUSED = false, bool RAG = false>
+__global__ __launch_bounds__(64) void hmm_estep_kernel(const std::conditional_t<RAG, HmmRaggedArgs, HmmArgs> a) {
+  static_assert(!(RAG && FUSED), "ragged launches take node potentials");
   const int lane = threadIdx.x;
   const int c = lane & 15;
   const int brow = blockIdx.x * 4 + (lane >> 4);
@@ -76,6 +88,20 @@ __global__ __launch_bounds__(64) void hmm_estep_kernel(const HmmArgs a) {
   const int cc = col ? c : 0;
   const int T = a.T;
   const double NEG_BIG = -1.0e300;
+  // RAG: TL = the row's own length (clamped for addressing; a value outside 1..T raises the status word), TW = the
+  // longest of the wavefront's rows
+  int TL = T, TW = T;
+  if constexpr (RAG) {
+    const int l = a.lengths[b];
+    if ((l < 1 || l > T) && valid && c == 0) atomicOr(a.info, 1);
+    TL = l < 1 ? 1 : (l > T ? T : l);
+    int m = TL;
+    const int m1 = __shfl_xor(m, 16, 64);
+    m = m1 > m ? m1 : m;
+    const int m2 = __shfl_xor(m, 32, 64);
+    m = m2 > m ? m2 : m;
+    TW = __builtin_amdgcn_readfirstlane(m);
+  }
   if (a.redo_only) {
     // fallback pass behind the two-ended kernel: only for sequences it flagged (a step whose normaliser underflowed)
     const double redo = a.ws[((long)b * T) * HMM_WS + HMM_REDO];
@@ -103,6 +129,7 @@ __global__ __launch_bounds__(64) void hmm_estep_kernel(const HmmArgs a) {
   // (callers clamp t to [1, T-1]; with T = 1 the second FUSED read is clamped into the row as well: the value is unused)
   auto node_at = [&](int t) -> double {
     if constexpr (FUSED) return (pc[(long)(t - 1) * 2 * K] + pc[(long)(t < T ? t : T - 1) * 2 * K + K]) + lzc;
+    else if constexpr (RAG) return node[(long)(t < TL ? t : TL - 1) * K];
     else return node[(long)(t < T ? t : T - 1) * K];
   };
   double node0;
@@ -131,12 +158,14 @@ __global__ __launch_bounds__(64) void hmm_estep_kernel(const HmmArgs a) {
   double lzS = 0.0;            // sum of the subtracted maxima
   double alpha = 0.0;
   double nd_n = node0;
-  for (int t = 0; t < T; ++t) {
+  for (int t = 0; t < TW; ++t) {
+    const bool live = !RAG || t < TL;       // (RAG: a row past its length computes on its last step's data and keeps nothing)
     double nd = col ? nd_n : NEG_BIG;
     if (nout && valid && col) nout[(long)t * K] = nd_n;
     // next step's potentials, UNCONDITIONALLY (clamped): a load inside `if (t + 1 < T)` is waited for at the end of
     // its block, i.e. every step stalled for the full memory latency (0.55 -> ... us per step)
-    nd_n = node_at(t + 1 < T ? t + 1 : (T > 1 ? T - 1 : 1));
+    if constexpr (RAG) nd_n = node_at(t + 1);
+    else nd_n = node_at(t + 1 < T ? t + 1 : (T > 1 ? T - 1 : 1));
     if (t == 0) nd += col ? a.init_params[cc] : 0.0;
     const double m = row_max16(nd);         // m = max_k node[k]
     const double e = col ? exp_nonpos(nd - m) : 0.0;      // (nd - m <= 0: m is the row maximum)
@@ -154,7 +183,7 @@ __global__ __launch_bounds__(64) void hmm_estep_kernel(const HmmArgs a) {
     static_for<0, K>([&](auto k) { mac_bc<k>(cs, al, one); });            // c_t = sum_k
     double rc = rcp_nr(cs);                 // (v_rcp_f64 + two Newton steps: no fp64 divide on the serial chain)
     double u_st = e * rc, shift = m + (t > 0 ? pmax : 0.0), flag = 0.0;
-    const bool tiny = !(cs > HMM_TINY);
+    const bool tiny = live && !(cs > HMM_TINY);
     if (__any(tiny)) {
       // log-space redo of this step for the rows that underflowed (wave-uniform branch; rows that did
       // not underflow keep their scaled result)
@@ -186,6 +215,18 @@ __global__ __launch_bounds__(64) void hmm_estep_kernel(const HmmArgs a) {
         u_st = nd - M - ::log(cs2);          // log of (likelihood / normaliser): the backward pass adds log P
       }
     }
+    if constexpr (RAG) {
+      alpha = live ? al * rc : alpha;
+      if (valid && live) { wsb[(long)t * HMM_WS] = alpha; wsb[(long)t * HMM_WS + 16] = u_st; }
+      if (valid && live && c == 0) wflag[(long)t * HMM_WS] = flag;
+      lzM = live ? lzM * __builtin_amdgcn_frexp_mant(cs) : lzM;
+      lzE += live ? __builtin_amdgcn_frexp_exp(cs) : 0;
+      lzS = live ? lzS + shift : lzS;
+      if ((t & 15) == 15) {
+        lzE += live ? __builtin_amdgcn_frexp_exp(lzM) : 0;
+        lzM = live ? __builtin_amdgcn_frexp_mant(lzM) : lzM;
+      }
+    } else {
     alpha = al * rc;
     if (valid) { wsb[(long)t * HMM_WS] = alpha; wsb[(long)t * HMM_WS + 16] = u_st; }
     if (valid && c == 0) wflag[(long)t * HMM_WS] = flag;
@@ -193,6 +234,7 @@ __global__ __launch_bounds__(64) void hmm_estep_kernel(const HmmArgs a) {
     lzE += __builtin_amdgcn_frexp_exp(cs);
     lzS += shift;
     if ((t & 15) == 15) { lzE += __builtin_amdgcn_frexp_exp(lzM); lzM = __builtin_amdgcn_frexp_mant(lzM); }
+    }
   }
   if (valid && c == 0) a.logZ[b] = lzS + ::log(lzM) + (double)lzE * 0.6931471805599453094;
 
@@ -205,23 +247,27 @@ __global__ __launch_bounds__(64) void hmm_estep_kernel(const HmmArgs a) {
   bool any_slow = false;
   double* oS = a.E_states + ((long)b * T) * K + cc;
   {
-    const double gam = alpha * beta;      // t = T-1
-    if (valid && col) oS[(long)(T - 1) * K] = gam;
-    if (T == 1 && valid && col) a.E_init[(long)b * K + c] = gam;
+    const double gam = alpha * beta;      // t = T-1  (RAG: the row's own last step, where alpha froze)
+    if (valid && col) oS[(long)(TL - 1) * K] = gam;
+    if (TL == 1 && valid && col) a.E_init[(long)b * K + c] = gam;
   }
   // (u, alpha) of a step are fetched one step ahead: the loop is serial in t and the forward pass
   // wrote them ~T steps ago
-  double u_n = T > 1 ? wsb[(long)(T - 1) * HMM_WS + 16] : 0.0, al_n = T > 1 ? wsb[(long)(T - 2) * HMM_WS] : 0.0;
-  double f_n = T > 1 ? wflag[(long)(T - 1) * HMM_WS] : 0.0;
-  for (int t = T - 2; t >= 0; --t) {
+  // (RAG: record indices clamped into the row's own steps; a row with t > L-2 is not `act`ive yet)
+  auto rec_hi = [&](int t) -> long { return RAG ? (long)(t < TL - 1 ? t : (TL > 1 ? TL - 1 : 0)) : (long)t; };
+  auto rec_lo = [&](int t) -> long { return RAG ? (long)(t < TL - 2 ? t : (TL > 2 ? TL - 2 : 0)) : (long)t; };
+  double u_n = TW > 1 ? wsb[rec_hi(TW - 1) * HMM_WS + 16] : 0.0, al_n = TW > 1 ? wsb[rec_lo(TW - 2) * HMM_WS] : 0.0;
+  double f_n = TW > 1 ? wflag[rec_hi(TW - 1) * HMM_WS] : 0.0;
+  for (int t = TW - 2; t >= 0; --t) {
     const double u = u_n;                              // e_{t+1} / c_{t+1}  (flagged step: its log-space stand-in)
     const double al = al_n;
-    const bool slow = f_n != 0.0;
+    const bool act = !RAG || t <= TL - 2;
+    const bool slow = act && f_n != 0.0;
     {
       const int tp = t > 0 ? t - 1 : 0;                // unconditional (clamped) prefetch of step t-1
-      u_n = wsb[(long)(tp + 1) * HMM_WS + 16];
-      al_n = wsb[(long)tp * HMM_WS];
-      f_n = wflag[(long)(tp + 1) * HMM_WS];
+      u_n = wsb[rec_hi(tp + 1) * HMM_WS + 16];
+      al_n = wsb[rec_lo(tp) * HMM_WS];
+      f_n = wflag[rec_hi(tp + 1) * HMM_WS];
     }
     if (__any(slow)) {
       // step t+1 was redone in log space: beta_t[j] = sum_k exp(log P[j][k] + ul[k] + log beta[k]),
@@ -250,33 +296,44 @@ __global__ __launch_bounds__(64) void hmm_estep_kernel(const HmmArgs a) {
           accS[j] += bcast<j>(al) * row;
         });
       }
-      double w0 = slow ? 0.0 : u * beta, al0 = slow ? 0.0 : al;
+      double w0 = (slow || !act) ? 0.0 : u * beta, al0 = (slow || !act) ? 0.0 : al;
       dpp_fence(w0);
       dpp_fence(al0);
       double bn = 0.0;
       static_for<0, K>([&](auto k) { mac_bc<k>(bn, w0, PT[k]); });
       static_for<0, K>([&](auto j) { mac_bc<j>(acc[j], al0, w0); });
-      beta = slow ? fmin(bn2, 1e300) : bn;
+      if constexpr (RAG) beta = act ? (slow ? fmin(bn2, 1e300) : bn) : beta;
+      else beta = slow ? fmin(bn2, 1e300) : bn;
       const double gam = al * beta;
-      if (valid && col) oS[(long)t * K] = gam;
-      if (t == 0 && valid && col) a.E_init[(long)b * K + c] = gam;
+      if (valid && col && act) oS[(long)t * K] = gam;
+      if (t == 0 && valid && col && act) a.E_init[(long)b * K + c] = gam;
       continue;
     }
     double w = u * beta;
     double al_f = al;
+    if constexpr (RAG) { w = act ? w : 0.0; al_f = act ? al : 0.0; }       // (0 * 0 into the xi sums: exact)
     dpp_fence(w);
     dpp_fence(al_f);
     double bn = 0.0;
     static_for<0, K>([&](auto k) { mac_bc<k>(bn, w, PT[k]); });            // beta_t[j] = sum_k P[j][k] w[k]
     static_for<0, K>([&](auto j) { mac_bc<j>(acc[j], al_f, w); });         // xi sums (without P)
-    beta = bn;
+    if constexpr (RAG) beta = act ? bn : beta;
+    else beta = bn;
     const double gam = al * beta;
-    if (valid && col) oS[(long)t * K] = gam;
-    if (t == 0 && valid && col) a.E_init[(long)b * K + c] = gam;
+    if (valid && col && act) oS[(long)t * K] = gam;
+    if (t == 0 && valid && col && act) a.E_init[(long)b * K + c] = gam;
   }
   if (valid && col) {
     static_for<0, K>([&](auto j) { a.E_trans[(long)b * K * K + j * K + c] = __builtin_fma(acc[j], P[j], accS[j]); });
     (void)any_slow;
+  }
+  if constexpr (RAG) {
+    // E_states from the row's length on: zeros, the 16 lanes of the row over the contiguous tail (after the last
+    // cross-lane operation: the trip count differs between rows)
+    if (valid) {
+      double* tail = a.E_states + ((long)b * T) * K;
+      for (long q = (long)TL * K + c; q < (long)T * K; q += 16) tail[q] = 0.0;
+    }
   }
 }
 
@@ -592,6 +649,13 @@ static int launch_hmm(const HmmArgs& a, hipStream_t s) {
 #endif
   if (a.pair_contr) hipLaunchKernelGGL((hmm_estep_kernel<K, true>), dim3((a.B + 3) / 4), dim3(64), 0, s, a);
   else hipLaunchKernelGGL((hmm_estep_kernel<K, false>), dim3((a.B + 3) / 4), dim3(64), 0, s, a);
+  return hipGetLastError() == hipSuccess ? 0 : -1000;
+}
+
+// per-sequence lengths: the one-directional kernel alone (log-space steps inline: one launch, no redo pass)
+template <int K>
+static int launch_hmm_ragged(const HmmRaggedArgs& a, hipStream_t s) {
+  hipLaunchKernelGGL((hmm_estep_kernel<K, false, true>), dim3((a.B + 3) / 4), dim3(64), 0, s, a);
   return hipGetLastError() == hipSuccess ? 0 : -1000;
 }
 
@@ -1054,6 +1118,50 @@ extern "C" int svae_slds_pair_contract_f64(int B, int T, int K, int n, const dou
   hipLaunchKernelGGL((svae::slds_pair_contract_kernel<5, 8>), dim3(blocks), dim3(256), 0, s, B, T, K, E, pair_stats, P, lz,
                      weights, node_out, gpart);
   return hipGetLastError() == hipSuccess ? 0 : -1000;
+}
+
+extern "C" int svae_hmm_wide_ragged_launch(const svae::HmmRaggedArgs* a, void* stream);     // hmm_estep_wide.hip
+
+// svae_hmm_estep_f64 with per-sequence lengths (include/svae_hip.h): every check before any HIP call
+extern "C" int svae_hmm_ragged_estep_f64(int B, int T, int K, int pair_batched,
+                                         const double* init_params, const double* pair_params,
+                                         const double* node_params, const int32_t* lengths,
+                                         double* logZ, double* E_init, double* E_trans, double* E_states,
+                                         int32_t* info, void* workspace, size_t ws_bytes, void* stream) {
+  if (B < 0) return -1;
+  if (T < 1) return -2;
+  if (K < 1 || K > SVAE_HMM_MAX_K) return -3;
+  if (pair_batched != 0 && pair_batched != 1) return -4;
+  if (!init_params) return -5;
+  if (!pair_params) return -6;
+  if (B == 0) return 0;
+  if (!node_params) return -7;
+  if (!lengths) return -8;
+  if (!logZ) return -9;
+  if (!E_init) return -10;
+  if (!E_trans) return -11;
+  if (!E_states) return -12;
+  if (!info) return -13;
+  if (!workspace) return -14;
+  if (ws_bytes < svae_hmm_workspace_bytes(B, T, K)) return -15;
+  svae::HmmRaggedArgs a;
+  a.B = B; a.T = T; a.K = K; a.pair_stride = pair_batched ? (long)K * K : 0;
+  a.init_params = init_params; a.pair_params = pair_params; a.node_params = node_params;
+  a.logZ = logZ; a.E_init = E_init; a.E_trans = E_trans; a.E_states = E_states;
+  a.ws = (double*)workspace;
+  a.seq_index = nullptr; a.n = 0; a.pair_contr = nullptr; a.lds_E_init = nullptr; a.init_J = nullptr; a.init_h = nullptr;
+  a.cinit = nullptr; a.lz = nullptr; a.node_out = nullptr; a.redo_only = 0;
+  a.lengths = lengths; a.info = info;
+  if (K > 16) return svae_hmm_wide_ragged_launch(&a, stream);
+  hipStream_t s = (hipStream_t)stream;
+  switch (K) {
+#define SVAE_CASE(KK) case KK: return svae::launch_hmm_ragged<KK>(a, s);
+    SVAE_CASE(1) SVAE_CASE(2) SVAE_CASE(3) SVAE_CASE(4) SVAE_CASE(5) SVAE_CASE(6) SVAE_CASE(7)
+    SVAE_CASE(8) SVAE_CASE(9) SVAE_CASE(10) SVAE_CASE(11) SVAE_CASE(12) SVAE_CASE(13)
+    SVAE_CASE(14) SVAE_CASE(15) SVAE_CASE(16)
+#undef SVAE_CASE
+  }
+  return -3;
 }
 
 static int hmm_dispatch(const svae::HmmArgs& a, void* stream) {

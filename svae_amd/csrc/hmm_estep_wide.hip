@@ -23,6 +23,8 @@
 #include <stdint.h>
 
 #include "../../include/svae_hip.h"
+#include <type_traits>
+
 #include "dpp.hpp"
 #include "hmm_args.hpp"
 
@@ -49,8 +51,11 @@ __device__ __forceinline__ void publish(double* line, int lane, double x) {
   __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
 
-template <int KP, bool LOGSPACE>
-__global__ __launch_bounds__(64) void hmm_estep_wide_kernel(const HmmArgs a) {
+// RAG (svae_hmm_ragged_estep_f64): the sequence's own length TL = lengths[b] (clamped to [1, T]; one wavefront per
+// sequence, so it is wave-uniform) bounds every loop; records and outputs keep stride T, nothing stored at t >= TL is
+// read, and the scaled launch zeroes E_states from TL on.  The uniform instantiations have TL = T.
+template <int KP, bool LOGSPACE, bool RAG = false>
+__global__ __launch_bounds__(64) void hmm_estep_wide_kernel(const std::conditional_t<RAG, HmmRaggedArgs, HmmArgs> a) {
   constexpr int REC = hmm_wide_rec(KP);
   constexpr double NEG_BIG = -1.0e300;
   __shared__ double line[64];
@@ -62,6 +67,16 @@ __global__ __launch_bounds__(64) void hmm_estep_wide_kernel(const HmmArgs a) {
   const bool st = lane < K;
   const int cc = st ? lane : 0;
   double* wsb = a.ws + b * T * REC;
+  int TL = T;
+  if constexpr (RAG) {
+    const int l = a.lengths[b];
+    TL = l < 1 ? 1 : (l > T ? T : l);
+    if constexpr (!LOGSPACE) {
+      if ((l < 1 || l > T) && lane == 0) atomicOr(a.info, 1);
+      double* tail = a.E_states + b * T * K;
+      for (long q = (long)TL * K + lane; q < (long)T * K; q += 64) tail[q] = 0.0;
+    }
+  }
   if constexpr (LOGSPACE) {
     if (wsb[KP + 1] == 0.0) return;           // not flagged by the scaled pass
   }
@@ -98,7 +113,7 @@ __global__ __launch_bounds__(64) void hmm_estep_wide_kernel(const HmmArgs a) {
     }
     if (lane < KP) wsb[lane] = al;
   }
-  for (int t = 1; t < T; ++t) {
+  for (int t = 1; t < TL; ++t) {
     const double x = st ? nd[(long)t * K + cc] : NEG_BIG;
     publish<KP>(line, lane, al);
     if constexpr (LOGSPACE) {
@@ -148,10 +163,10 @@ __global__ __launch_bounds__(64) void hmm_estep_wide_kernel(const HmmArgs a) {
   double bt = LOGSPACE ? 0.0 : (st ? 1.0 : 0.0);              // beta^_{T-1} = 1  (log beta = 0)
   {
     const double g = LOGSPACE ? (st ? exp(al - logZ) : 0.0) : al;
-    if (st) a.E_states[(b * T + (T - 1)) * K + lane] = g;
-    if (T == 1 && st) a.E_init[b * K + lane] = g;
+    if (st) a.E_states[(b * T + (TL - 1)) * K + lane] = g;
+    if (TL == 1 && st) a.E_init[b * K + lane] = g;
   }
-  for (int t = T - 2; t >= 0; --t) {
+  for (int t = TL - 2; t >= 0; --t) {
     const double x = st ? nd[(long)(t + 1) * K + cc] : NEG_BIG;
     const double alt = wsb[(long)t * REC + (lane < KP ? lane : 0)];
     double g;
@@ -206,6 +221,19 @@ extern "C" int svae_hmm_wide_launch(const svae::HmmArgs* a, void* stream) {
   } else {
     hipLaunchKernelGGL((svae::hmm_estep_wide_kernel<64, false>), grid, block, 0, s, *a);
     hipLaunchKernelGGL((svae::hmm_estep_wide_kernel<64, true>), grid, block, 0, s, *a);
+  }
+  return hipGetLastError() == hipSuccess ? 0 : -1000;
+}
+
+extern "C" int svae_hmm_wide_ragged_launch(const svae::HmmRaggedArgs* a, void* stream) {
+  hipStream_t s = (hipStream_t)stream;
+  dim3 grid(a->B), block(64);
+  if (a->K <= 32) {
+    hipLaunchKernelGGL((svae::hmm_estep_wide_kernel<32, false, true>), grid, block, 0, s, *a);
+    hipLaunchKernelGGL((svae::hmm_estep_wide_kernel<32, true, true>), grid, block, 0, s, *a);
+  } else {
+    hipLaunchKernelGGL((svae::hmm_estep_wide_kernel<64, false, true>), grid, block, 0, s, *a);
+    hipLaunchKernelGGL((svae::hmm_estep_wide_kernel<64, true, true>), grid, block, 0, s, *a);
   }
   return hipGetLastError() == hipSuccess ? 0 : -1000;
 }

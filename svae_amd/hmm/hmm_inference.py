@@ -7,7 +7,14 @@
 natparam = (init_params (K), pair_params (K,K), node_params (T,K)) are LOG potentials, as in the
 reference.  New: node_params may be (B,T,K) (and pair_params (B,K,K)); outputs then carry a leading
 batch axis.  All arithmetic in libsvae_hip.so (svae_hmm_estep_f64); no CPU fallback.
+
+Per-sequence lengths: every function takes lengths= (B,) integers with (B,T,K) node potentials -- one padded batch,
+sequence b occupying steps 0 .. lengths[b]-1.  logZ, E_init, E_trans, E_states[b, :L], states[b, :L] and the score are
+those of the sequence cut to its length; E_states[b, L:] is exactly 0, states[b, L:] is -1, and nothing stored at
+t >= L is read (it may be NaN).  A length outside 1..T is device data: clamped, and recorded in a persistent status
+word that check=True (or check_lengths_status) reads (svae_hmm_ragged_estep_f64 / svae_hmm_ragged_viterbi_f64).
 """
+import numpy as np
 import torch
 
 from .. import _lib
@@ -21,8 +28,52 @@ def _dev64(x, device):
     return t.to(device=device, dtype=torch.float64).contiguous()
 
 
-def hmm_estep(natparam, workspace=None):
+_STATUS = {}
+
+
+def _status_word(device):
+    """The persistent (1,) int32 status word of a device, handed to the ragged kernels as their `info` pointer: they only
+    ever OR into it (a length outside 1..T), so an earlier call's failure survives later clean ones until it is read."""
+    key = str(torch.device(device))
+    word = _STATUS.get(key)
+    if word is None:
+        _STATUS[key] = word = torch.zeros(1, dtype=torch.int32, device=device)
+    return word
+
+
+def check_lengths_status(device=None):
+    """Read (synchronising) and clear the status word of `device`; FloatingPointError if a ragged call since the last
+    check saw a length outside 1..T."""
+    dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+    word = _status_word(dev)
+    if int(word.item()) != 0:
+        word.zero_()
+        raise FloatingPointError("hmm: a sequence length outside 1..T was clamped (lengths= is device data)")
+
+
+def _lengths_arg(lengths, node_params):
+    """Validate lengths= against the node potentials BEFORE anything is converted or launched; the (B,) int32 device
+    tensor (a contiguous int32 device tensor is used as it is, a host array is copied once)."""
+    shape = tuple(node_params.shape) if hasattr(node_params, "shape") else np.shape(node_params)
+    if len(shape) != 3:
+        raise ValueError("lengths= needs batched node_params (B,T,K)")
+    is_t = isinstance(lengths, torch.Tensor)
+    ls = tuple(lengths.shape) if is_t else np.shape(lengths)
+    if ls != (shape[0],):
+        raise ValueError("lengths must have shape (B,) = (%d,), got %r" % (shape[0], ls))
+    if (lengths.is_floating_point() or lengths.is_complex() or lengths.dtype == torch.bool) if is_t \
+            else np.asarray(lengths).dtype.kind not in "iu":
+        raise ValueError("lengths must be integers")
+    dev = node_params.device if isinstance(node_params, torch.Tensor) and node_params.is_cuda \
+        else torch.device("cuda", torch.cuda.current_device())
+    if is_t:
+        return lengths.to(device=dev, dtype=torch.int32).contiguous()
+    return torch.as_tensor(np.asarray(lengths).astype(np.int32), device=dev)
+
+
+def hmm_estep(natparam, workspace=None, lengths=None, check=False):
     init_params, pair_params, node_params = natparam
+    lens = None if lengths is None else _lengths_arg(lengths, node_params)
     dev = node_params.device if isinstance(node_params, torch.Tensor) and node_params.is_cuda \
         else torch.device("cuda", torch.cuda.current_device())
     init_params, pair_params, node = (_dev64(x, dev) for x in (init_params, pair_params, node_params))
@@ -45,6 +96,14 @@ def hmm_estep(natparam, workspace=None):
     logZ = torch.empty(B, **f64)
     E_init, E_trans, E_states = torch.empty(B, K, **f64), torch.empty(B, K, K, **f64), torch.empty(B, T, K, **f64)
     p = _lib.ptr
+    if lens is not None:
+        rc = lib.svae_hmm_ragged_estep_f64(B, T, K, int(pair_batched), p(init_params), p(pair_params), p(node), p(lens),
+                                           p(logZ), p(E_init), p(E_trans), p(E_states), p(_status_word(dev)), p(ws), wsb,
+                                           _lib.current_stream(dev))
+        _lib.check(rc, "svae_hmm_ragged_estep_f64")
+        if check:
+            check_lengths_status(dev)
+        return logZ, (E_init, E_trans, E_states)
     rc = lib.svae_hmm_estep_f64(B, T, K, int(pair_batched), p(init_params), p(pair_params), p(node),
                                 p(logZ), p(E_init), p(E_trans), p(E_states), p(ws), wsb,
                                 _lib.current_stream(dev))
@@ -54,17 +113,19 @@ def hmm_estep(natparam, workspace=None):
     return logZ, (E_init, E_trans, E_states)
 
 
-def hmm_logZ(natparam):
-    return hmm_estep(natparam)[0]
+def hmm_logZ(natparam, lengths=None):
+    return hmm_estep(natparam, lengths=lengths)[0]
 
 
-def hmm_viterbi(natparam, workspace=None, return_score=False):
+def hmm_viterbi(natparam, workspace=None, return_score=False, lengths=None, check=False):
     """Most probable state path under the LOG potentials hmm_estep takes (entries may be -inf):
     labels torch.int32 (T,), or (B,T) when node_params is (B,T,K); with return_score also the path's score
     (0-d, or (B)).  The arithmetic is defined in include/svae_hip.h (svae_hmm_viterbi_f64): fp64 additions in a fixed
     order, ties to the lowest index -- labels and score are reproducible bit for bit.
-    workspace: any contiguous device tensor of at least svae_hmm_viterbi_workspace_bytes(B,T,K) bytes."""
+    workspace: any contiguous device tensor of at least svae_hmm_viterbi_workspace_bytes(B,T,K) bytes.
+    lengths: (B,) integers, see the module docstring -- labels from a sequence's length on are -1."""
     init_params, pair_params, node_params = natparam
+    lens = None if lengths is None else _lengths_arg(lengths, node_params)
     dev = node_params.device if isinstance(node_params, torch.Tensor) and node_params.is_cuda \
         else torch.device("cuda", torch.cuda.current_device())
     init_params, pair_params, node = (_dev64(x, dev) for x in (init_params, pair_params, node_params))
@@ -92,6 +153,14 @@ def hmm_viterbi(natparam, workspace=None, return_score=False):
     states = torch.empty(B, T, dtype=torch.int32, device=dev)
     score = torch.empty(B, dtype=torch.float64, device=dev) if return_score else None
     p = _lib.ptr
+    if lens is not None:
+        rc = lib.svae_hmm_ragged_viterbi_f64(B, T, K, int(pair_batched), p(init_params), p(pair_params), p(node), p(lens),
+                                             p(states), p(score), p(_status_word(dev)), p(ws), wsb,
+                                             _lib.current_stream(dev))
+        _lib.check(rc, "svae_hmm_ragged_viterbi_f64")
+        if check:
+            check_lengths_status(dev)
+        return (states, score) if return_score else states
     rc = lib.svae_hmm_viterbi_f64(B, T, K, int(pair_batched), p(init_params), p(pair_params), p(node),
                                   p(states), p(score), p(ws), wsb, _lib.current_stream(dev))
     _lib.check(rc, "svae_hmm_viterbi_f64")
@@ -107,18 +176,19 @@ class _HMMLogZ(torch.autograd.Function):
     126-166, restricted to the node argument -- all the SLDS-SVAE differentiates, slds_svae.py:150-155)."""
 
     @staticmethod
-    def forward(ctx, node_params, init_params, pair_params):
-        logZ, (_, _, E_states) = hmm_estep((init_params, pair_params, node_params))
+    def forward(ctx, node_params, init_params, pair_params, lengths=None):
+        logZ, (_, _, E_states) = hmm_estep((init_params, pair_params, node_params), lengths=lengths)
         ctx.save_for_backward(E_states)
         return logZ
 
     @staticmethod
     def backward(ctx, g):
         (E_states,) = ctx.saved_tensors
-        return g.reshape(g.shape + (1,) * (E_states.dim() - g.dim())) * E_states, None, None
+        return g.reshape(g.shape + (1,) * (E_states.dim() - g.dim())) * E_states, None, None, None
 
 
-def hmm_logZ_differentiable(natparam):
-    """hmm_logZ with gradients flowing to node_params ((T,K) or (B,T,K))."""
+def hmm_logZ_differentiable(natparam, lengths=None):
+    """hmm_logZ with gradients flowing to node_params ((T,K) or (B,T,K)).  With lengths= the gradient is g * E_states of
+    the same launch: exactly 0 from a sequence's length on."""
     init_params, pair_params, node_params = natparam
-    return _HMMLogZ.apply(node_params, init_params, pair_params)
+    return _HMMLogZ.apply(node_params, init_params, pair_params, lengths)
