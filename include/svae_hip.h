@@ -25,7 +25,7 @@
 extern "C" {
 #endif
 
-#define SVAE_HIP_ABI_VERSION 15   /* 15: (+ svae_hmm_ragged_estep_f64, svae_hmm_ragged_viterbi_f64: per-sequence lengths for the HMM E-step and Viterbi, added without a new number -- additions only, compatible with every caller of 15) (+ svae_lds_estep_vjp_params_f64, svae_lds_param_vjp_workspace_bytes: cotangents of the init / pair natural parameters, added without a new number -- additions only) + svae_gmm_wide_mw_workspace_bytes, svae_gmm_wide_mw_begin, svae_gmm_wide_mw_step_f64, svae_gmm_wide_sample_f64, svae_gmm_wide_local_vjp_f64, svae_gmm_wide_global_step_f64 (the GMM local step for N <= 16; additions only), svae_lds_filter_vjp_f64, svae_lds_smoother_vjp_f64 (+ svae_lds_smoother_vjp_workspace_bytes), svae_lds_sample_vjp_f64 (the reference's three reverse-mode primitives on caller-held forward messages); 14: + svae_lds_estep_vjp_dense_f64 (cotangent of dense node potentials), svae_hmm_* up to K = 64, svae_lds_inference_f64 (E-step + sampler in one call; lean per-step records for large homogeneous batches), svae_lds_inference_is_lean, SVAE_OPT_LEAN_ON / _OFF / SVAE_OPT_INFER_RECORDS; 13: + svae_slds_pair_contract_f64 (the two contractions of the SLDS final pass over the per-step pair statistics in one pass); 12: svae_gmm_global_step_f64 writes kl[0..1] (as spelled | as shipped), svae_ipc_allreduce_f64 takes the mailbox stride and never writes `out` on a timeout, + svae_slds_lds_meanfield options; 11: + svae_lds_global_step_multi_f64 (K parameter sets in one launch: the SLDS global -> local maps), svae_lds_diag_sample_f64 (filter + sampler of an all-diagonal LDS: the SLDS initial path); 10: + svae_ipc_allreduce_f64 / svae_ipc_mailbox_bytes, svae_gmm_sample_f64, svae_gmm_local_vjp_f64, svae_gmm_global_step_f64 (the differentiable tail and the global side of the GMM local step); 9: keep bit SVAE_KEEP_SIGMA of svae_lds_estep_f64 (16 <= n <= 64) + svae_lds_tile_sigma_offset_bytes; 8: step ranges (t_begin, t_end) in svae_lds_tile_vjp_f64 / svae_lds_tile_noise_f64, SVAE_OPT_TILE_FORWARD / _BACKWARD; 7: + svae_slds_path_nodeparams_f64, svae_slds_mix_pair_natparam_f64; 6: per-call `options` word replaces the process-global svae_lds_set_* selectors (re-entrant library), + svae_slds_hmm_meanfield_f64, svae_slds_sweep_glue_f64, g_E_pair in svae_lds_tile_vjp_f64; 5: + svae_lds_set_prod_max_b; 4: + svae_slds_lds_meanfield_f64, svae_gmm_mw_*, svae_lds_global_step_f64, svae_lds_natgrad_f64, svae_lds_tile_vjp_f64; 2: + svae_lds_workspace_bytes_ex, svae_lds_estep_vjp_ex_f64, svae_hmm_*, tiled path (n <= 64) */
+#define SVAE_HIP_ABI_VERSION 15   /* 15: (+ svae_lds_ragged_perstep_workspace_bytes, svae_lds_ragged_perstep_estep_f64, svae_lds_ragged_perstep_inference_f64: per-sequence lengths with per-step pair parameters and a per-sequence init potential, added without a new number -- additions only) (+ svae_hmm_ragged_estep_f64, svae_hmm_ragged_viterbi_f64: per-sequence lengths for the HMM E-step and Viterbi, added without a new number -- additions only, compatible with every caller of 15) (+ svae_lds_estep_vjp_params_f64, svae_lds_param_vjp_workspace_bytes: cotangents of the init / pair natural parameters, added without a new number -- additions only) + svae_gmm_wide_mw_workspace_bytes, svae_gmm_wide_mw_begin, svae_gmm_wide_mw_step_f64, svae_gmm_wide_sample_f64, svae_gmm_wide_local_vjp_f64, svae_gmm_wide_global_step_f64 (the GMM local step for N <= 16; additions only), svae_lds_filter_vjp_f64, svae_lds_smoother_vjp_f64 (+ svae_lds_smoother_vjp_workspace_bytes), svae_lds_sample_vjp_f64 (the reference's three reverse-mode primitives on caller-held forward messages); 14: + svae_lds_estep_vjp_dense_f64 (cotangent of dense node potentials), svae_hmm_* up to K = 64, svae_lds_inference_f64 (E-step + sampler in one call; lean per-step records for large homogeneous batches), svae_lds_inference_is_lean, SVAE_OPT_LEAN_ON / _OFF / SVAE_OPT_INFER_RECORDS; 13: + svae_slds_pair_contract_f64 (the two contractions of the SLDS final pass over the per-step pair statistics in one pass); 12: svae_gmm_global_step_f64 writes kl[0..1] (as spelled | as shipped), svae_ipc_allreduce_f64 takes the mailbox stride and never writes `out` on a timeout, + svae_slds_lds_meanfield options; 11: + svae_lds_global_step_multi_f64 (K parameter sets in one launch: the SLDS global -> local maps), svae_lds_diag_sample_f64 (filter + sampler of an all-diagonal LDS: the SLDS initial path); 10: + svae_ipc_allreduce_f64 / svae_ipc_mailbox_bytes, svae_gmm_sample_f64, svae_gmm_local_vjp_f64, svae_gmm_global_step_f64 (the differentiable tail and the global side of the GMM local step); 9: keep bit SVAE_KEEP_SIGMA of svae_lds_estep_f64 (16 <= n <= 64) + svae_lds_tile_sigma_offset_bytes; 8: step ranges (t_begin, t_end) in svae_lds_tile_vjp_f64 / svae_lds_tile_noise_f64, SVAE_OPT_TILE_FORWARD / _BACKWARD; 7: + svae_slds_path_nodeparams_f64, svae_slds_mix_pair_natparam_f64; 6: per-call `options` word replaces the process-global svae_lds_set_* selectors (re-entrant library), + svae_slds_hmm_meanfield_f64, svae_slds_sweep_glue_f64, g_E_pair in svae_lds_tile_vjp_f64; 5: + svae_lds_set_prod_max_b; 4: + svae_slds_lds_meanfield_f64, svae_gmm_mw_*, svae_lds_global_step_f64, svae_lds_natgrad_f64, svae_lds_tile_vjp_f64; 2: + svae_lds_workspace_bytes_ex, svae_lds_estep_vjp_ex_f64, svae_hmm_*, tiled path (n <= 64) */
 #define SVAE_HMM_MAX_K 64   /* svae_hmm_estep_f64 / svae_slds_hmm_meanfield_f64: K <= 16 one DPP row per sequence; 17 <= K <= 64 one wavefront per sequence (round 6) */
 #define SVAE_LDS_MAX_N 15   /* register/DPP path: one 16-lane row per sequence, n+1 <= 16 */
 #define SVAE_LDS_TILE_MAX_N 64   /* 16 <= n <= 64: LDS-tiled MFMA path (keep: SVAE_KEEP_SIGMA or 0) */
@@ -877,6 +877,53 @@ int svae_lds_ragged_reduce_stats_f64(int B, int T, int n, const double* E_init, 
 int svae_lds_ragged_natgrad_f64(int n, const double* packed_stats, const double* prior_flat,
                                 const double* params_flat, double num_batches, double scale,
                                 double* natgrad_flat, void* stream);
+
+/* ---- Per-sequence lengths with PER-STEP pair parameters, n <= SVAE_LDS_MAX_N (csrc/lds_estep.hip) -----------------------
+ * What the SLDS needs from the LDS side for a ragged batch: the construction above -- sequence b of length L = lengths[b]
+ * is the chain whose pairs t <= L-2 carry the real parameters and whose pairs t >= L-1 carry Q = (0, 0, -1/2 I, 0), zero node
+ * potentials from step L on -- with pair parameters that differ from step to step, (T-1,n,n) and (T-1), or, pair_batched = 1,
+ * from sequence to sequence as well, (B,T-1,n,n) and (B,T-1); and with the init potential shared, (n,n), (n), (1), or,
+ * init_batched = 1, one per sequence, (B,n,n), (B,n), (B).  The kernel is the INHOMOG + RAG instantiation of the packed
+ * one-directional E-step: per step a pointer select between the caller's block of pair t and a table [0 | -1/2 I] that a
+ * one-workgroup kernel leaves behind the uniform workspace layout.
+ *
+ * Contract, per sequence b with L = lengths[b]: lognorm[b], E_init[b], E_pair[b,:L-1] (per-step blocks (3,n,n)),
+ * E_node_*[b,:L] and samples[b,:L] (for eps[b,:L]) are those of the sequence cut at L steps -- pair parameters [:L-1], node
+ * potentials [:L], logZ_pair summed over t <= L-2 and node_logZ over t < L; E_pair[b,L-1:], E_node_*[b,L:] and
+ * samples[b,L:] are 0; J11 / J12 / J22 / logZ_pair at t >= L-1 (any sequence's with pair_batched = 0 only through another
+ * sequence's longer length), node_*[b,L:] and eps[b,L:] are never read (they may be NaN); no result of sequence b depends on
+ * another sequence's length.  A length outside 1..T raises the status word `info` (b+1) and is clamped to 1..T for
+ * addressing.  There are no VJP sweeps on these records.
+ *
+ * Workspace: the layout of svae_lds_workspace_bytes(B,T,n), then (256-byte aligned) the table, 2 n^2 doubles. */
+size_t svae_lds_ragged_perstep_workspace_bytes(int B, int T, int n);
+
+/* keep: 0, or 1 = keep the factor region for the sampler; bit 1 (the VJP's cross moments) is refused.  options: a valid
+ * SVAE_OPT_* word; it selects nothing here.  Returns 0, or before any HIP call: -1 B, -2 T, -3 n outside
+ * 1..SVAE_LDS_MAX_N, -32 pair_batched / init_batched outside {0, 1}, -31 lengths NULL, -23 keep, -6 init_J, -7 init_h,
+ * -8 init_logZ, -9 a pair array NULL with T > 1, -13 node_J, -14 node_h, -16 lognorm, -17 E_init, -18 E_pair (T > 1),
+ * -19 E_node_diagxx, -20 E_node_x, -21 info, -24 options, -22 workspace NULL or shorter than
+ * svae_lds_ragged_perstep_workspace_bytes; B = 0 returns 0 after the checks up to options. */
+int svae_lds_ragged_perstep_estep_f64(int B, int T, int n, int pair_batched, int init_batched, int keep, unsigned options,
+                                      const double* init_J, const double* init_h, const double* init_logZ,
+                                      const double* J11, const double* J12, const double* J22, const double* logZ_pair,
+                                      const double* node_J, const double* node_h, const double* node_logZ,
+                                      const int32_t* lengths,
+                                      double* lognorm, double* E_init, double* E_pair,
+                                      double* E_node_diagxx, double* E_node_x,
+                                      int32_t* info, void* workspace, size_t ws_bytes, void* stream);
+
+/* The E-step above (keeping the factor region whenever S > 0), then the ragged sampler of svae_lds_ragged_inference_f64 on
+ * its records: full per-step records at every batch size, any S that entry covers.  Error codes of
+ * svae_lds_ragged_perstep_estep_f64; -4 for S < 0 or S > 0 without eps / samples. */
+int svae_lds_ragged_perstep_inference_f64(int B, int T, int n, int S, int pair_batched, int init_batched, unsigned options,
+                                          const double* init_J, const double* init_h, const double* init_logZ,
+                                          const double* J11, const double* J12, const double* J22, const double* logZ_pair,
+                                          const double* node_J, const double* node_h, const double* node_logZ,
+                                          const int32_t* lengths, const double* eps, double* samples,
+                                          double* lognorm, double* E_init, double* E_pair,
+                                          double* E_node_diagxx, double* E_node_x,
+                                          int32_t* info, void* workspace, size_t ws_bytes, void* stream);
 
 #ifdef __cplusplus
 }

@@ -148,6 +148,13 @@ SIGNATURES = {
                                                                                               ctypes.c_void_p]),
     "svae_lds_ragged_natgrad_f64": (ctypes.c_int, [ctypes.c_int] + [_c_double_p] * 3 + [ctypes.c_double] * 2
                                     + [_c_double_p, ctypes.c_void_p]),
+    # per-sequence lengths with per-step pair parameters and an optional per-sequence init potential (n <= 15)
+    "svae_lds_ragged_perstep_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int] * 3),
+    "svae_lds_ragged_perstep_estep_f64": (ctypes.c_int, [ctypes.c_int] * 6 + [ctypes.c_uint] + [_c_double_p] * 10 + [_c_int_p]
+                                          + [_c_double_p] * 5 + [_c_int_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]),
+    "svae_lds_ragged_perstep_inference_f64": (ctypes.c_int, [ctypes.c_int] * 6 + [ctypes.c_uint] + [_c_double_p] * 10
+                                              + [_c_int_p] + [_c_double_p] * 7
+                                              + [_c_int_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]),
 }
 
 _lib = None

@@ -89,6 +89,14 @@ struct LdsArgs {
   const int32_t* __restrict__ lengths = nullptr;
 };
 
+// ragged launches with per-step pair parameters (svae_lds_ragged_perstep_*): J11 / J12 / J22 / logZ_pair are the caller's
+// (T-1,..) or (B,T-1,..) arrays (pair_seq_stride), read at pairs t <= lengths[b] - 2 only; pairs behind them read qtab.
+// A derived struct: the kernarg layout of every other launch stays as it is.
+struct LdsPerstepArgs : LdsArgs {
+  const double* __restrict__ qtab = nullptr;   // [0 (n,n) | -1/2 I (n,n)]: J11 = J12 = 0, J22 = -1/2 I of the decoupling set
+  int init_batched = 0;                        // 1: init_J (B,n,n), init_h (B,n), init_logZ (B) -- one init potential per sequence
+};
+
 struct SampleArgs {
   int B, T, S;
   int prod_max_b;                     // largest batch that runs with producer wavefronts (svae_lds_set_prod_max_b)

@@ -24,6 +24,7 @@ extern "C" {
   int svae_lds_infer_lean_n##NN(const svae::LdsArgs*, const svae::LeanSample*, int, void*); \
   int svae_lds_vjp_lean_n##NN(const svae::VjpArgs*, void*);                    \
   int svae_lds_launch_ragged_n##NN(const svae::LdsArgs*, void*);               \
+  int svae_lds_launch_ragged_perstep_n##NN(const svae::LdsPerstepArgs*, void*); \
   int svae_lds_sample_ragged_n##NN(const svae::SampleArgs*, void*);            \
   int svae_lds_vjp_ragged_n##NN(const svae::VjpArgs*, void*);
 #define SVAE_DECL(NN) SVAE_DECL_(NN)
@@ -739,6 +740,16 @@ __global__ __launch_bounds__(256) void lds_ragged_tables_kernel(int n, const dou
   }
 }
 
+// qtab = [0 | -1/2 I]  (2 n^2 doubles): J11 = J12 = 0 and J22 = -1/2 I of the decoupling set Q, what the per-step ragged
+// E-step (svae_lds_ragged_perstep_*) reads at the pairs t >= lengths[b] - 1 instead of the caller's blocks
+__global__ __launch_bounds__(256) void lds_ragged_qtable_kernel(int n, double* qtab) {
+  const int nn = n * n;
+  for (int e = threadIdx.x; e < nn; e += blockDim.x) {
+    qtab[e] = 0.0;
+    qtab[nn + e] = (e / n == e % n) ? -0.5 : 0.0;
+  }
+}
+
 // out[slot] = sum_b (clamp(lengths[b], 1, T) - 1): integer partial sums in a fixed tree, exact in any order
 __global__ __launch_bounds__(256) void lds_ragged_pair_count_kernel(int B, int T, const int32_t* lengths, double* out) {
   __shared__ long long red[256];
@@ -763,6 +774,11 @@ static size_t ragged_table_offset_bytes(int B, int T, int n) { return (svae_lds_
 extern "C" size_t svae_lds_ragged_workspace_bytes(int B, int T, int n) {
   if (B <= 0 || T <= 0 || n <= 0 || n > SVAE_LDS_MAX_N) return 0;
   return ragged_table_offset_bytes(B, T, n) + (size_t)6 * n * n * sizeof(double);
+}
+
+extern "C" size_t svae_lds_ragged_perstep_workspace_bytes(int B, int T, int n) {
+  if (B <= 0 || T <= 0 || n <= 0 || n > SVAE_LDS_MAX_N) return 0;
+  return ragged_table_offset_bytes(B, T, n) + (size_t)2 * n * n * sizeof(double);
 }
 
 #define SVAE_RAGGED_SWITCH(FN, ...)                                                                      \
@@ -829,6 +845,70 @@ extern "C" int svae_lds_ragged_estep_f64(int B, int T, int n, int inhomog, int p
   return -3;
 }
 
+// per-step pair parameters (T-1,n,n) or, pair_batched, (B,T-1,n,n), and an init potential per batch or, init_batched, per
+// sequence: the packed E-step in its INHOMOG + RAG instantiation; the decoupling set's blocks come from a table behind the
+// uniform workspace layout
+static size_t perstep_workspace_bytes(int B, int T, int n) {
+  return ragged_table_offset_bytes(B, T, n) + (size_t)2 * n * n * sizeof(double);
+}
+
+extern "C" int svae_lds_ragged_perstep_estep_f64(int B, int T, int n, int pair_batched, int init_batched, int keep,
+                                                 unsigned options,
+                                                 const double* init_J, const double* init_h, const double* init_logZ,
+                                                 const double* J11, const double* J12, const double* J22, const double* logZ_pair,
+                                                 const double* node_J, const double* node_h, const double* node_logZ,
+                                                 const int32_t* lengths,
+                                                 double* lognorm, double* E_init, double* E_pair,
+                                                 double* E_node_diagxx, double* E_node_x,
+                                                 int32_t* info, void* workspace, size_t ws_bytes, void* stream) {
+  if (B < 0) return -1;
+  if (T < 1) return -2;
+  if (n < 1 || n > SVAE_LDS_MAX_N) return -3;
+  if ((pair_batched & ~1) != 0 || (init_batched & ~1) != 0) return -32;
+  if (!lengths) return -31;
+  if ((keep & ~1) != 0) return -23;               /* bit 1, the cross moments of the VJP: no sweeps for this route */
+  if (!init_J) return -6;
+  if (!init_h) return -7;
+  if (!init_logZ) return -8;
+  if (T > 1 && (!J11 || !J12 || !J22 || !logZ_pair)) return -9;
+  if (!node_J) return -13;
+  if (!node_h) return -14;
+  if (!lognorm) return -16;
+  if (!E_init) return -17;
+  if (T > 1 && !E_pair) return -18;               /* (B,T-1,3,n,n): empty for T = 1 */
+  if (!E_node_diagxx) return -19;
+  if (!E_node_x) return -20;
+  if (!info) return -21;
+  Selection sel;
+  if (!decode_options(options, B, &sel)) return -24;      /* (a valid word; one route) */
+  if (B == 0) return 0;
+  if (!workspace || ws_bytes < perstep_workspace_bytes(B, T, n)) return -22;
+  double* qtab = (double*)((char*)workspace + ragged_table_offset_bytes(B, T, n));
+  hipLaunchKernelGGL(svae::lds_ragged_qtable_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, n, qtab);
+  if (hipGetLastError() != hipSuccess) return -1000;
+  svae::LdsPerstepArgs a;
+  a.tile_half = 0;
+  a.B = B; a.T = T;
+  a.init_J = init_J; a.init_h = init_h; a.init_logZ = init_logZ;
+  /* T = 1: no pair is ever addressed (pair 0 <= L-2 needs L >= 2 > T); the table stands in for the NULL arrays */
+  a.J11 = T > 1 ? J11 : qtab; a.J12 = T > 1 ? J12 : qtab; a.J22 = T > 1 ? J22 : qtab; a.logZ_pair = logZ_pair;
+  a.node_J = node_J; a.node_h = node_h; a.node_logZ = node_logZ;
+  a.lognorm = lognorm; a.E_init = E_init; a.E_pair = E_pair;
+  a.E_node_diagxx = E_node_diagxx; a.E_node_x = E_node_x;
+  a.info = info; a.ws = (double*)workspace;
+  a.ws2 = (keep & 1) ? (double*)workspace + main_ws_doubles(B, T, n) : nullptr;
+  a.ws3 = nullptr;
+  a.pair_seq_stride = (pair_batched && T > 1) ? (long)(T - 1) * n * n : 0;
+  a.msg_Jp = a.msg_hp = a.msg_Jf = a.msg_hf = nullptr;
+  a.mix_w = nullptr; a.mix_out = nullptr; a.seq_index = nullptr; a.mix_K = 0; a.lds_keep = 0;
+  a.sig_out = nullptr;
+  a.lengths = lengths;
+  a.qtab = qtab;
+  a.init_batched = init_batched;
+  SVAE_RAGGED_SWITCH(svae_lds_launch_ragged_perstep_n, &a, stream)
+  return -3;
+}
+
 static int ragged_sample(int B, int T, int n, int S, const double* eps, double* samples, const int32_t* lengths,
                          const void* workspace, void* stream) {
   svae::SampleArgs a;
@@ -856,6 +936,26 @@ extern "C" int svae_lds_ragged_inference_f64(int B, int T, int n, int S, int inh
   const int rc = svae_lds_ragged_estep_f64(B, T, n, inhomog, pair_batched, keep_vjp ? 3 : (S > 0 ? 1 : 0), options, init_J, init_h,
                                            init_logZ, J11, J12, J22, logZ_pair, node_J, node_h, node_logZ, lengths, lognorm,
                                            E_init, E_pair, E_node_diagxx, E_node_x, info, workspace, ws_bytes, stream);
+  if (rc != 0 || S == 0 || B == 0) return rc;
+  return ragged_sample(B, T, n, S, eps, samples, lengths, workspace, stream);
+}
+
+extern "C" int svae_lds_ragged_perstep_inference_f64(int B, int T, int n, int S, int pair_batched, int init_batched,
+                                                     unsigned options,
+                                                     const double* init_J, const double* init_h, const double* init_logZ,
+                                                     const double* J11, const double* J12, const double* J22,
+                                                     const double* logZ_pair,
+                                                     const double* node_J, const double* node_h, const double* node_logZ,
+                                                     const int32_t* lengths, const double* eps, double* samples,
+                                                     double* lognorm, double* E_init, double* E_pair,
+                                                     double* E_node_diagxx, double* E_node_x,
+                                                     int32_t* info, void* workspace, size_t ws_bytes, void* stream) {
+  if (n < 1 || n > SVAE_LDS_MAX_N) return -3;
+  if (S < 0 || (S > 0 && (!eps || !samples))) return -4;
+  const int rc = svae_lds_ragged_perstep_estep_f64(B, T, n, pair_batched, init_batched, S > 0 ? 1 : 0, options, init_J, init_h,
+                                                   init_logZ, J11, J12, J22, logZ_pair, node_J, node_h, node_logZ, lengths,
+                                                   lognorm, E_init, E_pair, E_node_diagxx, E_node_x, info, workspace, ws_bytes,
+                                                   stream);
   if (rc != 0 || S == 0 || B == 0) return rc;
   return ragged_sample(B, T, n, S, eps, samples, lengths, workspace, stream);
 }

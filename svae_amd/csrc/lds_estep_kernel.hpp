@@ -188,11 +188,16 @@ __device__ __forceinline__ void load_row(const double* __restrict__ p, double (&
 // of independent standard normals that adds exactly 0 to the log-normaliser and leaves the last real node without a J11 term,
 // so every DPP row keeps the uniform trip count.  Node potentials at t >= L are never used (select, not multiply: they may be
 // NaN), the node statistics there are written as 0, and the pair sums run over the row's own L-1 pairs.
+// RAG with INHOMOG (svae_lds_ragged_perstep_*, LdsPerstepArgs): the same chain with the caller's PER-STEP pair blocks at
+// pairs t <= L-2 -- (T-1,n,n), or (B,T-1,n,n) with pair_seq_stride -- and the table a.qtab = [0 | -1/2 I] at pairs t >= L-1: per
+// step a pointer select between the two, so nothing the caller stored at t >= L-1 is read (logZ_pair included).  The init
+// potential may come per sequence (a.init_batched); the per-step pair statistics of pairs t >= L-1 are written as 0.
 template <int N, bool INHOMOG, bool CHOL, bool FILT = false, bool RAG = false>
-__global__ __launch_bounds__(64) void lds_estep_kernel(const LdsArgs a) {
+__global__ __launch_bounds__(64) void lds_estep_kernel(const std::conditional_t<RAG && INHOMOG, LdsPerstepArgs, LdsArgs> a) {
   static_assert(N >= 1 && N <= SVAE_LDS_MAX_N, "n+1 lanes must fit a 16-lane DPP row");
-  static_assert(!(RAG && (INHOMOG || FILT)), "ragged launches: shared pair parameters, whole E-step");
+  static_assert(!(RAG && FILT), "ragged launches: whole E-step");
   constexpr bool PERSTEP = INHOMOG || RAG;      // the pair blocks are (re)loaded every step
+  constexpr bool RPS = RAG && INHOMOG;          // ragged launch with per-step pair blocks
   constexpr int IL = SVAE_IL;
   constexpr int HS = ws_h_stride(N), PS = ws_p_stride(N), WS = ws_step_doubles(N);
   // Above n = 10 the register tiles no longer fit 256 VGPRs: keep fewer constants resident (reload
@@ -217,7 +222,7 @@ __global__ __launch_bounds__(64) void lds_estep_kernel(const LdsArgs a) {
     len_bad = l < 1 || l > T;
     len = l < 1 ? 1 : (l > T ? T : l);
   }
-  auto pair_off = [&](int t) -> long {
+  auto pair_off = [&](int t) -> long {           // (RPS: not used, see pair_blk)
     if constexpr (RAG) return t <= len - 2 ? 0 : N * N;
     else return INHOMOG ? (long)t * N * N : 0;
   };
@@ -236,7 +241,26 @@ __global__ __launch_bounds__(64) void lds_estep_kernel(const LdsArgs a) {
   const double* pJ11 = a.J11 + (long)b * a.pair_seq_stride;
   const double* pJ12 = a.J12 + (long)b * a.pair_seq_stride;
   const double* pJ22 = a.J22 + (long)b * a.pair_seq_stride;
+  // RPS: block of pair t = the caller's (t <= len-2) or the decoupling set's (qz = 0 for J11 / J12, qd = -1/2 I for J22)
+  auto pair_blk = [&](const double* base, const double* q, int t) -> const double* {
+    return t <= len - 2 ? base + (long)t * N * N : q;
+  };
+  const double* qz = nullptr;
+  const double* qd = nullptr;
+  if constexpr (RPS) { qz = a.qtab; qd = a.qtab + N * N; }
   auto load_pair = [&](int t, bool with_next_J11) {   // pair t (and J11 of pair t+1)
+    if constexpr (RPS) {
+      const double* b11 = pair_blk(pJ11, qz, t + 1);
+      const double* b12 = pair_blk(pJ12, qz, t);
+      const double* b22 = pair_blk(pJ22, qd, t);
+      static_for<0, N>([&](auto i) {    // unconditional loads, selected afterwards
+        const double r12t = b12[cc * N + i], r22 = b22[i * N + cc], r12 = b12[i * N + cc];
+        const double r11 = with_next_J11 ? b11[i * N + cc] : 0.0;
+        NJ12T[i] = col ? r12t : 0.0;
+        if constexpr (!LOWREG) J12c[i] = col ? -r12 : 0.0;
+        Cc[i] = col ? -2.0 * (r22 + r11) : 0.0;
+      });
+    } else {
     const long o = pair_off(t);
     const long o1 = pair_off(t + 1);
     static_for<0, N>([&](auto i) {      // unconditional loads, selected afterwards
@@ -246,6 +270,7 @@ __global__ __launch_bounds__(64) void lds_estep_kernel(const LdsArgs a) {
       if constexpr (!LOWREG) J12c[i] = col ? -r12 : 0.0;
       Cc[i] = col ? -2.0 * (r22 + r11) : 0.0;
     });
+    }
   };
   if (!PERSTEP && T > 1) { load_pair(0, true); dpp_fence(NJ12T); }
 
@@ -253,10 +278,20 @@ __global__ __launch_bounds__(64) void lds_estep_kernel(const LdsArgs a) {
   // An: lanes < N = pivot block of the current step without the node diagonal (J_pred + J11; J_pred
   // alone at t = T-1); lane N = h_pred (column layout: register i holds component i).
   double An[N];
+  if constexpr (RPS) {
+    const double* iJ = a.init_J + (a.init_batched ? (long)b * N * N : 0);     // one init potential per batch or per sequence
+    const double* ihp = a.init_h + (a.init_batched ? (long)b * N : 0);
+    const double* j11_0 = pair_blk(pJ11, qz, 0);
+    static_for<0, N>([&](auto i) {
+      const double ij = iJ[i * N + cc], ih = ihp[i], j11 = T > 1 ? j11_0[i * N + cc] : 0.0;
+      An[i] = col ? -2.0 * (ij + j11) : ((c == N) ? ih : 0.0);
+    });
+  } else {
   static_for<0, N>([&](auto i) {
     const double ij = a.init_J[i * N + cc], ih = a.init_h[i], j11 = T > 1 ? pJ11[(RAG ? pair_off(0) : 0) + i * N + cc] : 0.0;
     An[i] = col ? -2.0 * (ij + j11) : ((c == N) ? ih : 0.0);
   });
+  }
 
   const double* nJ = a.node_J + ((long)b * T) * N + cc;
   const double* nh = a.node_h + ((long)b * T) * N + cc;
@@ -305,8 +340,13 @@ __global__ __launch_bounds__(64) void lds_estep_kernel(const LdsArgs a) {
       static_for<0, N>([&](auto i) { X[i] = EN * An[i]; });
     } else {
       if constexpr (LOWREG) {
+        if constexpr (RPS) {
+          const double* b12 = pair_blk(pJ12, qz, t);
+          static_for<0, N>([&](auto i) { const double r = b12[i * N + cc]; X[i] = __builtin_fma(EN, An[i], col ? -r : 0.0); });
+        } else {
         const long o = pair_off(t);
         static_for<0, N>([&](auto i) { const double r = pJ12[o + i * N + cc]; X[i] = __builtin_fma(EN, An[i], col ? -r : 0.0); });
+        }
       } else {
         static_for<0, N>([&](auto i) { X[i] = __builtin_fma(EN, An[i], J12c[i]); });
       }
@@ -371,10 +411,12 @@ __global__ __launch_bounds__(64) void lds_estep_kernel(const LdsArgs a) {
     }
     if (INHOMOG) {
       const double* lz = a.logZ_pair + (a.pair_seq_stride ? (long)bq * (T - 1) : 0);
-      for (int t = c; t < T - 1; t += 16) z += lz[t];
+      if constexpr (RPS) { for (int t = c; t < len - 1; t += 16) z += lz[t]; }      // the row's own pairs
+      else for (int t = c; t < T - 1; t += 16) z += lz[t];
     }
     double total = row_sum16(__builtin_fma(0.5, qacc * EN, z));
-    total += a.init_logZ[0];
+    if constexpr (RPS) total += a.init_logZ[a.init_batched ? bq : 0];
+    else total += a.init_logZ[0];
     if (!INHOMOG && T > 1) total += (double)((RAG ? len : T) - 1) * a.logZ_pair[0];
     total -= 0.5 * (::log(ldM) + (double)ldE * 0.6931471805599453094);
     if (valid && c == 0) a.lognorm[bq] = total;
@@ -437,9 +479,11 @@ __global__ __launch_bounds__(64) void lds_estep_kernel(const LdsArgs a) {
     double W[N + 1];
     static_for<0, N + 1>([&](auto i) { W[i] = 0.0; });
     static_for<0, (N + 1 + IL - 1) / IL>([&](auto g) { rows_src_bcast<IL, g * IL, N + 1, N>(W, S, H); });
+    if constexpr (!RPS) {   // (RPS keeps no cross moments: without the branch no block entry sits between the two DPP stages)
     if (a.ws3) {   // VJP mode: keep W~_t (rows 0..N, lanes 0..N)
       double* w3 = a.ws3 + ((long)bq * T + t) * (N + 1) * HS + c;
       if (sth) static_for<0, N + 1>([&](auto i) { w3[i * HS] = W[i]; });
+    }
     }
     // S~_t = G~ W~ + diag(P^-1, 0), computed through its transpose (S~ symmetric):
     //   S~[c][i] = sum_k G~[c][k] W~[k][i] = sum_k G~'[k](lane c) * W[k](lane i)
@@ -447,6 +491,24 @@ __global__ __launch_bounds__(64) void lds_estep_kernel(const LdsArgs a) {
     S[N] = 0.0;
     static_for<0, (N + 1 + IL - 1) / IL>([&](auto g) { rows_lane_bcast<IL, g * IL, N + 1, N>(S, W, H); });
 
+    if constexpr (RPS) {
+      // as the uniform per-step stores below, at the same addresses: the blocks of the row's own pairs (pair t <= len-2:
+      // blocks 0, 1 from step t, block 2 from step t+1 <= len-1), every other block 0 by select (the tail's moments are
+      // finite, but they are not the caller's)
+      if (st) {
+        const bool p0 = t <= len - 2, p2 = t <= len - 1;
+        if (t < T - 1) {
+          double* o = oPair + (long)t * 3 * N * N;
+          static_for<0, N>([&](auto i) { o[i * N] = p0 ? S[i] : 0.0; });
+          double* o2 = a.E_pair + (((long)bq * (T - 1) + t) * 3 + 1) * N * N + (long)cc * N;
+          static_for<0, N>([&](auto i) { o2[i] = p0 ? W[i] : 0.0; });
+        }
+        if (t > 0) {
+          double* o = oPair + ((long)(t - 1) * 3 + 2) * N * N;
+          static_for<0, N>([&](auto i) { o[i * N] = p2 ? S[i] : 0.0; });
+        }
+      }
+    } else
     if (INHOMOG) {
       // per-step pair blocks: [E x_t x_t' | E x_t x_{t+1}' | E x_{t+1} x_{t+1}'] for pair index t;
       // S~_t completes pair t (first block) and pair t-1 (third block); W~ (t < T-1) is pair t.
@@ -547,6 +609,15 @@ static int launch_estep_ragged(const LdsArgs& a, hipStream_t stream) {
   dim3 grid((a.B + 3) / 4), block(64);
   if (a.ws2 != nullptr) hipLaunchKernelGGL((lds_estep_kernel<N, false, true, false, true>), grid, block, 0, stream, a);
   else hipLaunchKernelGGL((lds_estep_kernel<N, false, false, false, true>), grid, block, 0, stream, a);
+  return hipGetLastError() == hipSuccess ? 0 : -1000;
+}
+
+// per-sequence lengths with per-step pair parameters (svae_lds_ragged_perstep_*): a.qtab, a.init_batched
+template <int N>
+static int launch_estep_ragged_perstep(const LdsPerstepArgs& a, hipStream_t stream) {
+  dim3 grid((a.B + 3) / 4), block(64);
+  if (a.ws2 != nullptr) hipLaunchKernelGGL((lds_estep_kernel<N, true, true, false, true>), grid, block, 0, stream, a);
+  else hipLaunchKernelGGL((lds_estep_kernel<N, true, false, false, true>), grid, block, 0, stream, a);
   return hipGetLastError() == hipSuccess ? 0 : -1000;
 }
 

@@ -80,3 +80,8 @@ extern "C" int SVAE_CAT(svae_lds_launch_ragged_n, SVAE_N)(const svae::LdsArgs* a
 extern "C" int SVAE_CAT(svae_lds_sample_ragged_n, SVAE_N)(const svae::SampleArgs* a, void* stream) {
   return svae::launch_sample_ragged<SVAE_N>(*a, (hipStream_t)stream);
 }
+
+// ... with per-step pair parameters and an optional per-sequence init potential (svae_lds_ragged_perstep_*)
+extern "C" int SVAE_CAT(svae_lds_launch_ragged_perstep_n, SVAE_N)(const svae::LdsPerstepArgs* a, void* stream) {
+  return svae::launch_estep_ragged_perstep<SVAE_N>(*a, (hipStream_t)stream);
+}

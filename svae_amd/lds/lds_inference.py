@@ -160,6 +160,11 @@ class LDSEStepPlan(object):
         if self.inhomog or pair_batched:
             raise ValueError("%s(lengths=): pair parameters shared by the batch and by the steps, (n,n) blocks -- per-step "
                              "or per-sequence ones are not supported with lengths" % what)
+        return self._ragged_lengths(lengths, what, self.lib.svae_lds_ragged_workspace_bytes)
+
+    def _ragged_lengths(self, lengths, what, workspace_bytes):
+        """The length handling of every ragged launch: shape / dtype checks, ONE copy of a host array (a device int32
+        tensor is used as it is), and the workspace grown to `workspace_bytes(B, T, n)`."""
         if _shape_of(lengths) != (self.B,):
             raise ValueError("%s(lengths=): lengths must have shape (B,) = (%d,), got %s" % (what, self.B, _shape_of(lengths)))
         if not (isinstance(lengths, torch.Tensor) and lengths.device == self.device and lengths.dtype == torch.int32
@@ -167,12 +172,95 @@ class LDSEStepPlan(object):
             if isinstance(lengths, torch.Tensor) and lengths.is_floating_point():
                 raise ValueError("%s(lengths=): an integer array or tensor" % what)
             lengths = torch.as_tensor(np.asarray(lengths) if not isinstance(lengths, torch.Tensor) else lengths)
+            if lengths.is_floating_point():
+                raise ValueError("%s(lengths=): an integer array or tensor" % what)
             lengths = lengths.to(device=self.device, dtype=torch.int32).contiguous()
-        need = int(self.lib.svae_lds_ragged_workspace_bytes(max(self.B, 1), self.T, self.n))
+        need = int(workspace_bytes(max(self.B, 1), self.T, self.n))
         if self.ws_bytes < need:
             self.ws = torch.empty(need // 8, dtype=torch.float64, device=self.device)
             self.ws_bytes = self.ws.numel() * 8
         return lengths
+
+    def _ragged_perstep(self, lengths, what, pair_batched, init_batched, tensors):
+        """Checks of launch_ragged_perstep / infer_ragged_perstep (ValueError before anything is launched) -> lengths."""
+        if not self.inhomog:
+            raise ValueError("%s: a plan made with inhomog=True (per-step pair statistics (B,T-1,3,n,n))" % what)
+        if self.n > _lib.LDS_MAX_N:
+            raise ValueError("%s: latent dimension <= %d (n = %d)" % (what, _lib.LDS_MAX_N, self.n))
+        if lengths is None:
+            raise ValueError("%s: lengths (B,) is required" % what)
+        B, T, n = self.B, self.T, self.n
+        init_J, init_h, init_logZ, J11, J12, J22, logZ_pair, node_J, node_h, node_logZ = tensors
+        lead_i = (B,) if init_batched else ()
+        lead_p = (B, T - 1) if pair_batched else (T - 1,)
+        want = [("init_J", init_J, lead_i + (n, n)), ("init_h", init_h, lead_i + (n,)),
+                ("node_J", node_J, (B, T, n)), ("node_h", node_h, (B, T, n))]
+        if init_batched:
+            want.append(("init_logZ", init_logZ, (B,)))
+        if T > 1:
+            want += [("J11", J11, lead_p + (n, n)), ("J12", J12, lead_p + (n, n)), ("J22", J22, lead_p + (n, n)),
+                     ("logZ_pair", logZ_pair, lead_p)]
+        if node_logZ is not None:
+            want.append(("node_logZ", node_logZ, (B, T)))
+        for name, x, shape in want:
+            if not isinstance(x, torch.Tensor) or tuple(x.shape) != shape or x.dtype != torch.float64 \
+                    or x.device != self.device or not x.is_contiguous():
+                raise ValueError("%s: %s must be a contiguous float64 tensor of shape %s on %s" % (what, name, shape, self.device))
+        return self._ragged_lengths(lengths, what, self.lib.svae_lds_ragged_perstep_workspace_bytes)
+
+    def launch_ragged_perstep(self, init_J, init_h, init_logZ, J11, J12, J22, logZ_pair, node_J, node_h, node_logZ=None,
+                              lengths=None, pair_batched=False, init_batched=False, keep_factor=False):
+        """The E-step with per-sequence lengths AND per-step pair parameters (svae_lds_ragged_perstep_estep_f64; a plan made
+        with inhomog=True, n <= 15).  Pair parameters (T-1,n,n) / (T-1), or with pair_batched (B,T-1,n,n) / (B,T-1); the init
+        potential (n,n), (n), (1), or with init_batched one per sequence, (B,n,n), (B,n), (B).  lengths (B,): as in `launch`.
+        Per sequence b of length L the results are those of the sequence cut at L; E_pair[b, L-1:] and E_node_*[b, L:] are 0;
+        pair parameters at t >= L-1 and node potentials at t >= L are never read.  `sample()` and `vjp()` cannot follow."""
+        p = _lib.ptr
+        lengths = self._ragged_perstep(lengths, "launch_ragged_perstep", pair_batched, init_batched,
+                                       (init_J, init_h, init_logZ, J11, J12, J22, logZ_pair, node_J, node_h, node_logZ))
+        rc = self.lib.svae_lds_ragged_perstep_estep_f64(
+            self.B, self.T, self.n, int(bool(pair_batched)), int(bool(init_batched)), int(bool(keep_factor)), self.options,
+            p(init_J), p(init_h), p(init_logZ), p(J11), p(J12), p(J22), p(logZ_pair),
+            p(node_J), p(node_h), p(node_logZ), p(lengths),
+            p(self.lognorm), p(self.E_init), p(self.E_pair), p(self.E_node_diagxx),
+            p(self.E_node_x), p(self.info), p(self.ws), self.ws_bytes, _lib.current_stream(self.device))
+        _lib.check(rc, "svae_lds_ragged_perstep_estep_f64")
+        self._after_ragged_perstep(lengths, J12, pair_batched, bool(keep_factor))
+
+    def infer_ragged_perstep(self, init_J, init_h, init_logZ, J11, J12, J22, logZ_pair, node_J, node_h, node_logZ=None,
+                             lengths=None, pair_batched=False, init_batched=False, eps=None, out=None):
+        """launch_ragged_perstep + the ragged sampler in one call (svae_lds_ragged_perstep_inference_f64).  eps (B,T,S,n) or
+        None -> samples (0 at t >= lengths[b]; eps there is never read) or None."""
+        p = _lib.ptr
+        S = 0
+        if eps is not None:
+            if eps.dim() != 4 or eps.shape[0] != self.B or eps.shape[1] != self.T or eps.shape[3] != self.n \
+                    or eps.shape[2] < 1:
+                raise ValueError("eps must be (B,T,S,n) with S >= 1")
+        lengths = self._ragged_perstep(lengths, "infer_ragged_perstep", pair_batched, init_batched,
+                                       (init_J, init_h, init_logZ, J11, J12, J22, logZ_pair, node_J, node_h, node_logZ))
+        if eps is not None:
+            eps = eps.to(device=self.device, dtype=torch.float64).contiguous()
+            S = eps.shape[2]
+            if out is None:
+                out = torch.empty_like(eps)
+        rc = self.lib.svae_lds_ragged_perstep_inference_f64(
+            self.B, self.T, self.n, S, int(bool(pair_batched)), int(bool(init_batched)), self.options,
+            p(init_J), p(init_h), p(init_logZ), p(J11), p(J12), p(J22), p(logZ_pair),
+            p(node_J), p(node_h), p(node_logZ), p(lengths), p(eps), p(out),
+            p(self.lognorm), p(self.E_init), p(self.E_pair), p(self.E_node_diagxx), p(self.E_node_x),
+            p(self.info), p(self.ws), self.ws_bytes, _lib.current_stream(self.device))
+        _lib.check(rc, "svae_lds_ragged_perstep_inference_f64")
+        self._after_ragged_perstep(lengths, J12, pair_batched, S > 0)
+        return out if eps is not None else None
+
+    def _after_ragged_perstep(self, lengths, J12, pair_batched, has_factor):
+        self.epoch += 1
+        self.has_factor, self.has_cross = has_factor, False       # (no cross moments: vjp() refuses)
+        self.lean, self._infer_S = False, None
+        self._J12 = J12
+        self._pair_batched = bool(pair_batched)
+        self._set_ragged(lengths)
 
     def _set_ragged(self, lengths):
         self._lengths = lengths

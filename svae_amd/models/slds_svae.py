@@ -24,7 +24,16 @@ over E[z_0]) is missing from lds_vlb / local_vlb as shipped, while its Python tw
 in that term (it also moves the stopping test); False = the Python twin (the value that is actually a bound).
 Batched: node potentials (B,T,n); every sequence runs its own coordinate ascent and stops on its own
 |delta vlb| < tol like the reference (converged sequences are frozen).
+
+Per-sequence lengths: optimize_local_meanfield(_withlabels), run_inference(_withlabels) and viterbi_labels take
+lengths= (B,) integers -- one padded batch, sequence b occupying steps 0 .. lengths[b]-1 (1 <= n <= 15, K <= 64, the
+materialised route: hmm_estep(lengths=) and LDSEStepPlan.launch_ragged_perstep with the per-sequence init potential).
+Every result up to L is that of the sequence cut at L; samples, node statistics and E_states from L on and per-step pair
+statistics from L-1 on are exactly 0, labels from L on are -1 (and ignored on input); nothing stored from L on is read (it
+may be NaN).  The SLDS has no one-step sequence: a length outside 2..T is clamped on the device and recorded in a status
+word that check_info() reports; the host never reads `lengths`.
 """
+import numpy as np
 import torch
 
 from .. import _lib
@@ -63,7 +72,76 @@ def check_info():
             word.zero_()                       # (every word is read and cleared before anything is raised)
             bad.append("%s on %s: status word %d" % (name, device, v))
     if bad:
-        raise FloatingPointError("SLDS " + "; ".join(bad) + " (parameters / potentials not positive definite)")
+        raise FloatingPointError("SLDS " + "; ".join(bad) + " (parameters / potentials not positive definite; "
+                                 "with lengths=: a length outside 2..T)")
+
+
+SLDS_RAGGED_MAX_K = 64
+
+
+def _slds_lengths(lengths, global_natparam, node_potentials, fused, what):
+    """lengths= of the SLDS entry points: every limit as a ValueError from shapes and dtypes alone, BEFORE anything is
+    launched -> (B,) int32 device tensor clamped to 2..T by device operations (a violation is ORed into the persistent
+    status word "sequence lengths"; the host never reads the values)."""
+    nh = node_potentials[1]
+    if len(tuple(nh.shape)) != 3 or tuple(node_potentials[0].shape) != tuple(nh.shape):
+        raise ValueError("%s(lengths=): diagonal node potentials J, h of shape (B,T,n)" % what)
+    B, T, n = nh.shape
+    K = len(global_natparam[1])
+    if fused:
+        raise ValueError("%s(lengths=): the fused mean-field kernels have no ragged form -- fused=None or False" % what)
+    if not (1 <= n <= _lib.LDS_MAX_N):
+        raise ValueError("%s(lengths=): latent dimension 1..%d (n = %d)" % (what, _lib.LDS_MAX_N, n))
+    if not (1 <= K <= SLDS_RAGGED_MAX_K):
+        raise ValueError("%s(lengths=): 1..%d discrete states (K = %d)" % (what, SLDS_RAGGED_MAX_K, K))
+    if T < 2:
+        raise ValueError("%s(lengths=): SLDS needs T > 1" % what)
+    is_t = isinstance(lengths, torch.Tensor)
+    ls = tuple(lengths.shape) if is_t else np.shape(lengths)
+    if ls != (B,):
+        raise ValueError("%s(lengths=): lengths must have shape (B,) = (%d,), got %r" % (what, B, ls))
+    if (lengths.is_floating_point() or lengths.is_complex() or lengths.dtype == torch.bool) if is_t \
+            else np.asarray(lengths).dtype.kind not in "iu":
+        raise ValueError("%s(lengths=): lengths must be integers" % what)
+    dev = nh.device
+    lens = lengths.to(device=dev, dtype=torch.int32) if is_t else \
+        torch.as_tensor(np.asarray(lengths).astype(np.int32), device=dev)
+    bad = ((lens < 2) | (lens > T)).any().to(torch.int32).reshape(1)
+    _status_word("sequence lengths", dev).bitwise_or_(bad)
+    return lens.clamp(2, T).contiguous()
+
+
+def _live(lens, T):
+    """(B,T) bool: t < lengths[b]"""
+    return torch.arange(T, device=lens.device)[None, :] < lens[:, None]
+
+
+def _ragged_lds_step(plan, lds_init, lds_pair, node, lens, reference_compat=True, eps=None):
+    """The LDS mean-field step of a ragged batch: LDSEStepPlan.launch_ragged_perstep (eps: infer_ragged_perstep) with the
+    per-sequence init potential passed whole -- no fold into J11[:, 0], which is the wrong pair for a sequence whose pair 0
+    is the decoupling set.  -> (lognorm (B), samples or None); the statistics stay in the plan's buffers."""
+    J0, h0, a0, b0 = lds_init
+    c = lambda x: x.contiguous()
+    lz0 = c(a0) if reference_compat else c(a0 + b0)
+    args = (c(J0), c(h0), lz0) + tuple(c(x) for x in lds_pair) + (c(node[0]), c(node[1]), c(node[2]) if len(node) > 2 else None)
+    if eps is None:
+        plan.launch_ragged_perstep(*args, lengths=lens, pair_batched=True, init_batched=True)
+        return plan.lognorm, None
+    samples = plan.infer_ragged_perstep(*args, lengths=lens, pair_batched=True, init_batched=True, eps=eps)
+    return plan.lognorm, samples
+
+
+def _ragged_plan(B, T, n, dev):
+    plan = LDSEStepPlan(B, T, n, dev, inhomog=True, pair_batched=True)
+    plan.info = _status_word("LDS E-step with lengths", dev)      # (persistent: check_info() reads it)
+    return plan
+
+
+def _masked_vlb_terms(node, dxx, ex, lens):
+    """sum_t <node potentials, statistics> per sequence with the potentials at t >= L replaced by 0 (select: they may be NaN)"""
+    live = _live(lens, node[1].shape[1])[..., None]
+    zero = torch.zeros((), dtype=torch.float64, device=node[1].device)
+    return (torch.where(live, node[0], zero) * dxx).sum((1, 2)) + (torch.where(live, node[1], zero) * ex).sum((1, 2))
 
 
 def _dev64(x, device):
@@ -492,7 +570,7 @@ def _initial_sample_path(node_potentials, eps):
 
 
 def optimize_local_meanfield(global_natparam, node_potentials, init_eps, tol=1e-2, max_iter=100, fused=None,
-                             pair_stats=True, reference_compat=True, local_maps=None):
+                             pair_stats=True, reference_compat=True, local_maps=None, lengths=None):
     """(:159-175).  Returns ((hmm_stats, lds_stats), (hmm_natparam, lds_natparam), (hmm_vlb, lds_vlb), iters).
 
     fused=None picks the fused LDS mean-field kernel (SLDSMeanfieldPlan) when it covers the shape, else the
@@ -501,9 +579,12 @@ def optimize_local_meanfield(global_natparam, node_potentials, init_eps, tol=1e-
     extra E-step on the converged mean field): callers that run their own final pass (run_inference) skip it
     and get `None` in that slot.  local_maps: the result of global_to_local_maps(global_natparam, device) where the caller
     has it already (run_inference needs it again behind the ascent: rebuilt there, its small host-to-device copies queue
-    behind the final pass's kernels and block the host for their duration)."""
+    behind the final pass's kernels and block the host for their duration).
+    lengths (B,): per-sequence lengths (module docstring) -- always the materialised route; fused=True raises."""
     hmm_global, lds_global = global_natparam
     dev = node_potentials[0].device
+    lens = None if lengths is None else _slds_lengths(lengths, global_natparam, node_potentials, fused,
+                                                      "optimize_local_meanfield")
     node = tuple(_dev64(x, dev) for x in node_potentials)
     B, T, n = node[1].shape
     hmm_init, hmm_pair, dense_init, dense_pair = local_maps if local_maps is not None else \
@@ -511,6 +592,8 @@ def optimize_local_meanfield(global_natparam, node_potentials, init_eps, tol=1e-
     K = dense_init[0].shape[0]
     if fused is None or (fused and not SLDSMeanfieldPlan.supported(n, T, K)):
         fused = SLDSMeanfieldPlan.supported(n, T, K)       # (a forced fused=True outside the kernel's coverage: the materialised path)
+    if lens is not None:
+        fused = False
     if fused:
         fplan, st, lds_vlb, iters = _optimize_local_meanfield_fused(
             hmm_init, hmm_pair, dense_init, dense_pair, node, _dev64(init_eps, dev), tol, max_iter, reference_compat)
@@ -524,9 +607,18 @@ def optimize_local_meanfield(global_natparam, node_potentials, init_eps, tol=1e-
         lds_stats = (init_stats, pstats, (fplan.E_node_diagxx, fplan.E_node_x))
         return ((st["Ei"], st["Et"], st["Es"]), lds_stats), \
             ((hmm_init, hmm_pair, st["node_hmm"]), (lds_init, lds_pair)), (st["hmm_vlb"], lds_vlb), iters
-    plan = LDSEStepPlan(B, T, n, dev, inhomog=True, pair_batched=True)
+    plan = LDSEStepPlan(B, T, n, dev, inhomog=True, pair_batched=True) if lens is None else _ragged_plan(B, T, n, dev)
 
-    init_stats, pair_stats = initialize_local_meanfield(node, _dev64(init_eps, dev))
+    if lens is None:
+        init_stats, pair_stats = initialize_local_meanfield(node, _dev64(init_eps, dev))
+    else:
+        # the ragged filter + sampler on the random-walk model (the diagonal kernel has no ragged form and would read the
+        # padding); x[b, L:] = 0, and what the statistics of pairs t >= L-1 give lands in HMM node rows that are never read
+        x = natural_lds_sample(_random_walk_natparam(n, dev), node, num_samples=1, eps=_dev64(init_eps, dev),
+                               lengths=lens)[:, :, 0]
+        out = lambda a, b: a.unsqueeze(-1) * b.unsqueeze(-2)
+        init_stats = (out(x[:, 0], x[:, 0]), x[:, 0])
+        pair_stats = (out(x[:, :-1], x[:, :-1]), out(x[:, :-1], x[:, 1:]), out(x[:, 1:], x[:, 1:]))
     vlb = torch.full((B,), -float("inf"), dtype=torch.float64, device=dev)
     active = torch.ones(B, dtype=torch.bool, device=dev)
     iters = torch.zeros(B, dtype=torch.int64, device=dev)
@@ -546,12 +638,16 @@ def optimize_local_meanfield(global_natparam, node_potentials, init_eps, tol=1e-
 
     for _ in range(max_iter):
         node_hmm = get_arhmm_local_nodeparams(dense_init, dense_pair, init_stats, pair_stats)
-        hmm_vlb, (Ei, Et, Es) = hmm_estep((hmm_init, hmm_pair, node_hmm))
+        hmm_vlb, (Ei, Et, Es) = hmm_estep((hmm_init, hmm_pair, node_hmm), lengths=lens)
         lds_init, lds_pair = get_var_lds_local_natparam(dense_init, dense_pair, Es)
-        # the E-step API takes one shared init potential per launch: fold each sequence's init
-        # potential into its first node potential instead (identical model: both multiply x_0's factor)
-        lds_vlb, (Ei_l, Ep_l, En_l) = _lds_estep_batched_init(plan, lds_init, lds_pair, node,
-                                                              reference_compat=reference_compat)
+        if lens is not None:
+            lds_vlb, _ = _ragged_lds_step(plan, lds_init, lds_pair, node, lens, reference_compat)
+            En_l = (plan.E_node_diagxx, plan.E_node_x)
+        else:
+            # the E-step API takes one shared init potential per launch: fold each sequence's init
+            # potential into its first node potential instead (identical model: both multiply x_0's factor)
+            lds_vlb, (Ei_l, Ep_l, En_l) = _lds_estep_batched_init(plan, lds_init, lds_pair, node,
+                                                                  reference_compat=reference_compat)
         all_active = bool(active.all())
         for name, val in (("Ei", Ei), ("Et", Et), ("Es", Es), ("node_hmm", node_hmm), ("E_init", plan.E_init),
                           ("E_pair", plan.E_pair), ("dxx", En_l[0]), ("ex", En_l[1]), ("hmm_vlb", hmm_vlb),
@@ -573,20 +669,41 @@ def optimize_local_meanfield(global_natparam, node_potentials, init_eps, tol=1e-
         ((hmm_init, hmm_pair, state["node_hmm"]), (lds_init, lds_pair)), (state["hmm_vlb"], state["lds_vlb"]), iters
 
 
-def optimize_local_meanfield_withlabels(global_natparam, node_potentials, labels):
-    """(:178-200) discrete states given: HMM stats from the labels (B,T) int, then one LDS mean-field step."""
+def optimize_local_meanfield_withlabels(global_natparam, node_potentials, labels, lengths=None):
+    """(:178-200) discrete states given: HMM stats from the labels (B,T) int, then one LDS mean-field step.
+    lengths (B,): per-sequence lengths (module docstring); labels[b, L:] are ignored whatever they hold (hmm_viterbi's -1
+    included), the indicators and the smoothed node statistics are 0 there, transitions are counted over t <= L-2."""
     hmm_global, lds_global = global_natparam
     dev = node_potentials[0].device
+    lens = None if lengths is None else _slds_lengths(lengths, global_natparam, node_potentials, False,
+                                                      "optimize_local_meanfield_withlabels")
     node = tuple(_dev64(x, dev) for x in node_potentials)
     B, T, n = node[1].shape
     K = torch.as_tensor(hmm_global[0]).shape[0]
     labels = torch.as_tensor(labels, device=dev).long()
+    if lens is not None:
+        if tuple(labels.shape) != (B, T):
+            raise ValueError("optimize_local_meanfield_withlabels(lengths=): labels must have shape (B,T)")
+        live = _live(lens, T)
+        labels = torch.where(live, labels, torch.zeros_like(labels))
     ind = torch.nn.functional.one_hot(labels, K).to(torch.float64)             # (B,T,K)
+    if lens is not None:
+        ind = ind * live[..., None]
     E_trans = torch.einsum("bti,btj->bij", ind[:, :-1], ind[:, 1:])
     soft = ind + 1e-2
     hmm_stats = (ind[:, 0], E_trans, soft / soft.sum(-1, keepdim=True))
+    if lens is not None:
+        hmm_stats = (hmm_stats[0], E_trans, hmm_stats[2] * live[..., None])
     _, _, dense_init, dense_pair = global_to_local_maps(global_natparam, dev)
     lds_init, lds_pair = get_var_lds_local_natparam(dense_init, dense_pair, hmm_stats[2])
+    if lens is not None:
+        plan = _ragged_plan(B, T, n, dev)
+        lds_vlb, _ = _ragged_lds_step(plan, lds_init, lds_pair, node, lens)
+        Ei = plan.E_init
+        lds_stats = ((Ei[:, :n * n].reshape(B, n, n).clone(), Ei[:, n * n:].clone()),
+                     tuple(plan.E_pair[:, :, i].clone() for i in range(3)),
+                     (plan.E_node_diagxx.clone(), plan.E_node_x.clone()))
+        return (hmm_stats, lds_stats), (None, (lds_init, lds_pair)), (torch.zeros_like(lds_vlb), lds_vlb.clone())
     plan = LDSEStepPlan(B, T, n, dev, inhomog=True, pair_batched=True)
     lds_vlb, (Ei, Ep, En) = _lds_estep_batched_init(plan, lds_init, lds_pair, node)
     lds_stats = ((Ei[0].clone(), Ei[1].clone()), tuple(x.clone() for x in Ep[:3]), tuple(x.clone() for x in En[:2]))
@@ -654,12 +771,14 @@ def global_stats_as_natparam(stats):
 
 
 def run_inference(prior_natparam, global_natparam, nn_potentials, num_samples, init_eps=None, eps=None,
-                  generator=None, tol=1e-2, group=None, reference_compat=True):
+                  generator=None, tol=1e-2, group=None, reference_compat=True, lengths=None):
     """(:289-310) -> (samples (B,T,S,n), expected_stats, global_vlb, local_vlb); forward values only
     (see run_inference_differentiable).  Under torch.distributed the sequences are this rank's shard (every
     sequence runs its own coordinate ascent: no collective inside it); the statistics and local_vlb are summed
-    over the ranks of `group` with ONE all-reduce."""
+    over the ranks of `group` with ONE all-reduce.
+    lengths (B,): per-sequence lengths (module docstring): samples[b, L:] = 0; the padding, NaN included, reaches no sum."""
     dev = nn_potentials[1].device
+    lens = None if lengths is None else _slds_lengths(lengths, global_natparam, nn_potentials, False, "run_inference")
     node = tuple(_dev64(x, dev) for x in nn_potentials)
     B, T, n = node[1].shape
     if init_eps is None:
@@ -670,13 +789,21 @@ def run_inference(prior_natparam, global_natparam, nn_potentials, num_samples, i
     host_params = (_HostParamsLater(global_natparam), _HostParamsLater(prior_natparam))
     maps = global_to_local_maps(global_natparam, dev)
     (hmm_stats, _), (hmm_nat, (lds_init, lds_pair)), _, _ = optimize_local_meanfield(
-        global_natparam, node, init_eps, tol, pair_stats=False, reference_compat=reference_compat, local_maps=maps)
-    plan = LDSEStepPlan(B, T, n, dev, inhomog=True, pair_batched=True)
+        global_natparam, node, init_eps, tol, pair_stats=False, reference_compat=reference_compat, local_maps=maps,
+        lengths=lens)
+    plan = LDSEStepPlan(B, T, n, dev, inhomog=True, pair_batched=True) if lens is None else _ragged_plan(B, T, n, dev)
     S = int(num_samples)
     if eps is None:
         eps = torch.randn(B, T, S, n, dtype=torch.float64, device=dev, generator=generator)
     eps = _dev64(eps, dev)
-    if n <= _lib.LDS_MAX_N and S <= 16:
+    if lens is not None:
+        # final E-step + sampler on the per-step parameters of the converged mean field, per-sequence init potential
+        lognorm, samples = _ragged_lds_step(plan, lds_init, lds_pair, node, lens, reference_compat, eps=eps if S > 0 else None)
+        if samples is None:
+            samples = eps
+        Ei = (plan.E_init[:, :n * n].reshape(B, n, n), plan.E_init[:, n * n:])
+        En = (plan.E_node_diagxx, plan.E_node_x)
+    elif n <= _lib.LDS_MAX_N and S <= 16:
         # final E-step + sampler in ONE call on the per-step parameters of the converged mean field (lean records above
         # 1024 sequences: csrc/lds_lean_estep.hpp, INH), J0 added into the mixed J11 in place
         lognorm, (Ei, Ep, En) = _lds_estep_batched_init(plan, lds_init, lds_pair, node, keep_factor=True,
@@ -690,48 +817,66 @@ def run_inference(prior_natparam, global_natparam, nn_potentials, num_samples, i
     fused = final_pass_contractions(dense_init, dense_pair, (Ei[0], Ei[1]), plan.E_pair, hmm_stats[2])
     node_hmm, pair_sums = fused if fused is not None else \
         (get_arhmm_local_nodeparams(dense_init, dense_pair, (Ei[0], Ei[1]), plan.E_pair), None)
-    hmm_vlb, _ = hmm_estep((hmm_nat[0], hmm_nat[1], node_hmm))
+    # (lengths: E_states[b, L:] and E_pair[b, L-1:] are exactly 0, so the weighted sums and the pair count need no mask)
+    hmm_vlb, _ = hmm_estep((hmm_nat[0], hmm_nat[1], node_hmm), lengths=lens)
     expected_stats = get_global_stats(hmm_stats, (Ei[0], Ei[1]), plan.E_pair, pair_sums)
-    lds_vlb = lognorm - ((node[0] * En[0]).sum((1, 2)) + (node[1] * En[1]).sum((1, 2)))
+    if lens is not None:
+        lds_vlb = lognorm - _masked_vlb_terms(node, En[0], En[1], lens)
+    else:
+        lds_vlb = lognorm - ((node[0] * En[0]).sum((1, 2)) + (node[1] * En[1]).sum((1, 2)))
     local_vlb = (hmm_vlb + lds_vlb).sum()
     expected_stats, local_vlb = allreduce_nested(expected_stats, local_vlb, group)
     global_vlb = slds_prior_vlb(host_params[0], host_params[1], dev)
     return samples, expected_stats, global_vlb, local_vlb
 
 
-def viterbi_labels(global_natparam, nn_potentials, init_eps=None, generator=None, tol=1e-2, reference_compat=True):
+def viterbi_labels(global_natparam, nn_potentials, init_eps=None, generator=None, tol=1e-2, reference_compat=True,
+                   lengths=None):
     """The segmentation of a batch of sequences under the model: the local mean field is optimised as in run_inference,
     then the most probable discrete path under the converged HMM factor (its init / pair potentials and the node
     potentials the LDS factor's statistics give) is decoded with hmm_viterbi.
-    -> (labels (B,T) int32, score (B)); the labels are what run_inference_withlabels consumes."""
+    -> (labels (B,T) int32, score (B)); the labels are what run_inference_withlabels consumes.
+    lengths (B,): per-sequence lengths (module docstring); labels[b, L:] = -1, which run_inference_withlabels(lengths=)
+    takes as they are."""
     dev = nn_potentials[1].device
+    lens = None if lengths is None else _slds_lengths(lengths, global_natparam, nn_potentials, False, "viterbi_labels")
     node = tuple(_dev64(x, dev) for x in nn_potentials)
     B, T, n = node[1].shape
     if init_eps is None:
         init_eps = torch.randn(B, T, 1, n, dtype=torch.float64, device=dev, generator=generator)
     _, (hmm_nat, _), _, _ = optimize_local_meanfield(global_natparam, node, init_eps, tol, pair_stats=False,
-                                                     reference_compat=reference_compat)
-    return hmm_viterbi(hmm_nat, return_score=True)
+                                                     reference_compat=reference_compat, lengths=lens)
+    return hmm_viterbi(hmm_nat, return_score=True, lengths=lens)
 
 
 def run_inference_withlabels(prior_natparam, global_natparam, potentials_and_labels, num_samples, eps=None,
-                             generator=None, group=None, reference_compat=True):
+                             generator=None, group=None, reference_compat=True, lengths=None):
     """(:313-334) run_inference with the discrete states GIVEN: potentials_and_labels = (nn_potentials, labels (B,T) int).
     -> (samples (B,T,S,n), expected_stats, global_vlb, local_vlb) with local_vlb = the LDS bound only (no HMM term);
-    forward values only.  Statistics and local_vlb are summed over the ranks of `group` with one all-reduce."""
+    forward values only.  Statistics and local_vlb are summed over the ranks of `group` with one all-reduce.
+    lengths (B,): per-sequence lengths (module docstring); labels[b, L:] are ignored (viterbi_labels' -1 included)."""
     nn_potentials, labels = potentials_and_labels
     dev = nn_potentials[1].device
+    lens = None if lengths is None else _slds_lengths(lengths, global_natparam, nn_potentials, False,
+                                                      "run_inference_withlabels")
     node = tuple(_dev64(x, dev) for x in nn_potentials)
     B, T, n = node[1].shape
     host_params = (_HostParamsLater(global_natparam), _HostParamsLater(prior_natparam))
-    (hmm_stats, _), (_, (lds_init, lds_pair)), _ = optimize_local_meanfield_withlabels(global_natparam, node, labels)
+    (hmm_stats, _), (_, (lds_init, lds_pair)), _ = optimize_local_meanfield_withlabels(global_natparam, node, labels,
+                                                                                      lengths=lens)
     # the final E-step + sampler of run_inference, on the per-step parameters the labels give
-    plan = LDSEStepPlan(B, T, n, dev, inhomog=True, pair_batched=True)
+    plan = LDSEStepPlan(B, T, n, dev, inhomog=True, pair_batched=True) if lens is None else _ragged_plan(B, T, n, dev)
     S = int(num_samples)
     if eps is None:
         eps = torch.randn(B, T, S, n, dtype=torch.float64, device=dev, generator=generator)
     eps = _dev64(eps, dev)
-    if n <= _lib.LDS_MAX_N and S <= 16:
+    if lens is not None:
+        lognorm, samples = _ragged_lds_step(plan, lds_init, lds_pair, node, lens, reference_compat, eps=eps if S > 0 else None)
+        if samples is None:
+            samples = eps
+        Ei = (plan.E_init[:, :n * n].reshape(B, n, n), plan.E_init[:, n * n:])
+        En = (plan.E_node_diagxx, plan.E_node_x)
+    elif n <= _lib.LDS_MAX_N and S <= 16:
         lognorm, (Ei, Ep, En) = _lds_estep_batched_init(plan, lds_init, lds_pair, node, keep_factor=True,
                                                         reference_compat=reference_compat, eps=eps)
         samples = plan._infer_samples
@@ -740,7 +885,10 @@ def run_inference_withlabels(prior_natparam, global_natparam, potentials_and_lab
                                                         reference_compat=reference_compat)
         samples = plan.sample(eps)
     expected_stats = get_global_stats(hmm_stats, (Ei[0], Ei[1]), plan.E_pair)
-    lds_vlb = lognorm - ((node[0] * En[0]).sum((1, 2)) + (node[1] * En[1]).sum((1, 2)))
+    if lens is not None:
+        lds_vlb = lognorm - _masked_vlb_terms(node, En[0], En[1], lens)
+    else:
+        lds_vlb = lognorm - ((node[0] * En[0]).sum((1, 2)) + (node[1] * En[1]).sum((1, 2)))
     local_vlb = lds_vlb.sum()
     expected_stats, local_vlb = allreduce_nested(expected_stats, local_vlb, group)
     global_vlb = slds_prior_vlb(host_params[0], host_params[1], dev)
@@ -868,11 +1016,15 @@ def final_pass_differentiable(global_natparam, hmm_natparam, lds_natparam, nn_po
 
 
 def run_inference_differentiable(prior_natparam, global_natparam, nn_potentials, num_samples, init_eps=None,
-                                 eps=None, generator=None, tol=1e-2, group=None, reference_compat=True):
+                                 eps=None, generator=None, tol=1e-2, group=None, reference_compat=True, lengths=None):
     """run_inference (slds_svae.py:289-310) with torch autograd attached to nn_potentials = (J, h),
     each (B,T,n): the local mean field is optimised on detached values (the reference's `unbox`),
     then the final pass is differentiated through the E-step / sampler VJP kernels and the HMM
-    kernel.  -> (samples (B,T,S,n), expected_stats, global_vlb, local_vlb)."""
+    kernel.  -> (samples (B,T,S,n), expected_stats, global_vlb, local_vlb).
+    lengths: not supported (the VJP sweeps have no form for per-step pair parameters with lengths): ValueError."""
+    if lengths is not None:
+        raise ValueError("run_inference_differentiable(lengths=): no gradients for a ragged SLDS batch -- the VJP sweeps for "
+                         "per-step pair parameters with lengths are not built (run_inference(lengths=) gives forward values)")
     dev = nn_potentials[1].device
     node_d = tuple(_dev64(x, dev) for x in nn_potentials)
     B, T, n = node_d[1].shape
@@ -895,11 +1047,15 @@ def run_inference_differentiable(prior_natparam, global_natparam, nn_potentials,
 
 
 def run_inference_withlabels_differentiable(prior_natparam, global_natparam, potentials_and_labels, num_samples,
-                                            eps=None, generator=None, group=None, reference_compat=True):
+                                            eps=None, generator=None, group=None, reference_compat=True, lengths=None):
     """run_inference_withlabels with torch autograd attached to nn_potentials = (J, h), each (B,T,n): the labelled
     mean-field step runs on detached values (the reference's `unbox`, :319), the final E-step + sampler is
     differentiated through the VJP kernels.  The signature make_gradfun calls with `recognize` returning
-    (nn_potentials, labels).  -> (samples (B,T,S,n), expected_stats, global_vlb, local_vlb)."""
+    (nn_potentials, labels).  -> (samples (B,T,S,n), expected_stats, global_vlb, local_vlb).
+    lengths: not supported (see run_inference_differentiable): ValueError."""
+    if lengths is not None:
+        raise ValueError("run_inference_withlabels_differentiable(lengths=): no gradients for a ragged SLDS batch -- the VJP "
+                         "sweeps for per-step pair parameters with lengths are not built")
     nn_potentials, labels = potentials_and_labels
     dev = nn_potentials[1].device
     node_d = tuple(_dev64(x, dev) for x in nn_potentials)
