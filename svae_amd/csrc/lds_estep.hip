@@ -1,41 +1,30 @@
-// lds_estep.hip -- C ABI (include/svae_hip.h) of the batched LDS E-step: argument checks, dispatch
-// on the latent dimension to the per-n kernels (lds_estep_n.hip), and the deterministic batch
-// reduction of the global statistics.
+// lds_estep.hip -- host side of the register-path LDS C ABI (include/svae_hip.h, 1 <= n <= 15): argument checks, kernel
+// selection and workspace layout of the uniform entry points (E-step, filter, sampler, fused inference, SLDS mean-field
+// step, VJPs) and of the per-sequence-length ones (svae_lds_ragged_*).  Every launch goes through the per-n unit tables
+// (lds_units.hpp; defined by lds_estep_n.hip and lds_vjp_n.hip); svae_lds_estep_f64 hands 16 <= n <= 64 to the tiled
+// path (lds_estep_tile.hip).  Device code here: the deterministic batch reduction of the global statistics and the
+// one-workgroup table / count kernels of the ragged entry points.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdlib.h>
 
 #include "../../include/svae_hip.h"
-#include "lds_args.hpp"
+#include "lds_units.hpp"
 #include "per_device.hpp"
 
-extern "C" {
-#define SVAE_DECL_(NN) int svae_lds_launch_n##NN(const svae::LdsArgs*, int, void*); \
-  int svae_lds_launch_split_n##NN(const svae::LdsArgs*, int, void*);           \
-  int svae_lds_launch_twoend_n##NN(const svae::LdsArgs*, int, int, int, void*);          \
-  int svae_lds_launch_twoend_mix_n##NN(const svae::LdsArgs*, void*);          \
-  int svae_lds_launch_slds_rpc_n##NN(const svae::LdsArgs*, int, int, void*);  \
-  int svae_lds_launch_filter_n##NN(const svae::LdsArgs*, int, void*);          \
-  int svae_lds_launch_filter_split_n##NN(const svae::LdsArgs*, int, void*);    \
-  int svae_lds_launch_filter_1r_n##NN(const svae::LdsArgs*, int, void*);       \
-  int svae_lds_launch_forward_pair_n##NN(const svae::LdsArgs*, const svae::LdsArgs*, int, void*); \
-  int svae_lds_sample_n##NN(const svae::SampleArgs*, void*);                   \
-  int svae_lds_vjp_n##NN(const svae::VjpArgs*, void*);                         \
-  int svae_lds_infer_lean_n##NN(const svae::LdsArgs*, const svae::LeanSample*, int, void*); \
-  int svae_lds_vjp_lean_n##NN(const svae::VjpArgs*, void*);                    \
-  int svae_lds_launch_ragged_n##NN(const svae::LdsArgs*, void*);               \
-  int svae_lds_launch_ragged_perstep_n##NN(const svae::LdsPerstepArgs*, void*); \
-  int svae_lds_sample_ragged_n##NN(const svae::SampleArgs*, void*);            \
-  int svae_lds_vjp_ragged_n##NN(const svae::VjpArgs*, void*);
-#define SVAE_DECL(NN) SVAE_DECL_(NN)
-#ifdef SVAE_ONLY_N   /* experimental single-n builds (tools/build_variant.sh) */
-SVAE_DECL(SVAE_ONLY_N)
-#else
-SVAE_DECL(1) SVAE_DECL(2) SVAE_DECL(3) SVAE_DECL(4) SVAE_DECL(5) SVAE_DECL(6) SVAE_DECL(7)
-SVAE_DECL(8) SVAE_DECL(9) SVAE_DECL(10) SVAE_DECL(11) SVAE_DECL(12) SVAE_DECL(13) SVAE_DECL(14)
-SVAE_DECL(15)
-#endif
+// the per-n units: units[n] for 1 <= n <= SVAE_LDS_MAX_N (every entry point checks n before it looks one up)
+#define SVAE_DECL(NN) extern "C" const svae::EstepUnit svae_lds_estep_unit_n##NN; \
+                      extern "C" const svae::VjpUnit svae_lds_vjp_unit_n##NN;
+SVAE_LDS_NS(SVAE_DECL)
 #undef SVAE_DECL
+#define SVAE_ESTEP(NN) &svae_lds_estep_unit_n##NN,
+#define SVAE_VJP(NN) &svae_lds_vjp_unit_n##NN,
+static const svae::EstepUnit* const estep_units[SVAE_LDS_MAX_N + 1] = {nullptr, SVAE_LDS_NS(SVAE_ESTEP)};
+static const svae::VjpUnit* const vjp_units[SVAE_LDS_MAX_N + 1] = {nullptr, SVAE_LDS_NS(SVAE_VJP)};
+#undef SVAE_ESTEP
+#undef SVAE_VJP
+
+extern "C" {
 /* 16 <= n <= SVAE_LDS_TILE_MAX_N: LDS-tiled MFMA path (lds_estep_tile.hip) */
 int svae_lds_launch_tile(const svae::LdsArgs*, int n, int inhomog, void* stream);
 size_t svae_lds_tile_step_doubles(int n);
@@ -101,6 +90,26 @@ __global__ __launch_bounds__(256) void lds_reduce_stats_kernel(int B, int n, con
 
 }  // namespace svae
 
+static void launch_reduce_stats(int B, int n, const double* E_init, const double* E_pair, const double* lognorm,
+                                double* out, void* stream) {
+  const int tot = 4 * n * n + n + 1;
+  hipLaunchKernelGGL(svae::lds_reduce_stats_kernel, dim3((tot + 7) / 8), dim3(256), 0,
+                     (hipStream_t)stream, B, n, E_init, E_pair, lognorm, out);
+}
+
+// svae_lds_reduce_stats_f64 and its XL twin: the same checks and launch, each on its own range of n
+static int reduce_stats(int B, int n, int n_min, int n_max, const double* E_init, const double* E_pair,
+                        const double* lognorm, double* out, void* stream) {
+  if (B < 0) return -1;
+  if (n < n_min || n > n_max) return -2;
+  if (!E_init) return -3;
+  if (!E_pair) return -4;
+  if (!lognorm) return -5;
+  if (!out) return -6;
+  launch_reduce_stats(B, n, E_init, E_pair, lognorm, out, stream);
+  return hipGetLastError() == hipSuccess ? 0 : -1000;
+}
+
 #ifndef SVAE_FILTER_WIDE_MAX_B
 #define SVAE_FILTER_WIDE_MAX_B 6144     // filter-only launches without message outputs: the one-register filter (two sequences per wavefront beyond 512) up to this batch; measured 4096: 0.89 vs 0.96 ms packed, 8192: equal
 #endif
@@ -155,6 +164,14 @@ static size_t main_ws_doubles(int B, int T, int n) {
 static size_t factor_ws_doubles(int B, int T, int n) { return (size_t)B * T * (n * n + n); }
 static size_t cross_ws_doubles(int B, int T, int n) { return (size_t)B * T * (n + 1) * svae::ws_h_stride(n); }
 
+// the regions behind the main one that a launch keeps (or a reader looks for): keep bit 0 = the factor region of the
+// sampler, bit 1 = the cross moments of the VJP behind it; nullptr for a bit that is not set
+struct Kept { double* factor; double* cross; };
+static Kept kept_regions(const void* workspace, int B, int T, int n, int keep) {
+  double* factor = (double*)workspace + main_ws_doubles(B, T, n);
+  return {(keep & 1) ? factor : nullptr, (keep & 2) ? factor + factor_ws_doubles(B, T, n) : nullptr};
+}
+
 size_t svae_lds_tile_sigma_offset_bytes(int B, int T, int n, int inhomog, int pair_batched) {
   if (n <= SVAE_LDS_MAX_N || n > SVAE_LDS_TILE_MAX_N) return 0;
   return (svae_lds_workspace_bytes_ex(B, T, n, inhomog, pair_batched) + 255) / 256 * 256;
@@ -186,18 +203,11 @@ int svae_lds_estep_f64(int B, int T, int n, int inhomog, int pair_batched, int k
   if (n < 1 || n > SVAE_LDS_TILE_MAX_N) return -3;
   if (n > SVAE_LDS_MAX_N ? (keep & ~SVAE_KEEP_SIGMA) != 0 : (keep & ~3) != 0) return -23;   /* factor / cross regions: register path; Sigma: tiled path */
   if (pair_batched && !inhomog) return -5;
-  if (!init_J) return -6;
-  if (!init_h) return -7;
-  if (!init_logZ) return -8;
-  if (T > 1 && (!J11 || !J12 || !J22 || !logZ_pair)) return -9;
-  if (!node_J) return -13;
-  if (!node_h) return -14;
-  if (!lognorm) return -16;
-  if (!E_init) return -17;
-  if (!E_pair) return -18;
-  if (!E_node_diagxx) return -19;
-  if (!E_node_x) return -20;
-  if (!info) return -21;
+  svae::LdsArgs a{};
+  svae::set_estep_args(a, B, T, n, pair_batched, init_J, init_h, init_logZ, J11, J12, J22, logZ_pair, node_J, node_h, node_logZ,
+                       lognorm, E_init, E_pair, E_node_diagxx, E_node_x, info, workspace);
+  if (const int rc = svae::check_model(a)) return rc;
+  if (const int rc = svae::check_arrays(a)) return rc;
   if (!workspace || ws_bytes < svae_lds_workspace_bytes_ex(B, T, n, inhomog, pair_batched)) return -22;
   Selection sel;
   const unsigned tile_bits = options & (SVAE_OPT_TILE_FORWARD | SVAE_OPT_TILE_BACKWARD);
@@ -206,23 +216,8 @@ int svae_lds_estep_f64(int B, int T, int n, int inhomog, int pair_batched, int k
   if (B == 0) return 0;
   const int twoend = sel.twoend;
 
-  svae::LdsArgs a;
   a.tile_half = (tile_bits & SVAE_OPT_TILE_FORWARD) ? 1 : (tile_bits & SVAE_OPT_TILE_BACKWARD) ? 2 : 0;
-  a.B = B; a.T = T;
-  a.init_J = init_J; a.init_h = init_h; a.init_logZ = init_logZ;
-  a.J11 = J11; a.J12 = J12; a.J22 = J22; a.logZ_pair = logZ_pair;
-  a.node_J = node_J; a.node_h = node_h; a.node_logZ = node_logZ;
-  a.lognorm = lognorm; a.E_init = E_init; a.E_pair = E_pair;
-  a.E_node_diagxx = E_node_diagxx; a.E_node_x = E_node_x;
-  a.info = info; a.ws = (double*)workspace;
-  a.ws2 = (keep & 1) ? (double*)workspace + main_ws_doubles(B, T, n) : nullptr;
-  a.ws3 = (keep & 2) ? (double*)workspace + main_ws_doubles(B, T, n) + factor_ws_doubles(B, T, n) : nullptr;
-  a.pair_seq_stride = pair_batched ? (long)(T - 1) * n * n : 0;
-  a.msg_Jp = a.msg_hp = a.msg_Jf = a.msg_hf = nullptr;
-  a.mix_w = nullptr; a.mix_out = nullptr; a.seq_index = nullptr; a.mix_K = 0; a.lds_keep = 0;
-  a.sig_out = nullptr;
   if (n > SVAE_LDS_MAX_N) {
-    a.ws2 = a.ws3 = nullptr;
     if (keep & SVAE_KEEP_SIGMA) {
       const size_t off = svae_lds_tile_sigma_offset_bytes(B, T, n, inhomog, pair_batched);
       if (ws_bytes < off + (size_t)B * T * n * n * sizeof(double)) return -22;
@@ -230,6 +225,9 @@ int svae_lds_estep_f64(int B, int T, int n, int inhomog, int pair_batched, int k
     }
     return svae_lds_launch_tile(&a, n, inhomog, stream);
   }
+  const Kept kept = kept_regions(workspace, B, T, n, keep);
+  a.ws2 = kept.factor; a.ws3 = kept.cross;
+  const svae::EstepUnit* unit = estep_units[n];
   const bool split = sel.split;
   if (twoend && keep && split && n <= svae::TE_MAX_N && T >= svae::TE_MIN_T) {
     // Small batch, hand-off kept: the statistics (and the cross moments the VJP reads: posterior moments, the same
@@ -239,56 +237,18 @@ int svae_lds_estep_f64(int B, int T, int n, int inhomog, int pair_batched, int k
     // Round 4: both in ONE launch (lds_forward_pair_kernel: the first B workgroups take the filter's body, the next
     // B the E-step's) instead of two kernels on two streams forked and joined by events (0.31 -> 0.27 ms at B = 512).
     svae::LdsArgs f = a;                       // the filter: one-directional layout at the start of the workspace
-    f.ws2 = (double*)workspace + main_ws_doubles(B, T, n);
+    f.ws2 = kept_regions(workspace, B, T, n, 1).factor;
     f.ws3 = nullptr;
-    f.lognorm = (double*)workspace + main_ws_doubles(B, T, n) - B;      // scratch (the E-step's lognorm is the other kernel's)
+    f.lognorm = f.ws2 - B;                     // scratch: the B doubles that end the main region (the E-step's lognorm is the other kernel's)
     f.E_init = nullptr; f.E_pair = nullptr; f.E_node_diagxx = nullptr; f.E_node_x = nullptr;
     svae::LdsArgs e = a;                       // the E-step: two-ended records behind the one-directional ones
     e.ws = (double*)workspace + one_ws_doubles(B, T, n);
     e.ws2 = nullptr;
-    switch (n) {
-#define SVAE_CASE_(NN) case NN: return svae_lds_launch_forward_pair_n##NN(&f, &e, inhomog, stream);
-#define SVAE_CASE(NN) SVAE_CASE_(NN)
-#ifdef SVAE_ONLY_N
-      SVAE_CASE(SVAE_ONLY_N)
-#else
-      SVAE_CASE(1) SVAE_CASE(2) SVAE_CASE(3) SVAE_CASE(4) SVAE_CASE(5) SVAE_CASE(6) SVAE_CASE(7)
-      SVAE_CASE(8) SVAE_CASE(9) SVAE_CASE(10)
-#endif
-#undef SVAE_CASE
-#undef SVAE_CASE_
-    }
-    return -3;
+    return unit->forward_pair(f, e, inhomog, stream);
   }
-  if (twoend && !keep && n <= svae::TE_MAX_N && T >= svae::TE_MIN_T) {
-    switch (n) {
-#define SVAE_CASE_(NN) case NN: return svae_lds_launch_twoend_n##NN(&a, inhomog, twoend == 1 && !inhomog, sel.layout, stream);
-#define SVAE_CASE(NN) SVAE_CASE_(NN)
-#ifdef SVAE_ONLY_N
-      SVAE_CASE(SVAE_ONLY_N)
-#else
-      SVAE_CASE(1) SVAE_CASE(2) SVAE_CASE(3) SVAE_CASE(4) SVAE_CASE(5) SVAE_CASE(6) SVAE_CASE(7)
-      SVAE_CASE(8) SVAE_CASE(9) SVAE_CASE(10)
-#endif
-#undef SVAE_CASE
-#undef SVAE_CASE_
-    }
-  }
-  switch (n) {
-#define SVAE_CASE_(NN) case NN: return split ? svae_lds_launch_split_n##NN(&a, inhomog, stream) \
-                                             : svae_lds_launch_n##NN(&a, inhomog, stream);
-#define SVAE_CASE(NN) SVAE_CASE_(NN)
-#ifdef SVAE_ONLY_N
-    SVAE_CASE(SVAE_ONLY_N)
-#else
-    SVAE_CASE(1) SVAE_CASE(2) SVAE_CASE(3) SVAE_CASE(4) SVAE_CASE(5) SVAE_CASE(6) SVAE_CASE(7)
-    SVAE_CASE(8) SVAE_CASE(9) SVAE_CASE(10) SVAE_CASE(11) SVAE_CASE(12) SVAE_CASE(13)
-    SVAE_CASE(14) SVAE_CASE(15)
-#endif
-#undef SVAE_CASE
-#undef SVAE_CASE_
-  }
-  return -3;
+  if (twoend && !keep && n <= svae::TE_MAX_N && T >= svae::TE_MIN_T)
+    return unit->twoend(a, inhomog, twoend == 1 && !inhomog, sel.layout, stream);
+  return split ? unit->estep_split(a, inhomog, stream) : unit->estep(a, inhomog, stream);
 }
 
 int svae_lds_filter_f64(int B, int T, int n, int inhomog, int pair_batched, unsigned options,
@@ -301,10 +261,10 @@ int svae_lds_filter_f64(int B, int T, int n, int inhomog, int pair_batched, unsi
   if (T < 1) return -2;
   if (n < 1 || n > SVAE_LDS_MAX_N) return -3;
   if (pair_batched && !inhomog) return -5;
-  if (!init_J) return -6;
-  if (!init_h) return -7;
-  if (!init_logZ) return -8;
-  if (T > 1 && (!J11 || !J12 || !J22 || !logZ_pair)) return -9;
+  svae::LdsArgs a{};
+  svae::set_estep_args(a, B, T, n, pair_batched, init_J, init_h, init_logZ, J11, J12, J22, logZ_pair, node_J, node_h, node_logZ,
+                       lognorm, nullptr, nullptr, nullptr, nullptr, info, workspace);
+  if (const int rc = svae::check_model(a)) return rc;
   if (!node_J) return -13;
   if (!node_h) return -14;
   if (!lognorm) return -16;
@@ -314,40 +274,16 @@ int svae_lds_filter_f64(int B, int T, int n, int inhomog, int pair_batched, unsi
   if (!decode_options(options, B, &sel)) return -24;
   if (B == 0) return 0;
   const int twoend = sel.twoend;
-  svae::LdsArgs a;
-  a.B = B; a.T = T;
-  a.init_J = init_J; a.init_h = init_h; a.init_logZ = init_logZ;
-  a.J11 = J11; a.J12 = J12; a.J22 = J22; a.logZ_pair = logZ_pair;
-  a.node_J = node_J; a.node_h = node_h; a.node_logZ = node_logZ;
-  a.lognorm = lognorm; a.E_init = nullptr; a.E_pair = nullptr;
-  a.E_node_diagxx = nullptr; a.E_node_x = nullptr;
-  a.info = info; a.ws = (double*)workspace;
-  a.ws2 = (double*)workspace + main_ws_doubles(B, T, n);      // factor region: the sampler may follow
-  a.ws3 = nullptr;
-  a.pair_seq_stride = pair_batched ? (long)(T - 1) * n * n : 0;
+  a.ws2 = kept_regions(workspace, B, T, n, 1).factor;         // factor region: the sampler may follow
   a.msg_Jp = J_pred; a.msg_hp = h_pred; a.msg_Jf = J_filt; a.msg_hf = h_filt;
-  a.mix_w = nullptr; a.mix_out = nullptr; a.seq_index = nullptr; a.mix_K = 0; a.lds_keep = 0; a.tile_half = 0; a.sig_out = nullptr;
   // small batches without message outputs: one sequence per wavefront (0.62 -> 0.24 ms at B = 512, T = 200, n = 10).
   // The one-register filter (n <= 10) stays ahead of the packed kernel until ~3 wavefronts per SIMD (filter + sampler,
   // T = 500: 1024 sequences 0.86 vs 1.81 ms, 2048: 1.85 vs 2.53; T = 200, 4096: 1.43 vs 1.27)
   const bool wide = sel.layout == 1 || (sel.layout == 0 && B <= (n <= svae::TE_MAX_N && twoend ? SVAE_FILTER_WIDE_MAX_B : 1023));
   const bool fsplit = wide && !J_pred && !h_pred && !J_filt && !h_filt;
-  switch (n) {
-#define SVAE_CASE_(NN) case NN: return !fsplit ? svae_lds_launch_filter_n##NN(&a, inhomog, stream)          \
-                                       : (NN <= svae::TE_MAX_N && twoend) ? svae_lds_launch_filter_1r_n##NN(&a, inhomog, stream) \
-                                       : svae_lds_launch_filter_split_n##NN(&a, inhomog, stream);
-#define SVAE_CASE(NN) SVAE_CASE_(NN)
-#ifdef SVAE_ONLY_N
-    SVAE_CASE(SVAE_ONLY_N)
-#else
-    SVAE_CASE(1) SVAE_CASE(2) SVAE_CASE(3) SVAE_CASE(4) SVAE_CASE(5) SVAE_CASE(6) SVAE_CASE(7)
-    SVAE_CASE(8) SVAE_CASE(9) SVAE_CASE(10) SVAE_CASE(11) SVAE_CASE(12) SVAE_CASE(13)
-    SVAE_CASE(14) SVAE_CASE(15)
-#endif
-#undef SVAE_CASE
-#undef SVAE_CASE_
-  }
-  return -3;
+  const svae::EstepUnit* unit = estep_units[n];
+  if (!fsplit) return unit->filter(a, inhomog, stream);
+  return (n <= svae::TE_MAX_N && twoend) ? unit->filter_1r(a, inhomog, stream) : unit->filter_split(a, inhomog, stream);
 }
 
 size_t svae_slds_lds_meanfield_workspace_bytes(int rows, int T, int n) {
@@ -396,63 +332,36 @@ int svae_slds_lds_meanfield_f64(int B, int rows, int T, int n, int K,
   if ((options & SVAE_OPT_LAYOUT_PACKED) && !rpc_ok) return -24;
   const bool rpc = rpc_ok && !(options & SVAE_OPT_LAYOUT_SPLIT);
   if (B == 0) return 0;
-  svae::LdsArgs a;
-  a.B = B; a.T = T;
-  a.init_J = init_J; a.init_h = init_h; a.init_logZ = nullptr;
-  a.J11 = J11; a.J12 = J12; a.J22 = J22; a.logZ_pair = nullptr;
-  a.node_J = node_J; a.node_h = node_h; a.node_logZ = node_logZ;
-  a.lognorm = lognorm; a.E_init = E_init; a.E_pair = nullptr;
-  a.E_node_diagxx = E_node_diagxx; a.E_node_x = E_node_x;
-  a.info = info; a.ws = (double*)workspace; a.ws2 = nullptr; a.ws3 = nullptr;
-  a.pair_seq_stride = 0;
-  a.msg_Jp = a.msg_hp = a.msg_Jf = a.msg_hf = nullptr;
-  a.mix_w = weights; a.mix_out = pair_contr; a.seq_index = seq_index; a.mix_K = K; a.lds_keep = 0; a.tile_half = 0; a.sig_out = nullptr;
-  switch (n) {
-#define SVAE_CASE_(NN) case NN: return rpc ? svae_lds_launch_slds_rpc_n##NN(&a, (options & SVAE_OPT_PRODUCERS_OFF) ? 1 : 0, \
-                                                                              (options & SVAE_OPT_LAYOUT_PACKED) ? 0 : 1, stream) \
-                                        : svae_lds_launch_twoend_mix_n##NN(&a, stream);
-#define SVAE_CASE(NN) SVAE_CASE_(NN)
-#ifdef SVAE_ONLY_N
-    SVAE_CASE(SVAE_ONLY_N)
-#else
-    SVAE_CASE(1) SVAE_CASE(2) SVAE_CASE(3) SVAE_CASE(4) SVAE_CASE(5) SVAE_CASE(6) SVAE_CASE(7)
-    SVAE_CASE(8) SVAE_CASE(9) SVAE_CASE(10)
-#endif
-#undef SVAE_CASE
-#undef SVAE_CASE_
-  }
-  return -3;
+  svae::LdsArgs a{};
+  svae::set_estep_args(a, B, T, n, 0, init_J, init_h, nullptr, J11, J12, J22, nullptr, node_J, node_h, node_logZ,
+                       lognorm, E_init, nullptr, E_node_diagxx, E_node_x, info, workspace);
+  a.mix_w = weights; a.mix_out = pair_contr; a.seq_index = seq_index; a.mix_K = K;
+  const svae::EstepUnit* unit = estep_units[n];
+  return rpc ? unit->slds_rpc(a, (options & SVAE_OPT_PRODUCERS_OFF) ? 1 : 0, (options & SVAE_OPT_LAYOUT_PACKED) ? 0 : 1, stream)
+             : unit->twoend_mix(a, stream);
 }
 
 int svae_lds_reduce_stats_f64(int B, int n, const double* E_init, const double* E_pair,
                               const double* lognorm, double* out, void* stream) {
-  if (B < 0) return -1;
-  if (n < 1 || n > SVAE_LDS_TILE_MAX_N) return -2;
-  if (!E_init) return -3;
-  if (!E_pair) return -4;
-  if (!lognorm) return -5;
-  if (!out) return -6;
-  const int tot = 4 * n * n + n + 1;
-  hipLaunchKernelGGL(svae::lds_reduce_stats_kernel, dim3((tot + 7) / 8), dim3(256), 0,
-                     (hipStream_t)stream, B, n, E_init, E_pair, lognorm, out);
-  return hipGetLastError() == hipSuccess ? 0 : -1000;
+  return reduce_stats(B, n, 1, SVAE_LDS_TILE_MAX_N, E_init, E_pair, lognorm, out, stream);
 }
 
 int svae_lds_xl_reduce_stats_f64(int B, int n, const double* E_init, const double* E_pair,
                                  const double* lognorm, double* out, void* stream) {
-  if (B < 0) return -1;
-  if (n <= SVAE_LDS_TILE_MAX_N || n > SVAE_LDS_XL_MAX_N) return -2;
-  if (!E_init) return -3;
-  if (!E_pair) return -4;
-  if (!lognorm) return -5;
-  if (!out) return -6;
-  const int tot = 4 * n * n + n + 1;
-  hipLaunchKernelGGL(svae::lds_reduce_stats_kernel, dim3((tot + 7) / 8), dim3(256), 0,
-                     (hipStream_t)stream, B, n, E_init, E_pair, lognorm, out);
-  return hipGetLastError() == hipSuccess ? 0 : -1000;
+  return reduce_stats(B, n, SVAE_LDS_TILE_MAX_N + 1, SVAE_LDS_XL_MAX_N, E_init, E_pair, lognorm, out, stream);
 }
 
 }  // extern "C"
+
+static svae::SampleArgs sample_args(int B, int T, int n, int S, int prod_max_b, const double* eps, double* samples,
+                                    const void* workspace) {
+  svae::SampleArgs a{};
+  a.B = B; a.T = T; a.S = S; a.eps = eps; a.samples = samples;
+  a.prod_max_b = prod_max_b;
+  a.ws = (const double*)workspace;
+  a.ws2 = kept_regions(workspace, B, T, n, 1).factor;
+  return a;
+}
 
 extern "C" int svae_lds_sample_f64(int B, int T, int n, int S, unsigned options, const double* eps, double* samples,
                                    const void* workspace, size_t ws_bytes, void* stream) {
@@ -466,25 +375,7 @@ extern "C" int svae_lds_sample_f64(int B, int T, int n, int S, unsigned options,
   Selection sel;
   if (!decode_options(options, B, &sel)) return -24;
   if (B == 0) return 0;
-  svae::SampleArgs a;
-  a.B = B; a.T = T; a.S = S; a.eps = eps; a.samples = samples;
-  a.prod_max_b = sel.prod_max_b;
-  a.ws = (const double*)workspace;
-  a.ws2 = (const double*)workspace + main_ws_doubles(B, T, n);
-  switch (n) {
-#define SVAE_CASE_(NN) case NN: return svae_lds_sample_n##NN(&a, stream);
-#define SVAE_CASE(NN) SVAE_CASE_(NN)
-#ifdef SVAE_ONLY_N
-    SVAE_CASE(SVAE_ONLY_N)
-#else
-    SVAE_CASE(1) SVAE_CASE(2) SVAE_CASE(3) SVAE_CASE(4) SVAE_CASE(5) SVAE_CASE(6) SVAE_CASE(7)
-    SVAE_CASE(8) SVAE_CASE(9) SVAE_CASE(10) SVAE_CASE(11) SVAE_CASE(12) SVAE_CASE(13)
-    SVAE_CASE(14) SVAE_CASE(15)
-#endif
-#undef SVAE_CASE
-#undef SVAE_CASE_
-  }
-  return -3;
+  return estep_units[n]->sample(sample_args(B, T, n, S, sel.prod_max_b, eps, samples, workspace), stream);
 }
 
 extern "C" int svae_lds_inference_f64(int B, int T, int n, int S, int inhomog, int pair_batched, int keep_vjp, unsigned options,
@@ -508,58 +399,42 @@ extern "C" int svae_lds_inference_f64(int B, int T, int n, int S, int inhomog, i
     return rs == 0 ? 0 : -100 + rs;
   }
   if (B < 0) return -1;
-  if (!init_J) return -6;
-  if (!init_h) return -7;
-  if (!init_logZ) return -8;
-  if (!J11 || !J12 || !J22 || !logZ_pair) return -9;
+  svae::LdsArgs a{};
+  svae::set_estep_args(a, B, T, n, pair_batched, init_J, init_h, init_logZ, J11, J12, J22, logZ_pair, node_J, node_h, node_logZ,
+                       lognorm, E_init, E_pair, E_node_diagxx, E_node_x, info, workspace);    // lean records at the start of the main region
+  if (const int rc = svae::check_model(a)) return rc;       // (T >= 2 here: lean_applies)
   if (pair_batched && !inhomog) return -5;
-  if (!node_J) return -13;
-  if (!node_h) return -14;
-  if (!lognorm) return -16;
-  if (!E_init) return -17;
-  if (!E_pair) return -18;
-  if (!E_node_diagxx) return -19;
-  if (!E_node_x) return -20;
-  if (!info) return -21;
+  if (const int rc = svae::check_arrays(a)) return rc;
   if (!workspace || ws_bytes < svae_lds_workspace_bytes(B, T, n)) return -22;
   Selection sel;
   if (!decode_options(options, B, &sel)) return -24;
   if (B == 0) return 0;
-  svae::LdsArgs a;
-  a.tile_half = 0;
-  a.B = B; a.T = T;
-  a.init_J = init_J; a.init_h = init_h; a.init_logZ = init_logZ;
-  a.J11 = J11; a.J12 = J12; a.J22 = J22; a.logZ_pair = logZ_pair;
-  a.node_J = node_J; a.node_h = node_h; a.node_logZ = node_logZ;
-  a.lognorm = lognorm; a.E_init = E_init; a.E_pair = E_pair;
-  a.E_node_diagxx = E_node_diagxx; a.E_node_x = E_node_x;
-  a.info = info; a.ws = (double*)workspace;        // lean records at the start of the main region
-  a.ws2 = nullptr;
-  a.ws3 = keep_vjp ? (double*)workspace + main_ws_doubles(B, T, n) + factor_ws_doubles(B, T, n) : nullptr;   // cross moments: where the VJP looks
-  a.pair_seq_stride = pair_batched ? (long)(T - 1) * n * n : 0;
-  a.msg_Jp = a.msg_hp = a.msg_Jf = a.msg_hf = nullptr;
-  a.mix_w = nullptr; a.mix_out = nullptr; a.seq_index = nullptr; a.mix_K = 0; a.lds_keep = 0;
-  a.sig_out = nullptr;
+  a.ws3 = kept_regions(workspace, B, T, n, keep_vjp ? 2 : 0).cross;   // cross moments: where the VJP looks
   svae::LeanSample ls;
   ls.S = S; ls.eps = eps; ls.samples = samples;
-  switch (n) {
-#define SVAE_CASE_(NN) case NN: return svae_lds_infer_lean_n##NN(&a, &ls, inhomog, stream);
-#define SVAE_CASE(NN) SVAE_CASE_(NN)
-#ifdef SVAE_ONLY_N
-    SVAE_CASE(SVAE_ONLY_N)
-#else
-    SVAE_CASE(1) SVAE_CASE(2) SVAE_CASE(3) SVAE_CASE(4) SVAE_CASE(5) SVAE_CASE(6) SVAE_CASE(7)
-    SVAE_CASE(8) SVAE_CASE(9) SVAE_CASE(10)
-#endif
-#undef SVAE_CASE
-#undef SVAE_CASE_
-  }
-  return -3;
+  return estep_units[n]->infer_lean(a, ls, inhomog, stream);
 }
 
 extern "C" size_t svae_lds_vjp_workspace_bytes(int B, int T, int n) {
   if (B <= 0 || T <= 0 || n <= 0 || n > SVAE_LDS_MAX_N) return 0;
   return (size_t)B * T * svae::vjp_step_doubles(n) * sizeof(double);
+}
+
+// what every VJP launch carries; the caller adds J12 and its strides and the cotangents of the E_init / E_pair / parameters
+static svae::VjpArgs vjp_args(int B, int T, int n, int S, int prod_max_b, const double* g_lognorm,
+                              const double* g_E_node_diagxx, const double* g_E_node_x, const double* g_samples,
+                              const double* eps, const double* samples, double* g_node_J, double* g_node_h,
+                              const void* workspace, void* vjp_workspace) {
+  svae::VjpArgs a{};
+  a.B = B; a.T = T; a.S = g_samples ? S : 0;
+  a.prod_max_b = prod_max_b;
+  a.g_lognorm = g_lognorm; a.g_diagxx = g_E_node_diagxx; a.g_x = g_E_node_x;
+  a.g_samples = g_samples; a.eps = eps; a.samples = samples;
+  a.g_node_J = g_node_J; a.g_node_h = g_node_h;
+  const Kept kept = kept_regions(workspace, B, T, n, 3);
+  a.ws = (const double*)workspace; a.ws2 = kept.factor; a.ws3 = kept.cross;
+  a.adj = (double*)vjp_workspace;
+  return a;
 }
 
 static int vjp_impl(int B, int T, int n, int S, int inhomog, int pair_batched, unsigned options,
@@ -587,52 +462,20 @@ static int vjp_impl(int B, int T, int n, int S, int inhomog, int pair_batched, u
   Selection sel;
   if (!decode_options(options, B, &sel)) return -24;
   if (B == 0) return 0;
-  svae::VjpArgs a;
-  a.B = B; a.T = T; a.S = g_samples ? S : 0;
-  a.prod_max_b = sel.prod_max_b;
-  a.J12 = J12; a.g_lognorm = g_lognorm; a.g_diagxx = g_E_node_diagxx; a.g_x = g_E_node_x;
+  svae::VjpArgs a = vjp_args(B, T, n, S, sel.prod_max_b, g_lognorm, g_E_node_diagxx, g_E_node_x, g_samples, eps, samples,
+                             g_node_J, g_node_h, workspace, vjp_workspace);
+  a.J12 = J12;
   a.pair_t_stride = inhomog ? (long)n * n : 0;
   a.pair_seq_stride = pair_batched ? (long)(T - 1) * n * n : 0;
   a.g_E_init = g_E_init; a.g_E_pair = g_E_pair; a.E_pair = E_pair; a.E_node_x = E_node_x;
-  a.g_samples = g_samples; a.eps = eps; a.samples = samples;
-  a.g_node_J = g_node_J; a.g_node_h = g_node_h;
-  a.ws = (const double*)workspace;
-  a.ws2 = a.ws + main_ws_doubles(B, T, n);
-  a.ws3 = a.ws2 + factor_ws_doubles(B, T, n);
-  a.adj = (double*)vjp_workspace;
   a.g_P = g_node_J_dense;
-  a.g_R = g_R; a.pg_only = 0;
+  a.g_R = g_R;
   if (g_node_J_dense && !g_R) a.prod_max_b = 0;  /* the packed sweeps write it (with g_R: launch_vjp adds the packed sweep 2 where the selection is another) */
   if ((options & SVAE_OPT_INFER_RECORDS) && lean_applies(B, T, n, S, inhomog, 1, options)) {
     if (g_E_init || g_E_pair || g_node_J_dense) return -8;        /* lean records: cotangents of the node statistics, lognorm and samples */
-    switch (n) {
-#define SVAE_CASE_(NN) case NN: return svae_lds_vjp_lean_n##NN(&a, stream);
-#define SVAE_CASE(NN) SVAE_CASE_(NN)
-#ifdef SVAE_ONLY_N
-      SVAE_CASE(SVAE_ONLY_N)
-#else
-      SVAE_CASE(1) SVAE_CASE(2) SVAE_CASE(3) SVAE_CASE(4) SVAE_CASE(5) SVAE_CASE(6) SVAE_CASE(7)
-      SVAE_CASE(8) SVAE_CASE(9) SVAE_CASE(10)
-#endif
-#undef SVAE_CASE
-#undef SVAE_CASE_
-    }
-    return -3;
+    return vjp_units[n]->vjp_lean(a, stream);
   }
-  switch (n) {
-#define SVAE_CASE_(NN) case NN: return svae_lds_vjp_n##NN(&a, stream);
-#define SVAE_CASE(NN) SVAE_CASE_(NN)
-#ifdef SVAE_ONLY_N
-    SVAE_CASE(SVAE_ONLY_N)
-#else
-    SVAE_CASE(1) SVAE_CASE(2) SVAE_CASE(3) SVAE_CASE(4) SVAE_CASE(5) SVAE_CASE(6) SVAE_CASE(7)
-    SVAE_CASE(8) SVAE_CASE(9) SVAE_CASE(10) SVAE_CASE(11) SVAE_CASE(12) SVAE_CASE(13)
-    SVAE_CASE(14) SVAE_CASE(15)
-#endif
-#undef SVAE_CASE
-#undef SVAE_CASE_
-  }
-  return -3;
+  return vjp_units[n]->vjp(a, stream);
 }
 
 extern "C" int svae_lds_estep_vjp_ex_f64(int B, int T, int n, int S, int inhomog, int pair_batched, unsigned options,
@@ -711,11 +554,10 @@ extern "C" int svae_lds_estep_vjp_f64(int B, int T, int n, int S, const double* 
                                       double* g_node_J, double* g_node_h,
                                       const void* workspace, size_t ws_bytes,
                                       void* vjp_workspace, size_t vjp_ws_bytes, void* stream) {
-  const int rc = svae_lds_estep_vjp_ex_f64(B, T, n, S, 0, 0, SVAE_OPT_DEFAULT, J12, g_lognorm, g_E_node_diagxx, g_E_node_x,
-                                           nullptr, nullptr, g_samples, eps, samples, nullptr, nullptr,
-                                           g_node_J, g_node_h, workspace, ws_bytes, vjp_workspace,
-                                           vjp_ws_bytes, stream);
-  return rc == -12 ? -12 : rc;
+  return svae_lds_estep_vjp_ex_f64(B, T, n, S, 0, 0, SVAE_OPT_DEFAULT, J12, g_lognorm, g_E_node_diagxx, g_E_node_x,
+                                   nullptr, nullptr, g_samples, eps, samples, nullptr, nullptr,
+                                   g_node_J, g_node_h, workspace, ws_bytes, vjp_workspace,
+                                   vjp_ws_bytes, stream);
 }
 
 // ---- per-sequence lengths (svae_lds_ragged_*) ----------------------------------------------------------------------
@@ -781,16 +623,6 @@ extern "C" size_t svae_lds_ragged_perstep_workspace_bytes(int B, int T, int n) {
   return ragged_table_offset_bytes(B, T, n) + (size_t)2 * n * n * sizeof(double);
 }
 
-#define SVAE_RAGGED_SWITCH(FN, ...)                                                                      \
-  switch (n) {                                                                                           \
-    case 1: return FN##1(__VA_ARGS__);   case 2: return FN##2(__VA_ARGS__);   case 3: return FN##3(__VA_ARGS__);    \
-    case 4: return FN##4(__VA_ARGS__);   case 5: return FN##5(__VA_ARGS__);   case 6: return FN##6(__VA_ARGS__);    \
-    case 7: return FN##7(__VA_ARGS__);   case 8: return FN##8(__VA_ARGS__);   case 9: return FN##9(__VA_ARGS__);    \
-    case 10: return FN##10(__VA_ARGS__); case 11: return FN##11(__VA_ARGS__); case 12: return FN##12(__VA_ARGS__);  \
-    case 13: return FN##13(__VA_ARGS__); case 14: return FN##14(__VA_ARGS__); case 15: return FN##15(__VA_ARGS__);  \
-  }
-
-#ifndef SVAE_ONLY_N
 extern "C" int svae_lds_ragged_estep_f64(int B, int T, int n, int inhomog, int pair_batched, int keep, unsigned options,
                                          const double* init_J, const double* init_h, const double* init_logZ,
                                          const double* J11, const double* J12, const double* J22, const double* logZ_pair,
@@ -805,18 +637,11 @@ extern "C" int svae_lds_ragged_estep_f64(int B, int T, int n, int inhomog, int p
   if (inhomog || pair_batched) return -32;       /* pair parameters shared by the batch and by the steps */
   if (!lengths) return -31;
   if ((keep & ~3) != 0) return -23;
-  if (!init_J) return -6;
-  if (!init_h) return -7;
-  if (!init_logZ) return -8;
-  if (T > 1 && (!J11 || !J12 || !J22 || !logZ_pair)) return -9;
-  if (!node_J) return -13;
-  if (!node_h) return -14;
-  if (!lognorm) return -16;
-  if (!E_init) return -17;
-  if (!E_pair) return -18;
-  if (!E_node_diagxx) return -19;
-  if (!E_node_x) return -20;
-  if (!info) return -21;
+  svae::LdsArgs a{};
+  svae::set_estep_args(a, B, T, n, 0, init_J, init_h, init_logZ, J11, J12, J22, logZ_pair, node_J, node_h, node_logZ,
+                       lognorm, E_init, E_pair, E_node_diagxx, E_node_x, info, workspace);
+  if (const int rc = svae::check_model(a)) return rc;
+  if (const int rc = svae::check_arrays(a)) return rc;
   Selection sel;
   if (!decode_options(options, B, &sel)) return -24;      /* (a valid word; the ragged dispatcher has one route) */
   if (B == 0) return 0;
@@ -825,33 +650,16 @@ extern "C" int svae_lds_ragged_estep_f64(int B, int T, int n, int inhomog, int p
   hipLaunchKernelGGL(svae::lds_ragged_tables_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, n, J11, J12, J22, tab);
   if (hipGetLastError() != hipSuccess) return -1000;
   const long nn = (long)n * n;
-  svae::LdsArgs a;
-  a.tile_half = 0;
-  a.B = B; a.T = T;
-  a.init_J = init_J; a.init_h = init_h; a.init_logZ = init_logZ;
-  a.J11 = tab; a.J12 = tab + 2 * nn; a.J22 = tab + 4 * nn; a.logZ_pair = logZ_pair;
-  a.node_J = node_J; a.node_h = node_h; a.node_logZ = node_logZ;
-  a.lognorm = lognorm; a.E_init = E_init; a.E_pair = E_pair;
-  a.E_node_diagxx = E_node_diagxx; a.E_node_x = E_node_x;
-  a.info = info; a.ws = (double*)workspace;
-  a.ws2 = (keep & 1) ? (double*)workspace + main_ws_doubles(B, T, n) : nullptr;
-  a.ws3 = (keep & 2) ? (double*)workspace + main_ws_doubles(B, T, n) + factor_ws_doubles(B, T, n) : nullptr;
-  a.pair_seq_stride = 0;
-  a.msg_Jp = a.msg_hp = a.msg_Jf = a.msg_hf = nullptr;
-  a.mix_w = nullptr; a.mix_out = nullptr; a.seq_index = nullptr; a.mix_K = 0; a.lds_keep = 0;
-  a.sig_out = nullptr;
+  a.J11 = tab; a.J12 = tab + 2 * nn; a.J22 = tab + 4 * nn;
+  const Kept kept = kept_regions(workspace, B, T, n, keep);
+  a.ws2 = kept.factor; a.ws3 = kept.cross;
   a.lengths = lengths;
-  SVAE_RAGGED_SWITCH(svae_lds_launch_ragged_n, &a, stream)
-  return -3;
+  return estep_units[n]->ragged(a, stream);
 }
 
 // per-step pair parameters (T-1,n,n) or, pair_batched, (B,T-1,n,n), and an init potential per batch or, init_batched, per
 // sequence: the packed E-step in its INHOMOG + RAG instantiation; the decoupling set's blocks come from a table behind the
 // uniform workspace layout
-static size_t perstep_workspace_bytes(int B, int T, int n) {
-  return ragged_table_offset_bytes(B, T, n) + (size_t)2 * n * n * sizeof(double);
-}
-
 extern "C" int svae_lds_ragged_perstep_estep_f64(int B, int T, int n, int pair_batched, int init_batched, int keep,
                                                  unsigned options,
                                                  const double* init_J, const double* init_h, const double* init_logZ,
@@ -867,58 +675,32 @@ extern "C" int svae_lds_ragged_perstep_estep_f64(int B, int T, int n, int pair_b
   if ((pair_batched & ~1) != 0 || (init_batched & ~1) != 0) return -32;
   if (!lengths) return -31;
   if ((keep & ~1) != 0) return -23;               /* bit 1, the cross moments of the VJP: no sweeps for this route */
-  if (!init_J) return -6;
-  if (!init_h) return -7;
-  if (!init_logZ) return -8;
-  if (T > 1 && (!J11 || !J12 || !J22 || !logZ_pair)) return -9;
-  if (!node_J) return -13;
-  if (!node_h) return -14;
-  if (!lognorm) return -16;
-  if (!E_init) return -17;
-  if (T > 1 && !E_pair) return -18;               /* (B,T-1,3,n,n): empty for T = 1 */
-  if (!E_node_diagxx) return -19;
-  if (!E_node_x) return -20;
-  if (!info) return -21;
+  svae::LdsPerstepArgs a{};
+  svae::set_estep_args(a, B, T, n, pair_batched, init_J, init_h, init_logZ, J11, J12, J22, logZ_pair, node_J, node_h, node_logZ,
+                       lognorm, E_init, E_pair, E_node_diagxx, E_node_x, info, workspace);
+  if (const int rc = svae::check_model(a)) return rc;
+  if (const int rc = svae::check_arrays(a, T > 1)) return rc;       /* E_pair (B,T-1,3,n,n): empty for T = 1 */
   Selection sel;
   if (!decode_options(options, B, &sel)) return -24;      /* (a valid word; one route) */
   if (B == 0) return 0;
-  if (!workspace || ws_bytes < perstep_workspace_bytes(B, T, n)) return -22;
+  if (!workspace || ws_bytes < svae_lds_ragged_perstep_workspace_bytes(B, T, n)) return -22;
   double* qtab = (double*)((char*)workspace + ragged_table_offset_bytes(B, T, n));
   hipLaunchKernelGGL(svae::lds_ragged_qtable_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, n, qtab);
   if (hipGetLastError() != hipSuccess) return -1000;
-  svae::LdsPerstepArgs a;
-  a.tile_half = 0;
-  a.B = B; a.T = T;
-  a.init_J = init_J; a.init_h = init_h; a.init_logZ = init_logZ;
   /* T = 1: no pair is ever addressed (pair 0 <= L-2 needs L >= 2 > T); the table stands in for the NULL arrays */
-  a.J11 = T > 1 ? J11 : qtab; a.J12 = T > 1 ? J12 : qtab; a.J22 = T > 1 ? J22 : qtab; a.logZ_pair = logZ_pair;
-  a.node_J = node_J; a.node_h = node_h; a.node_logZ = node_logZ;
-  a.lognorm = lognorm; a.E_init = E_init; a.E_pair = E_pair;
-  a.E_node_diagxx = E_node_diagxx; a.E_node_x = E_node_x;
-  a.info = info; a.ws = (double*)workspace;
-  a.ws2 = (keep & 1) ? (double*)workspace + main_ws_doubles(B, T, n) : nullptr;
-  a.ws3 = nullptr;
-  a.pair_seq_stride = (pair_batched && T > 1) ? (long)(T - 1) * n * n : 0;
-  a.msg_Jp = a.msg_hp = a.msg_Jf = a.msg_hf = nullptr;
-  a.mix_w = nullptr; a.mix_out = nullptr; a.seq_index = nullptr; a.mix_K = 0; a.lds_keep = 0;
-  a.sig_out = nullptr;
+  if (T == 1) a.J11 = a.J12 = a.J22 = qtab;
+  a.ws2 = kept_regions(workspace, B, T, n, keep).factor;
   a.lengths = lengths;
   a.qtab = qtab;
   a.init_batched = init_batched;
-  SVAE_RAGGED_SWITCH(svae_lds_launch_ragged_perstep_n, &a, stream)
-  return -3;
+  return estep_units[n]->ragged_perstep(a, stream);
 }
 
 static int ragged_sample(int B, int T, int n, int S, const double* eps, double* samples, const int32_t* lengths,
                          const void* workspace, void* stream) {
-  svae::SampleArgs a;
-  a.B = B; a.T = T; a.S = S; a.eps = eps; a.samples = samples;
-  a.prod_max_b = 0;
-  a.ws = (const double*)workspace;
-  a.ws2 = (const double*)workspace + main_ws_doubles(B, T, n);
+  svae::SampleArgs a = sample_args(B, T, n, S, 0, eps, samples, workspace);
   a.lengths = lengths;
-  SVAE_RAGGED_SWITCH(svae_lds_sample_ragged_n, &a, stream)
-  return -3;
+  return estep_units[n]->sample_ragged(a, stream);
 }
 
 extern "C" int svae_lds_ragged_inference_f64(int B, int T, int n, int S, int inhomog, int pair_batched, int keep_vjp,
@@ -982,26 +764,12 @@ extern "C" int svae_lds_ragged_vjp_f64(int B, int T, int n, int S, int inhomog, 
   if (!workspace || ws_bytes < svae_lds_ragged_workspace_bytes(B, T, n)) return -14;
   if (!vjp_workspace || vjp_ws_bytes < svae_lds_vjp_workspace_bytes(B, T, n)) return -16;
   const long nn = (long)n * n;
-  svae::VjpArgs a;
-  a.B = B; a.T = T; a.S = g_samples ? S : 0;
-  a.prod_max_b = 0;
+  svae::VjpArgs a = vjp_args(B, T, n, S, 0, g_lognorm, g_E_node_diagxx, g_E_node_x, g_samples, eps, samples, g_node_J, g_node_h,
+                             workspace, vjp_workspace);
   a.J12 = (const double*)((const char*)workspace + ragged_table_offset_bytes(B, T, n)) + 2 * nn;   /* [real | 0], left by the forward pass */
-  a.g_lognorm = g_lognorm; a.g_diagxx = g_E_node_diagxx; a.g_x = g_E_node_x;
-  a.pair_t_stride = 0; a.pair_seq_stride = 0;
-  a.g_E_init = nullptr; a.g_E_pair = nullptr; a.E_pair = nullptr; a.E_node_x = nullptr;
-  a.g_samples = g_samples; a.eps = eps; a.samples = samples;
-  a.g_node_J = g_node_J; a.g_node_h = g_node_h;
-  a.ws = (const double*)workspace;
-  a.ws2 = a.ws + main_ws_doubles(B, T, n);
-  a.ws3 = a.ws2 + factor_ws_doubles(B, T, n);
-  a.adj = (double*)vjp_workspace;
-  a.g_P = nullptr; a.g_R = nullptr; a.pg_only = 0;
   a.lengths = lengths;
-  SVAE_RAGGED_SWITCH(svae_lds_vjp_ragged_n, &a, stream)
-  return -3;
+  return vjp_units[n]->vjp_ragged(a, stream);
 }
-#endif  /* !SVAE_ONLY_N */
-#undef SVAE_RAGGED_SWITCH
 
 // [sum E_init | sum E_pair | sum lognorm | B | sum_b (lengths[b] - 1)]: the uniform layout with one more slot, the number
 // of pairs behind the E_pair sums (what the uniform consumers derive as count (T-1))
@@ -1015,10 +783,8 @@ extern "C" int svae_lds_ragged_reduce_stats_f64(int B, int T, int n, const doubl
   if (!lognorm) return -5;
   if (!lengths) return -31;
   if (!out) return -6;
-  const int tot = 4 * n * n + n + 1;
-  hipLaunchKernelGGL(svae::lds_reduce_stats_kernel, dim3((tot + 7) / 8), dim3(256), 0,
-                     (hipStream_t)stream, B, n, E_init, E_pair, lognorm, out);
+  launch_reduce_stats(B, n, E_init, E_pair, lognorm, out, stream);
   hipLaunchKernelGGL(svae::lds_ragged_pair_count_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, B, T, lengths,
-                     out + tot + 1);
+                     out + 4 * n * n + n + 2);
   return hipGetLastError() == hipSuccess ? 0 : -1000;
 }

@@ -12,6 +12,7 @@
 #include "lds_estep_twoend_rpcmix.hpp"
 #include "lds_filter_1r.hpp"
 #include "lds_lean_estep.hpp"
+#include "lds_units.hpp"
 
 #ifndef SVAE_N
 #error "compile with -DSVAE_N=<latent dim>"
@@ -19,69 +20,66 @@
 #define SVAE_CAT_(a, b) a##b
 #define SVAE_CAT(a, b) SVAE_CAT_(a, b)
 
-extern "C" int SVAE_CAT(svae_lds_launch_n, SVAE_N)(const svae::LdsArgs* a, int inhomog, void* stream) {
-  return svae::launch_estep<SVAE_N>(*a, inhomog != 0, (hipStream_t)stream);
+// The table's entries (lds_units.hpp says what each one is): file-local, reached only through svae_lds_estep_unit_n<N>.
+static int estep(const svae::LdsArgs& a, int inhomog, void* stream) {
+  return svae::launch_estep<SVAE_N>(a, inhomog != 0, (hipStream_t)stream);
 }
 
-extern "C" int SVAE_CAT(svae_lds_sample_n, SVAE_N)(const svae::SampleArgs* a, void* stream) {
-  return svae::launch_sample<SVAE_N>(*a, (hipStream_t)stream);
+static int sample(const svae::SampleArgs& a, void* stream) { return svae::launch_sample<SVAE_N>(a, (hipStream_t)stream); }
+
+static int estep_split(const svae::LdsArgs& a, int inhomog, void* stream) {
+  return svae::launch_estep_split<SVAE_N>(a, inhomog != 0, (hipStream_t)stream);
 }
 
-extern "C" int SVAE_CAT(svae_lds_launch_split_n, SVAE_N)(const svae::LdsArgs* a, int inhomog, void* stream) {
-  return svae::launch_estep_split<SVAE_N>(*a, inhomog != 0, (hipStream_t)stream);
+static int twoend(const svae::LdsArgs& a, int inhomog, int lean, int layout, void* stream) {
+  const bool rpc_ok = !inhomog && lean && !a.ws3 && a.T >= svae::TE_MIN_T;
+  if (rpc_ok && (layout == 2 || (layout == 0 && a.B >= svae::TE_RPC_MIN_B)))
+    return svae::launch_estep_twoend_rpc<SVAE_N>(a, (hipStream_t)stream);
+  return svae::launch_estep_twoend<SVAE_N>(a, inhomog != 0, lean != 0, (hipStream_t)stream);
 }
 
-// layout: 0 = by batch size (one sequence per wavefront below TE_RPC_MIN_B, two per wavefront from there), 1 = one sequence
-// per wavefront, 2 = two per wavefront (row-per-chain kernel; homogeneous lean launches without the cross-moment hand-off)
-extern "C" int SVAE_CAT(svae_lds_launch_twoend_n, SVAE_N)(const svae::LdsArgs* a, int inhomog, int lean, int layout,
-                                                          void* stream) {
-  const bool rpc_ok = !inhomog && lean && !a->ws3 && a->T >= svae::TE_MIN_T;
-  if (rpc_ok && (layout == 2 || (layout == 0 && a->B >= svae::TE_RPC_MIN_B)))
-    return svae::launch_estep_twoend_rpc<SVAE_N>(*a, (hipStream_t)stream);
-  return svae::launch_estep_twoend<SVAE_N>(*a, inhomog != 0, lean != 0, (hipStream_t)stream);
+static int twoend_mix(const svae::LdsArgs& a, void* stream) {
+  return svae::launch_estep_twoend_mix<SVAE_N>(a, (hipStream_t)stream);
 }
 
-extern "C" int SVAE_CAT(svae_lds_launch_twoend_mix_n, SVAE_N)(const svae::LdsArgs* a, void* stream) {
-  return svae::launch_estep_twoend_mix<SVAE_N>(*a, (hipStream_t)stream);
+static int slds_rpc(const svae::LdsArgs& a, int refprod, int seq_ok, void* stream) {
+  return svae::launch_slds_meanfield_rpc<SVAE_N>(a, refprod, seq_ok, (hipStream_t)stream);
 }
 
-// the SLDS mean-field step in the row-per-chain layout with producer wavefronts (refprod != 0: reference producers)
-extern "C" int SVAE_CAT(svae_lds_launch_slds_rpc_n, SVAE_N)(const svae::LdsArgs* a, int refprod, int seq_ok, void* stream) {
-  return svae::launch_slds_meanfield_rpc<SVAE_N>(*a, refprod, seq_ok, (hipStream_t)stream);
+static int filter(const svae::LdsArgs& a, int inhomog, void* stream) {
+  return svae::launch_filter<SVAE_N>(a, inhomog != 0, (hipStream_t)stream);
 }
 
-extern "C" int SVAE_CAT(svae_lds_launch_filter_n, SVAE_N)(const svae::LdsArgs* a, int inhomog, void* stream) {
-  return svae::launch_filter<SVAE_N>(*a, inhomog != 0, (hipStream_t)stream);
+static int filter_1r(const svae::LdsArgs& a, int inhomog, void* stream) {
+  return svae::launch_filter_1r<SVAE_N>(a, inhomog != 0, (hipStream_t)stream);
 }
 
-extern "C" int SVAE_CAT(svae_lds_launch_filter_1r_n, SVAE_N)(const svae::LdsArgs* a, int inhomog, void* stream) {
-  return svae::launch_filter_1r<SVAE_N>(*a, inhomog != 0, (hipStream_t)stream);
+static int forward_pair(const svae::LdsArgs& f, const svae::LdsArgs& e, int inhomog, void* stream) {
+  return svae::launch_forward_pair<SVAE_N>(f, e, inhomog != 0, (hipStream_t)stream);
 }
 
-extern "C" int SVAE_CAT(svae_lds_launch_forward_pair_n, SVAE_N)(const svae::LdsArgs* f, const svae::LdsArgs* e, int inhomog,
-                                                                void* stream) {
-  return svae::launch_forward_pair<SVAE_N>(*f, *e, inhomog != 0, (hipStream_t)stream);
+static int filter_split(const svae::LdsArgs& a, int inhomog, void* stream) {
+  return svae::launch_filter_split<SVAE_N>(a, inhomog != 0, (hipStream_t)stream);
 }
 
-extern "C" int SVAE_CAT(svae_lds_launch_filter_split_n, SVAE_N)(const svae::LdsArgs* a, int inhomog, void* stream) {
-  return svae::launch_filter_split<SVAE_N>(*a, inhomog != 0, (hipStream_t)stream);
+static int infer_lean(const svae::LdsArgs& a, const svae::LeanSample& ls, int inhomog, void* stream) {
+  return svae::launch_infer_lean<SVAE_N>(a, ls, inhomog != 0, (hipStream_t)stream);
 }
 
-// E-step + sampler in one launch on lean records (lds_lean_estep.hpp): homogeneous pair parameters, n <= LEAN_MAX_N
-extern "C" int SVAE_CAT(svae_lds_infer_lean_n, SVAE_N)(const svae::LdsArgs* a, const svae::LeanSample* ls, int inhomog, void* stream) {
-  return svae::launch_infer_lean<SVAE_N>(*a, *ls, inhomog != 0, (hipStream_t)stream);
+static int ragged(const svae::LdsArgs& a, void* stream) { return svae::launch_estep_ragged<SVAE_N>(a, (hipStream_t)stream); }
+
+static int sample_ragged(const svae::SampleArgs& a, void* stream) {
+  return svae::launch_sample_ragged<SVAE_N>(a, (hipStream_t)stream);
 }
 
-// per-sequence lengths (svae_lds_ragged_*): the packed E-step and samplers in their ragged instantiations
-extern "C" int SVAE_CAT(svae_lds_launch_ragged_n, SVAE_N)(const svae::LdsArgs* a, void* stream) {
-  return svae::launch_estep_ragged<SVAE_N>(*a, (hipStream_t)stream);
+static int ragged_perstep(const svae::LdsPerstepArgs& a, void* stream) {
+  return svae::launch_estep_ragged_perstep<SVAE_N>(a, (hipStream_t)stream);
 }
 
-extern "C" int SVAE_CAT(svae_lds_sample_ragged_n, SVAE_N)(const svae::SampleArgs* a, void* stream) {
-  return svae::launch_sample_ragged<SVAE_N>(*a, (hipStream_t)stream);
-}
-
-// ... with per-step pair parameters and an optional per-sequence init potential (svae_lds_ragged_perstep_*)
-extern "C" int SVAE_CAT(svae_lds_launch_ragged_perstep_n, SVAE_N)(const svae::LdsPerstepArgs* a, void* stream) {
-  return svae::launch_estep_ragged_perstep<SVAE_N>(*a, (hipStream_t)stream);
-}
+#ifndef __HIP_DEVICE_COMPILE__   /* host data: a const table with a constant initialiser would be emitted for the device too */
+extern "C" const svae::EstepUnit SVAE_CAT(svae_lds_estep_unit_n, SVAE_N) = {
+  .estep = estep, .estep_split = estep_split, .twoend = twoend, .twoend_mix = twoend_mix, .slds_rpc = slds_rpc,
+  .forward_pair = forward_pair, .filter = filter, .filter_split = filter_split, .filter_1r = filter_1r, .sample = sample,
+  .infer_lean = infer_lean, .ragged = ragged, .sample_ragged = sample_ragged, .ragged_perstep = ragged_perstep,
+};
+#endif

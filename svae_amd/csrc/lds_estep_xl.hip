@@ -36,7 +36,7 @@
 
 #include "../../include/svae_hip.h"
 #include "dpp.hpp"
-#include "lds_args.hpp"
+#include "lds_units.hpp"
 #include "lds_tile_mfma.hpp"
 #include "per_device.hpp"
 
@@ -487,33 +487,14 @@ extern "C" int svae_lds_xl_estep_f64(int B, int T, int n, int inhomog, int pair_
   if (n <= SVAE_LDS_TILE_MAX_N || n > SVAE_LDS_XL_MAX_N) return -3;
   if (keep != 0) return -23;
   if (pair_batched && !inhomog) return -5;
-  if (!init_J) return -6;
-  if (!init_h) return -7;
-  if (!init_logZ) return -8;
-  if (T > 1 && (!J11 || !J12 || !J22 || !logZ_pair)) return -9;
+  svae::LdsArgs a{};
+  svae::set_estep_args(a, B, T, n, pair_batched, init_J, init_h, init_logZ, J11, J12, J22, logZ_pair, node_J, node_h, node_logZ,
+                       lognorm, E_init, E_pair, E_node_diagxx, E_node_x, info, workspace);
+  if (const int rc = svae::check_model(a)) return rc;
   if (options != 0) return -24;
   if (B == 0) return 0;                  // (the per-sequence arrays of an empty batch may be NULL)
-  if (!node_J) return -13;
-  if (!node_h) return -14;
-  if (!lognorm) return -16;
-  if (!E_init) return -17;
-  if (!E_pair) return -18;
-  if (!E_node_diagxx) return -19;
-  if (!E_node_x) return -20;
-  if (!info) return -21;
+  if (const int rc = svae::check_arrays(a)) return rc;
   if (!workspace || ws_bytes < svae_lds_xl_workspace_bytes(B, T, n, inhomog, pair_batched)) return -22;
-  svae::LdsArgs a;
-  a.B = B; a.T = T;
-  a.init_J = init_J; a.init_h = init_h; a.init_logZ = init_logZ;
-  a.J11 = J11; a.J12 = J12; a.J22 = J22; a.logZ_pair = logZ_pair;
-  a.node_J = node_J; a.node_h = node_h; a.node_logZ = node_logZ;
-  a.lognorm = lognorm; a.E_init = E_init; a.E_pair = E_pair;
-  a.E_node_diagxx = E_node_diagxx; a.E_node_x = E_node_x;
-  a.info = info; a.ws = (double*)workspace; a.ws2 = a.ws3 = nullptr;
-  a.pair_seq_stride = pair_batched ? (long)(T - 1) * n * n : 0;
-  a.msg_Jp = a.msg_hp = a.msg_Jf = a.msg_hf = nullptr;
-  a.mix_w = nullptr; a.mix_out = nullptr; a.seq_index = nullptr; a.mix_K = 0; a.lds_keep = 0;
-  a.sig_out = nullptr; a.tile_half = 0;
   hipStream_t s = (hipStream_t)stream;
   switch ((n + 15) / 16) {
     case 5: return svae::launch_xl<5>(a, n, inhomog, s);

@@ -2,26 +2,22 @@
 // per-latent-dimension units of lds_prim_vjp_n.hip.  No allocation, no host synchronisation.
 #include <cstdint>
 #include "lds_prim_vjp.hpp"
+#include "lds_units.hpp"
 #include "../../include/svae_hip.h"
 
-extern "C" {
-#define SVAE_DECL(NN) int svae_lds_prim_vjp_n##NN(int, const svae::PrimArgs*, void*);
-SVAE_DECL(1) SVAE_DECL(2) SVAE_DECL(3) SVAE_DECL(4) SVAE_DECL(5) SVAE_DECL(6) SVAE_DECL(7)
-SVAE_DECL(8) SVAE_DECL(9) SVAE_DECL(10) SVAE_DECL(11) SVAE_DECL(12) SVAE_DECL(13) SVAE_DECL(14)
-SVAE_DECL(15)
+// the per-n units (lds_prim_vjp_n.hip: one launch function each, `which` = 0 filter, 1 smoother, 2 sampler VJP)
+typedef int (*PrimUnit)(int which, const svae::PrimArgs*, void* stream);
+#define SVAE_DECL(NN) extern "C" int svae_lds_prim_vjp_n##NN(int, const svae::PrimArgs*, void*);
+SVAE_LDS_NS(SVAE_DECL)
 #undef SVAE_DECL
-}
+#define SVAE_UNIT(NN) svae_lds_prim_vjp_n##NN,
+static const PrimUnit prim_units[SVAE_LDS_MAX_N + 1] = {nullptr, SVAE_LDS_NS(SVAE_UNIT)};
+#undef SVAE_UNIT
 
+// (prim_common has checked 1 <= n <= SVAE_LDS_MAX_N)
 static int prim_dispatch(int which, int n, const svae::PrimArgs* a, void* stream) {
   if (a->B == 0) return 0;
-  switch (n) {
-#define SVAE_CASE(NN) case NN: return svae_lds_prim_vjp_n##NN(which, a, stream);
-    SVAE_CASE(1) SVAE_CASE(2) SVAE_CASE(3) SVAE_CASE(4) SVAE_CASE(5) SVAE_CASE(6) SVAE_CASE(7)
-    SVAE_CASE(8) SVAE_CASE(9) SVAE_CASE(10) SVAE_CASE(11) SVAE_CASE(12) SVAE_CASE(13) SVAE_CASE(14)
-    SVAE_CASE(15)
-#undef SVAE_CASE
-  }
-  return -3;
+  return prim_units[n](which, a, stream);
 }
 
 static int prim_common(int B, int T, int n, int inhomog, int pair_batched, svae::PrimArgs* a) {

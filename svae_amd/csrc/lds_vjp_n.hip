@@ -8,6 +8,7 @@
 #endif
 #include "lds_vjp_kernel.hpp"
 #include "lds_lean_vjp.hpp"
+#include "lds_units.hpp"
 
 #ifndef SVAE_N
 #error "compile with -DSVAE_N=<latent dim>"
@@ -15,16 +16,11 @@
 #define SVAE_CAT_(a, b) a##b
 #define SVAE_CAT(a, b) SVAE_CAT_(a, b)
 
-extern "C" int SVAE_CAT(svae_lds_vjp_n, SVAE_N)(const svae::VjpArgs* a, void* stream) {
-  return svae::launch_vjp<SVAE_N>(*a, (hipStream_t)stream);
-}
+// The table's entries (lds_units.hpp says what each one is): file-local, reached only through svae_lds_vjp_unit_n<N>.
+static int vjp(const svae::VjpArgs& a, void* stream) { return svae::launch_vjp<SVAE_N>(a, (hipStream_t)stream); }
+static int vjp_lean(const svae::VjpArgs& a, void* stream) { return svae::launch_vjp_lean<SVAE_N>(a, (hipStream_t)stream); }
+static int vjp_ragged(const svae::VjpArgs& a, void* stream) { return svae::launch_vjp_ragged<SVAE_N>(a, (hipStream_t)stream); }
 
-// the two sweeps on the lean records of svae_lds_inference_f64 (lds_lean_vjp.hpp)
-extern "C" int SVAE_CAT(svae_lds_vjp_lean_n, SVAE_N)(const svae::VjpArgs* a, void* stream) {
-  return svae::launch_vjp_lean<SVAE_N>(*a, (hipStream_t)stream);
-}
-
-// per-sequence lengths (svae_lds_ragged_vjp_f64): the packed sweeps in their ragged instantiations
-extern "C" int SVAE_CAT(svae_lds_vjp_ragged_n, SVAE_N)(const svae::VjpArgs* a, void* stream) {
-  return svae::launch_vjp_ragged<SVAE_N>(*a, (hipStream_t)stream);
-}
+#ifndef __HIP_DEVICE_COMPILE__   /* host data: a const table with a constant initialiser would be emitted for the device too */
+extern "C" const svae::VjpUnit SVAE_CAT(svae_lds_vjp_unit_n, SVAE_N) = {.vjp = vjp, .vjp_lean = vjp_lean, .vjp_ragged = vjp_ragged};
+#endif
