@@ -190,6 +190,11 @@ def ptr(t):
     return None if t is None else ctypes.c_void_p(t.data_ptr())
 
 
+def ptrs(tensors, _void_p=ctypes.c_void_p):
+    """[ptr(t) for t in tensors] without a Python call per tensor: the argument groups of the launch wrappers, per call."""
+    return [None if t is None else _void_p(t.data_ptr()) for t in tensors]
+
+
 def current_stream(device):
     return ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)
 

@@ -25,20 +25,44 @@ __all__ = ["LDSEStepPlan", "natural_lds_estep_general", "cython_natural_lds_este
            "lds_inference_differentiable"]
 
 
-def _as_dev(x, device):
+def _as_dev(x, device, graph=False):
+    """float64, contiguous, on `device`; graph: a tensor stays in its autograd graph on the way (else detached)"""
     if isinstance(x, torch.Tensor):
-        t = x.detach()
+        t = x if graph else x.detach()
     else:
         t = torch.as_tensor(x, dtype=torch.float64)   # (a bare python float would become float32)
     return t.to(device=device, dtype=torch.float64).contiguous()
 
 
-def _canonical_init_params(init_params, device):
+def _find_device(tensors):
+    """The device of the first CUDA tensor among `tensors` (host data mixed in is copied there); the current one if none."""
+    for x in tensors:
+        if isinstance(x, torch.Tensor) and x.is_cuda:
+            return x.device
+    return torch.device("cuda", torch.cuda.current_device())
+
+
+def _canonical_init_params(init_params, device, graph=False):
     """lds_inference.py:62-63: (J, h, sum of the remaining log-normaliser terms)."""
-    J, h = _as_dev(init_params[0], device), _as_dev(init_params[1], device)
-    logZ = sum(_as_dev(z, device).reshape(()) for z in init_params[2:]) \
+    J, h = _as_dev(init_params[0], device, graph), _as_dev(init_params[1], device, graph)
+    logZ = sum(_as_dev(z, device, graph).reshape(()) for z in init_params[2:]) \
         if len(init_params) > 2 else torch.zeros((), dtype=torch.float64, device=device)
     return J, h, logZ.reshape(1).contiguous()
+
+
+def _canonical_pair_params(pair_params, B, T, n, device, graph=False):
+    """Shape checks and device tensors of pair_params = (J11, J12, J22, logZ): (n,n) blocks shared by all steps, per-step
+    (T-1,n,n) or per-step, per-sequence (B,T-1,n,n) ones -> (J11, J12, J22, logZ flat, inhomog, pair_batched).
+    graph: the tensors stay in their autograd graph (natparam_grad), where a shared logZ must be ONE number too."""
+    J11, J12, J22 = (_as_dev(x, device, graph) for x in pair_params[:3])
+    logZ_pair = _as_dev(pair_params[3], device, graph).reshape(-1)
+    inhomog, pair_batched = J11.dim() >= 3, J11.dim() == 4
+    want = {2: (n, n), 3: (T - 1, n, n), 4: (B, T - 1, n, n)}.get(J11.dim())
+    if want is None or any(tuple(x.shape) != want for x in (J11, J12, J22)):
+        raise ValueError("pair_params must be (n,n), (T-1,n,n) or (B,T-1,n,n)")
+    if (inhomog or graph) and logZ_pair.numel() != (1 if not inhomog else B * (T - 1) if pair_batched else T - 1):
+        raise ValueError("pair logZ must have one entry per " + ("pair block" if graph else "step"))
+    return J11, J12, J22, logZ_pair, inhomog, pair_batched
 
 
 _default_options = _lib.OPT_DEFAULT
@@ -125,21 +149,10 @@ class LDSEStepPlan(object):
         self.device = torch.device(device)
         f64 = dict(dtype=torch.float64, device=self.device)
         # (n > 15: the workspace also holds the re-packed pair parameters, one set per sequence if batched)
-        if self.xl:
-            self.ws_bytes = int(self.lib.svae_lds_xl_workspace_bytes(max(B, 1), T, n, int(self.inhomog),
-                                                                     int(bool(pair_batched))))
-        else:
-            self.ws_bytes = int(self.lib.svae_lds_workspace_bytes_ex(max(B, 1), T, n, int(self.inhomog),
-                                                                     int(bool(pair_batched))))
+        workspace_bytes = self.lib.svae_lds_xl_workspace_bytes if self.xl else self.lib.svae_lds_workspace_bytes_ex
+        self.ws_bytes = int(workspace_bytes(max(B, 1), T, n, int(self.inhomog), int(bool(pair_batched))))
         self.ws = torch.empty(self.ws_bytes // 8, **f64)
-        self.lognorm = torch.empty(B, **f64)
-        self.E_init = torch.empty(B, n * n + n, **f64)
-        if self.inhomog:
-            self.E_pair = torch.empty(B, max(T - 1, 0), 3, n, n, **f64)
-        else:
-            self.E_pair = torch.empty(B, 3, n, n, **f64)
-        self.E_node_diagxx = torch.empty(B, T, n, **f64)
-        self.E_node_x = torch.empty(B, T, n, **f64)
+        self._new_outputs()
         self.info = torch.zeros(1, dtype=torch.int32, device=self.device)
         self.reduced = torch.empty(4 * n * n + n + 2, **f64)
         # constants of the reference's statistic tuples (built once: no per-call allocation)
@@ -147,10 +160,61 @@ class LDSEStepPlan(object):
         self.ones_BT = torch.ones(B, T, **f64)
         self.ones_pair = torch.ones(B, max(T - 1, 0), **f64) if self.inhomog \
             else torch.full((B,), float(T - 1), **f64)
+        # buffers made on first use: the workspaces of vjp() and of its param_out, the batch sums of a ragged launch, and
+        # (lds_large.py) the tile VJP's workspace and the event of work that still reads the hand-off on a helper stream
+        self.vjp_ws = self.param_ws = self.reduced_ragged = self._vjp_ws = self._side_event = None
         # launch counter: the sampler / VJP read the workspace of the LAST launch, so an autograd node
         # remembers the launch it belongs to and refuses to run after the plan has been reused
-        self.epoch = 0
-        self._lengths = None     # (B,) int32 device tensor while the records of the last launch are ragged ones
+        self.epoch = -1
+        self._kept()             # (epoch 0: nothing launched, nothing kept)
+
+    def _kept(self, J12=None, pair_batched=False, has_factor=False, has_cross=False, lean=False, infer_S=None, lengths=None):
+        """What the launch that just succeeded left behind, all of it at once -- called after EVERY forward launch and from
+        nowhere else, so that no field survives from the launch before.  has_factor / has_cross: the records `sample()` /
+        `vjp()` read; lean: `infer()` kept lean records; infer_S: the number of samples `infer()` drew (it fixes the record
+        format), None after every other launch; lengths: (B,) int32 device tensor while the records are ragged ones."""
+        self.epoch += 1
+        self.has_factor, self.has_cross, self.lean, self._infer_S = bool(has_factor), bool(has_cross), bool(lean), infer_S
+        self._J12, self._pair_batched, self._lengths = J12, bool(pair_batched), lengths
+        # E_pair's fourth entry after a ragged launch: the sequence's own number of pairs
+        self.pair_counts = None if lengths is None else (lengths.clamp(1, self.T) - 1).to(torch.float64)
+
+    def _new_outputs(self):
+        f64 = dict(dtype=torch.float64, device=self.device)
+        B, T, n = self.B, self.T, self.n
+        self.lognorm = torch.empty(B, **f64)
+        self.E_init = torch.empty(B, n * n + n, **f64)
+        self.E_pair = torch.empty(B, max(T - 1, 0), 3, n, n, **f64) if self.inhomog else torch.empty(B, 3, n, n, **f64)
+        self.E_node_diagxx = torch.empty(B, T, n, **f64)
+        self.E_node_x = torch.empty(B, T, n, **f64)
+
+    def _call(self, name, args):
+        """The one way into the library's launching entry points: the return code is checked under the name called."""
+        _lib.check(getattr(self.lib, name)(*args), name)
+
+    def _forward(self, name, ints, model, outputs=None):
+        """A forward entry point: its integers; the pointers of `model` -- the ten tensors of the model and what the entry
+        takes behind them (lengths, eps, samples); then the end they all share, [five outputs | info | workspace, its
+        size | stream] -- outputs: the statistics, or (filter) lognorm and the four forward messages."""
+        if outputs is None:
+            outputs = (self.lognorm, self.E_init, self.E_pair, self.E_node_diagxx, self.E_node_x)
+        self._call(name, [*ints, *_lib.ptrs((*model, *outputs, self.info, self.ws)), self.ws_bytes,
+                          _lib.current_stream(self.device)])
+
+    def _grow_ws(self, need_bytes):
+        if self.ws_bytes < need_bytes:
+            self.ws = torch.empty(need_bytes // 8, dtype=torch.float64, device=self.device)
+            self.ws_bytes = self.ws.numel() * 8
+
+    def _checked_eps(self, eps):
+        shape = eps.shape
+        if len(shape) != 4 or shape[0] != self.B or shape[1] != self.T or shape[3] != self.n or shape[2] < 1:
+            raise ValueError("eps must be (B,T,S,n) with S >= 1")
+        return eps.to(device=self.device, dtype=torch.float64).contiguous()
+
+    def live(self):
+        """(B,T) bool: step t belongs to sequence b, t < lengths[b] (after a launch with per-sequence lengths)"""
+        return torch.arange(self.T, device=self.device)[None, :] < self._lengths[:, None]
 
     def _ragged(self, lengths, what, pair_batched=False):
         """Checks of a launch with per-sequence lengths (ValueError before anything is launched) -> (B,) int32 device
@@ -175,10 +239,7 @@ class LDSEStepPlan(object):
             if lengths.is_floating_point():
                 raise ValueError("%s(lengths=): an integer array or tensor" % what)
             lengths = lengths.to(device=self.device, dtype=torch.int32).contiguous()
-        need = int(workspace_bytes(max(self.B, 1), self.T, self.n))
-        if self.ws_bytes < need:
-            self.ws = torch.empty(need // 8, dtype=torch.float64, device=self.device)
-            self.ws_bytes = self.ws.numel() * 8
+        self._grow_ws(int(workspace_bytes(max(self.B, 1), self.T, self.n)))
         return lengths
 
     def _ragged_perstep(self, lengths, what, pair_batched, init_batched, tensors):
@@ -215,57 +276,28 @@ class LDSEStepPlan(object):
         potential (n,n), (n), (1), or with init_batched one per sequence, (B,n,n), (B,n), (B).  lengths (B,): as in `launch`.
         Per sequence b of length L the results are those of the sequence cut at L; E_pair[b, L-1:] and E_node_*[b, L:] are 0;
         pair parameters at t >= L-1 and node potentials at t >= L are never read.  `sample()` and `vjp()` cannot follow."""
-        p = _lib.ptr
-        lengths = self._ragged_perstep(lengths, "launch_ragged_perstep", pair_batched, init_batched,
-                                       (init_J, init_h, init_logZ, J11, J12, J22, logZ_pair, node_J, node_h, node_logZ))
-        rc = self.lib.svae_lds_ragged_perstep_estep_f64(
-            self.B, self.T, self.n, int(bool(pair_batched)), int(bool(init_batched)), int(bool(keep_factor)), self.options,
-            p(init_J), p(init_h), p(init_logZ), p(J11), p(J12), p(J22), p(logZ_pair),
-            p(node_J), p(node_h), p(node_logZ), p(lengths),
-            p(self.lognorm), p(self.E_init), p(self.E_pair), p(self.E_node_diagxx),
-            p(self.E_node_x), p(self.info), p(self.ws), self.ws_bytes, _lib.current_stream(self.device))
-        _lib.check(rc, "svae_lds_ragged_perstep_estep_f64")
-        self._after_ragged_perstep(lengths, J12, pair_batched, bool(keep_factor))
+        model = (init_J, init_h, init_logZ, J11, J12, J22, logZ_pair, node_J, node_h, node_logZ)
+        lengths = self._ragged_perstep(lengths, "launch_ragged_perstep", pair_batched, init_batched, model)
+        self._forward("svae_lds_ragged_perstep_estep_f64", (self.B, self.T, self.n, int(bool(pair_batched)),
+                      int(bool(init_batched)), int(bool(keep_factor)), self.options), model + (lengths,))
+        self._kept(J12, pair_batched, has_factor=keep_factor, lengths=lengths)       # (no cross moments: vjp() refuses)
 
     def infer_ragged_perstep(self, init_J, init_h, init_logZ, J11, J12, J22, logZ_pair, node_J, node_h, node_logZ=None,
                              lengths=None, pair_batched=False, init_batched=False, eps=None, out=None):
         """launch_ragged_perstep + the ragged sampler in one call (svae_lds_ragged_perstep_inference_f64).  eps (B,T,S,n) or
         None -> samples (0 at t >= lengths[b]; eps there is never read) or None."""
-        p = _lib.ptr
         S = 0
         if eps is not None:
-            if eps.dim() != 4 or eps.shape[0] != self.B or eps.shape[1] != self.T or eps.shape[3] != self.n \
-                    or eps.shape[2] < 1:
-                raise ValueError("eps must be (B,T,S,n) with S >= 1")
-        lengths = self._ragged_perstep(lengths, "infer_ragged_perstep", pair_batched, init_batched,
-                                       (init_J, init_h, init_logZ, J11, J12, J22, logZ_pair, node_J, node_h, node_logZ))
-        if eps is not None:
-            eps = eps.to(device=self.device, dtype=torch.float64).contiguous()
+            eps = self._checked_eps(eps)
             S = eps.shape[2]
-            if out is None:
-                out = torch.empty_like(eps)
-        rc = self.lib.svae_lds_ragged_perstep_inference_f64(
-            self.B, self.T, self.n, S, int(bool(pair_batched)), int(bool(init_batched)), self.options,
-            p(init_J), p(init_h), p(init_logZ), p(J11), p(J12), p(J22), p(logZ_pair),
-            p(node_J), p(node_h), p(node_logZ), p(lengths), p(eps), p(out),
-            p(self.lognorm), p(self.E_init), p(self.E_pair), p(self.E_node_diagxx), p(self.E_node_x),
-            p(self.info), p(self.ws), self.ws_bytes, _lib.current_stream(self.device))
-        _lib.check(rc, "svae_lds_ragged_perstep_inference_f64")
-        self._after_ragged_perstep(lengths, J12, pair_batched, S > 0)
+        model = (init_J, init_h, init_logZ, J11, J12, J22, logZ_pair, node_J, node_h, node_logZ)
+        lengths = self._ragged_perstep(lengths, "infer_ragged_perstep", pair_batched, init_batched, model)
+        if S and out is None:
+            out = torch.empty_like(eps)
+        self._forward("svae_lds_ragged_perstep_inference_f64", (self.B, self.T, self.n, S, int(bool(pair_batched)),
+                      int(bool(init_batched)), self.options), model + (lengths, eps, out))
+        self._kept(J12, pair_batched, has_factor=S > 0, lengths=lengths)
         return out if eps is not None else None
-
-    def _after_ragged_perstep(self, lengths, J12, pair_batched, has_factor):
-        self.epoch += 1
-        self.has_factor, self.has_cross = has_factor, False       # (no cross moments: vjp() refuses)
-        self.lean, self._infer_S = False, None
-        self._J12 = J12
-        self._pair_batched = bool(pair_batched)
-        self._set_ragged(lengths)
-
-    def _set_ragged(self, lengths):
-        self._lengths = lengths
-        # E_pair's fourth entry: the sequence's own number of pairs
-        self.pair_counts = (lengths.clamp(1, self.T) - 1).to(torch.float64)
 
     @property
     def xl(self):
@@ -287,85 +319,42 @@ class LDSEStepPlan(object):
         (smoother + statistics from the hand-off of a preceding half=1 launch); 0 = both.
         keep_sigma (16 <= n <= 64 only, after `vjp_tail`): the backward half leaves the smoothed covariances in the
         first section of the VJP workspace behind the hand-off (SVAE_KEEP_SIGMA), which saves the VJP its phase 0."""
-        p = _lib.ptr
+        model = (init_J, init_h, init_logZ, J11, J12, J22, logZ_pair, node_J, node_h, node_logZ)
+        keep = int(bool(keep_factor)) | (2 if keep_cross else 0)
         if lengths is not None:
             if half or keep_sigma:
                 raise ValueError("launch(lengths=): no E-step halves / keep_sigma (latent dimension <= %d)" % _lib.LDS_MAX_N)
             lengths = self._ragged(lengths, "launch", pair_batched)
-            keep = int(bool(keep_factor)) | (2 if keep_cross else 0)
-            rc = self.lib.svae_lds_ragged_estep_f64(
-                self.B, self.T, self.n, 0, 0, keep, self.options,
-                p(init_J), p(init_h), p(init_logZ), p(J11), p(J12), p(J22), p(logZ_pair),
-                p(node_J), p(node_h), p(node_logZ), p(lengths),
-                p(self.lognorm), p(self.E_init), p(self.E_pair), p(self.E_node_diagxx),
-                p(self.E_node_x), p(self.info), p(self.ws), self.ws_bytes,
-                _lib.current_stream(self.device))
-            _lib.check(rc, "svae_lds_ragged_estep_f64")
-            self.epoch += 1
-            self.has_factor, self.has_cross = bool(keep_factor), bool(keep_cross)
-            self.lean, self._infer_S = False, None
-            self._J12 = J12
-            self._pair_batched = False
-            self._set_ragged(lengths)
+            self._forward("svae_lds_ragged_estep_f64", (self.B, self.T, self.n, 0, 0, keep, self.options), model + (lengths,))
+            self._kept(J12, has_factor=keep_factor, has_cross=keep_cross, lengths=lengths)
             return
-        self._lengths = None
         if self.xl:
             # 65 <= n <= 128: E-step only; the plan's options word (kernel choice of the smaller paths) does not apply
             if half or keep_factor or keep_cross or keep_sigma:
                 self._no_xl("E-step halves and kept records (half=, keep_*)")
-            rc = self.lib.svae_lds_xl_estep_f64(
-                self.B, self.T, self.n, int(self.inhomog), int(pair_batched), 0, 0,
-                p(init_J), p(init_h), p(init_logZ), p(J11), p(J12), p(J22), p(logZ_pair),
-                p(node_J), p(node_h), p(node_logZ),
-                p(self.lognorm), p(self.E_init), p(self.E_pair), p(self.E_node_diagxx),
-                p(self.E_node_x), p(self.info), p(self.ws), self.ws_bytes,
-                _lib.current_stream(self.device))
-            _lib.check(rc, "svae_lds_xl_estep_f64")
-            self.epoch += 1
-            self.has_factor = self.has_cross = False
-            self.lean, self._infer_S = False, None
-            self._J12 = J12
-            self._pair_batched = bool(pair_batched)
+            self._forward("svae_lds_xl_estep_f64", (self.B, self.T, self.n, int(self.inhomog), int(pair_batched), 0, 0), model)
+            self._kept(J12, pair_batched)
             return
-        ev = getattr(self, "_side_event", None)
-        if ev is not None:       # work on a helper stream still reads the hand-off this launch overwrites (lds_large.py)
-            torch.cuda.current_stream(self.device).wait_event(ev)
+        if self._side_event is not None:   # work on a helper stream still reads the hand-off this launch overwrites (lds_large.py)
+            torch.cuda.current_stream(self.device).wait_event(self._side_event)
             self._side_event = None
-        keep = int(bool(keep_factor)) | (2 if keep_cross else 0)
-        if self.n > _lib.LDS_MAX_N:
+        small = self.n <= _lib.LDS_MAX_N
+        if not small:
             # tile kernel: its hand-off always serves the sampler / VJP kernels (lds_large.py)
             keep = _lib.KEEP_SIGMA if (keep_sigma and half != 1) else 0
         options = self.options
         if half:
-            if self.n <= _lib.LDS_MAX_N:
+            if small:
                 raise ValueError("E-step halves: latent dimension > %d only" % _lib.LDS_MAX_N)
             options |= _lib.OPT_TILE_FORWARD if half == 1 else _lib.OPT_TILE_BACKWARD
-        rc = self.lib.svae_lds_estep_f64(
-            self.B, self.T, self.n, int(self.inhomog), int(pair_batched), keep, options,
-            p(init_J), p(init_h), p(init_logZ), p(J11), p(J12), p(J22), p(logZ_pair),
-            p(node_J), p(node_h), p(node_logZ),
-            p(self.lognorm), p(self.E_init), p(self.E_pair), p(self.E_node_diagxx),
-            p(self.E_node_x), p(self.info), p(self.ws), self.ws_bytes,
-            _lib.current_stream(self.device))
-        _lib.check(rc, "svae_lds_estep_f64")
-        self.epoch += 1
-        self.has_factor = bool(keep_factor) and self.n <= _lib.LDS_MAX_N
-        self.has_cross = bool(keep_cross) and self.n <= _lib.LDS_MAX_N
-        self.lean, self._infer_S = False, None
-        self._J12 = J12
-        self._pair_batched = bool(pair_batched)
+        self._forward("svae_lds_estep_f64", (self.B, self.T, self.n, int(self.inhomog), int(pair_batched), keep, options), model)
+        self._kept(J12, pair_batched, keep_factor and small, keep_cross and small)
 
     def fresh_outputs(self):
         """New output tensors for the next launch (lognorm, E_init, E_pair, E_node_*): a caller that hands the outputs on
         -- the autograd node below -- returns them as they are instead of copying them out of buffers the next launch
         would overwrite (two of them are (B,T,n): 2 x 65 MB at 4096 x 200 x 10)."""
-        f64 = dict(dtype=torch.float64, device=self.device)
-        B, T, n = self.B, self.T, self.n
-        self.lognorm = torch.empty(B, **f64)
-        self.E_init = torch.empty(B, n * n + n, **f64)
-        self.E_pair = torch.empty(B, max(T - 1, 0), 3, n, n, **f64) if self.inhomog else torch.empty(B, 3, n, n, **f64)
-        self.E_node_diagxx = torch.empty(B, T, n, **f64)
-        self.E_node_x = torch.empty(B, T, n, **f64)
+        self._new_outputs()
 
     def infer(self, init_J, init_h, init_logZ, J11, J12, J22, logZ_pair, node_J, node_h, node_logZ=None,
               pair_batched=False, eps=None, out=None, keep_vjp=True, lengths=None):
@@ -380,49 +369,25 @@ class LDSEStepPlan(object):
         self._no_xl("infer()")
         if self.n > _lib.LDS_MAX_N:
             raise ValueError("infer(): latent dimension <= %d (the tile path runs its stages separately)" % _lib.LDS_MAX_N)
-        p = _lib.ptr
         S = 0
         if eps is not None:
-            if eps.dim() != 4 or eps.shape[0] != self.B or eps.shape[1] != self.T or eps.shape[3] != self.n \
-                    or eps.shape[2] < 1:
-                raise ValueError("eps must be (B,T,S,n) with S >= 1")
-            eps = eps.to(device=self.device, dtype=torch.float64).contiguous()
+            eps = self._checked_eps(eps)
             S = eps.shape[2]
             if out is None:
                 out = torch.empty_like(eps)
+        model = (init_J, init_h, init_logZ, J11, J12, J22, logZ_pair, node_J, node_h, node_logZ)
+        keep_vjp = bool(keep_vjp)
         if lengths is not None:
             lengths = self._ragged(lengths, "infer", pair_batched)
-            rc = self.lib.svae_lds_ragged_inference_f64(
-                self.B, self.T, self.n, S, 0, 0, int(bool(keep_vjp)), self.options,
-                p(init_J), p(init_h), p(init_logZ), p(J11), p(J12), p(J22), p(logZ_pair),
-                p(node_J), p(node_h), p(node_logZ), p(lengths), p(eps), p(out),
-                p(self.lognorm), p(self.E_init), p(self.E_pair), p(self.E_node_diagxx), p(self.E_node_x),
-                p(self.info), p(self.ws), self.ws_bytes, _lib.current_stream(self.device))
-            _lib.check(rc, "svae_lds_ragged_inference_f64")
-            self.epoch += 1
-            self.lean, self._infer_S = False, None
-            self.has_factor = bool(keep_vjp) or S > 0
-            self.has_cross = bool(keep_vjp)
-            self._J12 = J12
-            self._pair_batched = False
-            self._set_ragged(lengths)
-            return out if eps is not None else None
-        self._lengths = None
-        rc = self.lib.svae_lds_inference_f64(
-            self.B, self.T, self.n, S, int(self.inhomog), int(pair_batched), int(bool(keep_vjp)), self.options,
-            p(init_J), p(init_h), p(init_logZ), p(J11), p(J12), p(J22), p(logZ_pair),
-            p(node_J), p(node_h), p(node_logZ), p(eps), p(out),
-            p(self.lognorm), p(self.E_init), p(self.E_pair), p(self.E_node_diagxx), p(self.E_node_x),
-            p(self.info), p(self.ws), self.ws_bytes, _lib.current_stream(self.device))
-        _lib.check(rc, "svae_lds_inference_f64")
-        self.epoch += 1
-        self.lean = bool(self.lib.svae_lds_inference_is_lean(self.B, self.T, self.n, S, int(self.inhomog),
-                                                             int(bool(keep_vjp)), self.options))
-        self.has_factor = not self.lean and (bool(keep_vjp) or S > 0)
-        self.has_cross = bool(keep_vjp)
-        self._infer_S = S
-        self._J12 = J12
-        self._pair_batched = bool(pair_batched)
+            self._forward("svae_lds_ragged_inference_f64", (self.B, self.T, self.n, S, 0, 0, int(keep_vjp), self.options),
+                          model + (lengths, eps, out))
+            self._kept(J12, has_factor=keep_vjp or S > 0, has_cross=keep_vjp, lengths=lengths)
+        else:
+            self._forward("svae_lds_inference_f64", (self.B, self.T, self.n, S, int(self.inhomog), int(pair_batched),
+                          int(keep_vjp), self.options), model + (eps, out))
+            lean = bool(self.lib.svae_lds_inference_is_lean(self.B, self.T, self.n, S, int(self.inhomog), int(keep_vjp),
+                                                            self.options))
+            self._kept(J12, pair_batched, not lean and (keep_vjp or S > 0), keep_vjp, lean, infer_S=S)
         return out if eps is not None else None
 
     def vjp_tail(self, S, pair_batched=False):
@@ -435,9 +400,7 @@ class LDSEStepPlan(object):
         nws = int(self.lib.svae_lds_tile_vjp_workspace_doubles(B, T, n, S))
         if off == 0:
             raise ValueError("vjp_tail: latent dimension > %d only" % _lib.LDS_MAX_N)
-        if self.ws.numel() < off + nws:
-            self.ws = torch.empty(off + nws, dtype=torch.float64, device=self.device)
-            self.ws_bytes = self.ws.numel() * 8
+        self._grow_ws((off + nws) * 8)
         return self.ws[off:off + nws]
 
     def filter(self, init_J, init_h, init_logZ, J11, J12, J22, logZ_pair, node_J, node_h,
@@ -445,48 +408,34 @@ class LDSEStepPlan(object):
         """Filter-only launch (svae_lds_filter_f64): lognorm, optional forward messages, and the hand-off
         `sample()` needs."""
         self._no_xl("filter()")
-        p = _lib.ptr
-        rc = self.lib.svae_lds_filter_f64(
-            self.B, self.T, self.n, int(self.inhomog), int(pair_batched), self.options,
-            p(init_J), p(init_h), p(init_logZ), p(J11), p(J12), p(J22), p(logZ_pair),
-            p(node_J), p(node_h), p(node_logZ), p(self.lognorm), p(J_pred), p(h_pred), p(J_filt), p(h_filt),
-            p(self.info), p(self.ws), self.ws_bytes, _lib.current_stream(self.device))
-        _lib.check(rc, "svae_lds_filter_f64")
-        self.epoch += 1
-        self._lengths = None
-        self.has_factor, self.has_cross = True, False
-        self.lean, self._infer_S = False, None
-        self._J12 = J12
-        self._pair_batched = bool(pair_batched)
+        model = (init_J, init_h, init_logZ, J11, J12, J22, logZ_pair, node_J, node_h, node_logZ)
+        self._forward("svae_lds_filter_f64", (self.B, self.T, self.n, int(self.inhomog), int(pair_batched), self.options),
+                      model, outputs=(self.lognorm, J_pred, h_pred, J_filt, h_filt))
+        self._kept(J12, pair_batched, has_factor=True)
 
     def sample(self, eps, out=None):
         """Backward sampling from the messages of the last `launch(..., keep_factor=True)`.
         eps: (B,T,S,n) standard-normal draws -> samples (B,T,S,n)
         [natural_sample_backward, cython_lds_inference.pyx:310-355]."""
         self._no_xl("sample()")
-        if eps.dim() != 4 or eps.shape[0] != self.B or eps.shape[1] != self.T or eps.shape[3] != self.n \
-                or eps.shape[2] < 1:
-            raise ValueError("eps must be (B,T,S,n) with S >= 1")
+        eps = self._checked_eps(eps)
         if self.n > _lib.LDS_MAX_N:
             # 16 <= n <= 64: noise-factor kernel + recursion kernel on the tile kernel's hand-off (lds_large.py)
             from .lds_large import sample_from_handoff
             if self.epoch == 0:
                 raise RuntimeError("sample() needs a preceding launch()")
-            return sample_from_handoff(self, eps.to(device=self.device, dtype=torch.float64))
+            return sample_from_handoff(self, eps)
         if self._lengths is not None:
             raise RuntimeError("sample(): the last launch had per-sequence lengths -- draw the samples in that call, infer(..., eps, lengths=)")
-        if getattr(self, "lean", False):
+        if self.lean:
             raise RuntimeError("sample(): the last launch was infer() on lean records -- its samples were drawn there")
-        if not getattr(self, "has_factor", False):
+        if not self.has_factor:
             raise RuntimeError("sample() needs a preceding launch(..., keep_factor=True)")
-        eps = eps.to(device=self.device, dtype=torch.float64).contiguous()
-        S = eps.shape[2]
         if out is None:
             out = torch.empty_like(eps)
         p = _lib.ptr
-        rc = self.lib.svae_lds_sample_f64(self.B, self.T, self.n, S, self.options, p(eps), p(out), p(self.ws),
-                                          self.ws_bytes, _lib.current_stream(self.device))
-        _lib.check(rc, "svae_lds_sample_f64")
+        self._call("svae_lds_sample_f64", (self.B, self.T, self.n, eps.shape[2], self.options, p(eps), p(out), p(self.ws),
+                                           self.ws_bytes, _lib.current_stream(self.device)))
         return out
 
     def vjp(self, g_lognorm, g_E_node_diagxx=None, g_E_node_x=None, g_samples=None, eps=None,
@@ -518,7 +467,7 @@ class LDSEStepPlan(object):
                                  "no dense node-potential cotangents")
             if g_E_init is not None or g_E_pair is not None:
                 raise ValueError("vjp() after a launch with lengths: no cotangents of E_init / E_pair (pair_stats_grad)")
-        lean = getattr(self, "lean", False)
+        lean = self.lean
         if param_out:
             if self.n > _lib.LDS_MAX_N:
                 raise ValueError("parameter gradients: latent dimension <= %d (n = %d)" % (_lib.LDS_MAX_N, self.n))
@@ -527,7 +476,7 @@ class LDSEStepPlan(object):
                                  "kept lean ones (make the plan with options | OPT_LEAN_OFF)")
             if dense_out is not None:
                 raise ValueError("param_out and dense_out are separate calls")
-        if not (getattr(self, "has_cross", False) and (lean or getattr(self, "has_factor", False))):
+        if not (self.has_cross and (lean or self.has_factor)):
             raise RuntimeError("vjp() needs a preceding launch(..., keep_factor=True, keep_cross=True) or infer()")
         if lean and (g_E_init is not None or g_E_pair is not None):
             raise ValueError("lean records (infer() on a large homogeneous batch): no cotangents of E_init / E_pair")
@@ -541,13 +490,12 @@ class LDSEStepPlan(object):
         g_E_init, g_E_pair = c(g_E_init), c(g_E_pair)
         S = 0 if g_samples is None else g_samples.shape[2]
         options = self.options
-        infer_S = getattr(self, "_infer_S", None)
-        if infer_S is not None:
+        if self._infer_S is not None:
             # the workspace was written by infer(): the VJP is told so and takes the S of that call (it fixes the format)
-            if g_samples is not None and S != infer_S:
-                raise ValueError("vjp(): %d sample cotangents for an infer() call that drew %d" % (S, infer_S))
+            if g_samples is not None and S != self._infer_S:
+                raise ValueError("vjp(): %d sample cotangents for an infer() call that drew %d" % (S, self._infer_S))
             options |= _lib.OPT_INFER_RECORDS
-            S = infer_S
+            S = self._infer_S
         if S > 16:
             # the kernels take 16 sample cotangents per launch; the VJP is linear in the cotangents: the first chunk
             # travels with all the others, the remaining chunks alone
@@ -564,38 +512,33 @@ class LDSEStepPlan(object):
                     for x, y in zip(first[2], more[2]):
                         x += y
             return (gJ, gh, first[2]) if param_out else (gJ, gh)
-        if not hasattr(self, "vjp_ws"):
-            self.vjp_ws_bytes = int(self.lib.svae_lds_vjp_workspace_bytes(max(self.B, 1), self.T, self.n))
+        B, T, n = self.B, self.T, self.n
+        if self.vjp_ws is None:
+            self.vjp_ws_bytes = int(self.lib.svae_lds_vjp_workspace_bytes(max(B, 1), T, n))
             self.vjp_ws = torch.empty(self.vjp_ws_bytes // 8, **f64)
-        gJ = torch.empty(self.B, self.T, self.n, **f64)
-        gh = torch.empty(self.B, self.T, self.n, **f64)
+        gJ = torch.empty(B, T, n, **f64)
+        gh = torch.empty(B, T, n, **f64)
         p = _lib.ptr
+        workspaces = [p(self.ws), self.ws_bytes, p(self.vjp_ws), self.vjp_ws_bytes, _lib.current_stream(self.device)]
         if ragged:
-            rc = self.lib.svae_lds_ragged_vjp_f64(
-                self.B, self.T, self.n, S, 0, 0, self.options,
-                p(g_lognorm), p(g_E_node_diagxx), p(g_E_node_x), p(g_samples), p(eps), p(samples), p(self._lengths),
-                p(gJ), p(gh), p(self.ws), self.ws_bytes, p(self.vjp_ws), self.vjp_ws_bytes,
-                _lib.current_stream(self.device))
-            _lib.check(rc, "svae_lds_ragged_vjp_f64")
+            self._call("svae_lds_ragged_vjp_f64", [B, T, n, S, 0, 0, self.options] + _lib.ptrs(
+                (g_lognorm, g_E_node_diagxx, g_E_node_x, g_samples, eps, samples, self._lengths, gJ, gh)) + workspaces)
             return gJ, gh
+        # what the three entry points begin with: shape, layout and options, then the thirteen pointers up to (gJ, gh)
+        pb = self._pair_batched
+        head = [B, T, n, S, int(self.inhomog), int(pb), options] + _lib.ptrs(
+            (self._J12, g_lognorm, g_E_node_diagxx, g_E_node_x, g_E_init, g_E_pair, g_samples, eps, samples,
+             self.E_pair, self.E_node_x, gJ, gh))
         if param_out:
-            B, T, n = self.B, self.T, self.n
-            pb = bool(self._pair_batched)
-            if not hasattr(self, "param_ws"):
+            if self.param_ws is None:
                 self.param_ws_bytes = int(self.lib.svae_lds_param_vjp_workspace_bytes(max(B, 1), T, n, int(self.inhomog), int(pb)))
                 self.param_ws = torch.empty(self.param_ws_bytes // 8, **f64)
             lead = ((B, max(T - 1, 0)) if pb else (max(T - 1, 0),)) if self.inhomog else ()
             out = (torch.empty(n, n, **f64), torch.empty(n, **f64), torch.empty(1, **f64),
                    torch.empty(*lead, n, n, **f64), torch.empty(*lead, n, n, **f64), torch.empty(*lead, n, n, **f64),
                    torch.empty(*lead, **f64) if self.inhomog else torch.empty(1, **f64))
-            rc = self.lib.svae_lds_estep_vjp_params_f64(
-                B, T, n, S, int(self.inhomog), int(pb), options,
-                p(self._J12), p(g_lognorm), p(g_E_node_diagxx), p(g_E_node_x), p(g_E_init), p(g_E_pair),
-                p(g_samples), p(eps), p(samples), p(self.E_pair), p(self.E_node_x), p(gJ), p(gh),
-                *[p(x) for x in out],
-                p(self.ws), self.ws_bytes, p(self.vjp_ws), self.vjp_ws_bytes, p(self.param_ws), self.param_ws_bytes,
-                _lib.current_stream(self.device))
-            _lib.check(rc, "svae_lds_estep_vjp_params_f64")
+            workspaces[4:4] = [p(self.param_ws), self.param_ws_bytes]            # (in front of the stream)
+            self._call("svae_lds_estep_vjp_params_f64", head + _lib.ptrs(out) + workspaces)
             if B == 0:
                 for x in out:
                     x.zero_()
@@ -603,19 +546,9 @@ class LDSEStepPlan(object):
         if dense_out is not None:
             if S > 16 or lean:
                 raise ValueError("dense node-potential cotangents: at most 16 sample cotangents, full records")
-            rc = self.lib.svae_lds_estep_vjp_dense_f64(
-                self.B, self.T, self.n, S, int(self.inhomog), int(self._pair_batched), options,
-                p(self._J12), p(g_lognorm), p(g_E_node_diagxx), p(g_E_node_x), p(g_E_init), p(g_E_pair),
-                p(g_samples), p(eps), p(samples), p(self.E_pair), p(self.E_node_x), p(gJ), p(gh), p(dense_out),
-                p(self.ws), self.ws_bytes, p(self.vjp_ws), self.vjp_ws_bytes, _lib.current_stream(self.device))
-            _lib.check(rc, "svae_lds_estep_vjp_dense_f64")
-            return gJ, gh
-        rc = self.lib.svae_lds_estep_vjp_ex_f64(
-            self.B, self.T, self.n, S, int(self.inhomog), int(self._pair_batched), options,
-            p(self._J12), p(g_lognorm), p(g_E_node_diagxx), p(g_E_node_x), p(g_E_init), p(g_E_pair),
-            p(g_samples), p(eps), p(samples), p(self.E_pair), p(self.E_node_x), p(gJ), p(gh),
-            p(self.ws), self.ws_bytes, p(self.vjp_ws), self.vjp_ws_bytes, _lib.current_stream(self.device))
-        _lib.check(rc, "svae_lds_estep_vjp_ex_f64")
+            self._call("svae_lds_estep_vjp_dense_f64", head + [p(dense_out)] + workspaces)
+        else:
+            self._call("svae_lds_estep_vjp_ex_f64", head + workspaces)
         return gJ, gh
 
     def reduce(self):
@@ -623,20 +556,17 @@ class LDSEStepPlan(object):
         per-sequence lengths one more slot, sum_b (lengths[b] - 1): the pair count, which is not B (T-1) then."""
         if self.inhomog:
             raise ValueError("reduce(): per-step pair statistics (B,T-1,3,n,n) have no batch-summed form here")
-        p = _lib.ptr
+        stats = (self.E_init, self.E_pair, self.lognorm)
+        stream = [_lib.current_stream(self.device)]
         if self._lengths is not None:
             # [sum E_init | sum E_pair | sum lognorm | B | sum_b (lengths[b] - 1)]: one more slot, the pair count
-            if not hasattr(self, "reduced_ragged"):
+            if self.reduced_ragged is None:
                 self.reduced_ragged = torch.empty(4 * self.n * self.n + self.n + 3, dtype=torch.float64, device=self.device)
-            rc = self.lib.svae_lds_ragged_reduce_stats_f64(self.B, self.T, self.n, p(self.E_init), p(self.E_pair),
-                                                           p(self.lognorm), p(self._lengths), p(self.reduced_ragged),
-                                                           _lib.current_stream(self.device))
-            _lib.check(rc, "svae_lds_ragged_reduce_stats_f64")
+            self._call("svae_lds_ragged_reduce_stats_f64",
+                       [self.B, self.T, self.n] + _lib.ptrs(stats + (self._lengths, self.reduced_ragged)) + stream)
             return self.reduced_ragged
-        fn = self.lib.svae_lds_xl_reduce_stats_f64 if self.xl else self.lib.svae_lds_reduce_stats_f64
-        rc = fn(self.B, self.n, p(self.E_init), p(self.E_pair), p(self.lognorm), p(self.reduced),
-                _lib.current_stream(self.device))
-        _lib.check(rc, fn.__name__)
+        self._call("svae_lds_xl_reduce_stats_f64" if self.xl else "svae_lds_reduce_stats_f64",
+                   [self.B, self.n] + _lib.ptrs(stats + (self.reduced,)) + stream)
         return self.reduced
 
     def check_info(self):
@@ -677,13 +607,7 @@ def _fold_dense_nodes(natparam, node_params):
     by these terms (put back in `natural_filter_forward_general`).
     -> (natparam', node_params' batched (B,T,n), info)"""
     init_params, pair_params = natparam
-    dev = None
-    for x in list(node_params) + list(init_params[:2]):
-        if isinstance(x, torch.Tensor) and x.is_cuda:
-            dev = x.device
-            break
-    if dev is None:
-        dev = torch.device("cuda", torch.cuda.current_device())
+    dev = _find_device(list(node_params) + list(init_params[:2]))
     node_J, node_h = _as_dev(node_params[0], dev), _as_dev(node_params[1], dev)
     node_logZ = _as_dev(node_params[2], dev) if len(node_params) == 3 else None
     batched = node_h.dim() == 3
@@ -777,13 +701,7 @@ def _prepare(natparam, node_params, plan):
     init_params, pair_params = natparam
     if not isinstance(node_params, (tuple, list)) or len(node_params) not in (2, 3):
         raise ValueError("node_params must be (J, h) or (J, h, logZ)")
-    dev = None
-    for x in list(node_params) + list(init_params[:2]):
-        if isinstance(x, torch.Tensor) and x.is_cuda:
-            dev = x.device
-            break
-    if dev is None:
-        dev = torch.device("cuda", torch.cuda.current_device())
+    dev = _find_device(list(node_params) + list(init_params[:2]))
     node_J, node_h = _as_dev(node_params[0], dev), _as_dev(node_params[1], dev)
     node_logZ = _as_dev(node_params[2], dev) if len(node_params) == 3 else None
     if node_J.dim() == 3 and node_h.dim() == 2:
@@ -804,16 +722,7 @@ def _prepare(natparam, node_params, plan):
     init_J, init_h, init_logZ = _canonical_init_params(init_params, dev)
     if tuple(init_J.shape) != (n, n) or tuple(init_h.shape) != (n,):
         raise ValueError("init_params shapes do not match the node potentials")
-    J11, J12, J22 = (_as_dev(x, dev) for x in pair_params[:3])
-    logZ_pair = _as_dev(pair_params[3], dev).reshape(-1)
-    inhomog = J11.dim() >= 3
-    pair_batched = J11.dim() == 4
-    want = {2: (n, n), 3: (T - 1, n, n), 4: (B, T - 1, n, n)}.get(J11.dim())
-    if want is None or any(tuple(x.shape) != want for x in (J11, J12, J22)):
-        raise ValueError("pair_params must be (n,n), (T-1,n,n) or (B,T-1,n,n)")
-    if inhomog and logZ_pair.numel() != (B * (T - 1) if pair_batched else T - 1):
-        raise ValueError("pair logZ must have one entry per step")
-
+    J11, J12, J22, logZ_pair, inhomog, pair_batched = _canonical_pair_params(pair_params, B, T, n, dev)
     if plan is None:
         plan = LDSEStepPlan(B, T, n, dev, inhomog, pair_batched, options=_guarded_plan_options(pair_params, inhomog))
     elif (plan.B, plan.T, plan.n, plan.inhomog) != (B, T, n, inhomog):
@@ -822,8 +731,7 @@ def _prepare(natparam, node_params, plan):
                 args=(init_J, init_h, init_logZ, J11, J12, J22, logZ_pair, node_J, node_h, node_logZ))
 
 
-def natural_lds_estep_general(natparam, node_params, plan=None, check=False, keep_factor=False, _infer_eps=None,
-                              lengths=None):
+def natural_lds_estep_general(natparam, node_params, plan=None, check=False, keep_factor=False, lengths=None):
     """E-step = filter + smoother (lds_inference.py:223-237).
 
     natparam = (init_params, pair_params); init_params = (-1/2 J0, h0, logZ...) and
@@ -857,12 +765,17 @@ def natural_lds_estep_general(natparam, node_params, plan=None, check=False, kee
         natparam, node_params, info = _fold_dense_nodes(natparam, node_params)
         lognorm, stats = natural_lds_estep_general(natparam, node_params, check=check, keep_factor=keep_factor)
         return (lognorm if info["batched"] else lognorm[0]), _dense_stats(stats, info)
+    return _estep(natparam, node_params, plan, check, keep_factor, lengths=lengths)[:2]
+
+
+def _estep(natparam, node_params, plan=None, check=False, keep_factor=False, eps=None, lengths=None):
+    """natural_lds_estep_general on diagonal node potentials -> (lognorm, expected_stats, samples).  eps (B,T,S,n): E-step +
+    sampler in ONE call (plan.infer, forward values only: lean records for large homogeneous batches); None: no samples."""
     q = _prepare(natparam, node_params, plan)
-    plan, batched, B, T, n, inhomog = q["plan"], q["batched"], q["B"], q["T"], q["n"], q["inhomog"]
-    dev = plan.device
-    if _infer_eps is not None:
-        # (natural_lds_inference_general: E-step + sampler in one call -- lean records for large homogeneous batches)
-        plan._infer_samples = plan.infer(*q["args"], q["pair_batched"], _infer_eps, keep_vjp=False, lengths=lengths)
+    plan, batched, B, n, inhomog = q["plan"], q["batched"], q["B"], q["n"], q["inhomog"]
+    samples = None
+    if eps is not None:
+        samples = plan.infer(*q["args"], q["pair_batched"], eps, keep_vjp=False, lengths=lengths)
     else:
         plan.launch(*q["args"], q["pair_batched"], keep_factor, lengths=lengths)
     if check:
@@ -876,15 +789,14 @@ def natural_lds_estep_general(natparam, node_params, plan=None, check=False, kee
         Ep = (plan.E_pair[:, 0], plan.E_pair[:, 1], plan.E_pair[:, 2], plan.ones_pair)
     En = (plan.E_node_diagxx, plan.E_node_x, plan.ones_BT)
     if lengths is not None:
-        live = (torch.arange(T, device=dev)[None, :] < plan._lengths[:, None]).to(torch.float64)
         Ep = Ep[:3] + (plan.pair_counts,)
-        En = (plan.E_node_diagxx, plan.E_node_x, live)
+        En = (plan.E_node_diagxx, plan.E_node_x, plan.live().to(torch.float64))
     Ei = (ExxT0, Ex0, plan.ones_B, plan.ones_B)
     lognorm = plan.lognorm
     if not batched:
         sq = lambda tup: tuple(x[0] for x in tup)
-        return lognorm[0], (sq(Ei), sq(Ep), sq(En))
-    return lognorm, (Ei, Ep, En)
+        return lognorm[0], (sq(Ei), sq(Ep), sq(En)), samples
+    return lognorm, (Ei, Ep, En), samples
 
 
 cython_natural_lds_estep_general = natural_lds_estep_general
@@ -928,7 +840,7 @@ def _model_from_messages(forward_messages, pair_params):
     parameters -- every call site of the reference (lds_inference.py:196-202, 232-237, 260-264) -- the smoother / sampler
     of this model IS the reference's smoother / sampler on the messages."""
     (Jp, hp), (Jf, hf) = forward_messages
-    dev = hf.device if isinstance(hf, torch.Tensor) and hf.is_cuda else torch.device("cuda")
+    dev = _find_device([hf])
     Jp, hp, Jf, hf = (_as_dev(x, dev) for x in (Jp, hp, Jf, hf))
     batched = hf.dim() == 3
     if not batched:
@@ -1048,9 +960,7 @@ def natural_lds_inference_general(natparam, node_params, num_samples=None, eps=N
         eps = eps if batched else eps[None]
     if plan.n <= _lib.LDS_MAX_N and eps.dim() == 4 and (eps.shape[2] <= 16 or lengths is not None):
         # ONE call (svae_lds_inference_f64 = the reference's composite, lds_inference.py:196-202)
-        lognorm, stats = natural_lds_estep_general(natparam, node_params, plan=plan, keep_factor=True, _infer_eps=eps,
-                                                   lengths=lengths)
-        samples = plan._infer_samples
+        lognorm, stats, samples = _estep(natparam, node_params, plan, keep_factor=True, eps=eps, lengths=lengths)
     else:
         lognorm, stats = natural_lds_estep_general(natparam, node_params, plan=plan, keep_factor=True)
         samples = plan.sample(eps)
@@ -1076,6 +986,25 @@ def reduce_stats(plan):
     Ep = (r[o:o + nn].reshape(n, n), r[o + nn:o + 2 * nn].reshape(n, n),
           r[o + 2 * nn:o + 3 * nn].reshape(n, n), float(B * (T - 1)))
     return Ei, Ep, r[o + 3 * nn]
+
+
+def require_same_launch(ctx, message="LDSEStepPlan was launched again before backward(): the hand-off workspace of this "
+                        "forward pass is gone (use one plan per live autograd graph, or call backward before the next forward)"):
+    """The plan of an autograd node, if its last launch is still the node's forward pass (ctx.epoch); else RuntimeError."""
+    if ctx.plan.epoch != ctx.epoch:
+        raise RuntimeError(message)
+    return ctx.plan
+
+
+def _backward_prologue(ctx, g_lognorm, g_samples, **relaunched):
+    """What the backward passes below begin with -> (plan, g_lognorm (zeros for None), (g_samples, eps, samples) for
+    plan.vjp: all None unless samples were drawn and their cotangent arrived)"""
+    plan = require_same_launch(ctx, **relaunched)
+    if g_lognorm is None:
+        g_lognorm = torch.zeros_like(plan.lognorm)
+    if not ctx.has_samples or g_samples is None:
+        return plan, g_lognorm, (None, None, None)
+    return plan, g_lognorm, (g_samples,) + tuple(ctx.saved_tensors)
 
 
 class _LDSInference(torch.autograd.Function):
@@ -1123,24 +1052,14 @@ class _LDSInference(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, g_lognorm, g_dxx, g_x, g_samples, g_init, g_pair):
-        plan = ctx.plan
-        if plan.epoch != ctx.epoch:
-            raise RuntimeError("LDSEStepPlan was launched again before backward(): the hand-off workspace of "
-                               "this forward pass is gone (use one plan per live autograd graph, or call "
-                               "backward before the next forward)")
-        eps, samples = ctx.saved_tensors
-        zero = lambda g, like: torch.zeros_like(like) if g is None else g
-        g_lognorm = zero(g_lognorm, plan.lognorm)
-        gs = g_samples if (ctx.has_samples and g_samples is not None) else None
+        plan, g_lognorm, sampled = _backward_prologue(ctx, g_lognorm, g_samples)
         if not plan.inhomog:
             g_init = g_pair = None
-        gJ, gh = plan.vjp(g_lognorm, g_dxx, g_x, gs, eps if gs is not None else None,
-                          samples if gs is not None else None, g_init, g_pair)
+        gJ, gh = plan.vjp(g_lognorm, g_dxx, g_x, *sampled, g_init, g_pair)
         gz = g_lognorm[:, None].expand(plan.B, plan.T).clone() if ctx.has_logZ else None
         if ctx.ragged:
             if gz is not None:      # (select: the cotangent of a sequence that does not exist is not propagated)
-                live = torch.arange(plan.T, device=plan.device)[None, :] < plan._lengths[:, None]
-                gz = torch.where(live, gz, torch.zeros_like(gz))
+                gz = torch.where(plan.live(), gz, torch.zeros_like(gz))
             return gJ, gh, gz, None, None, None, None, None
         return gJ, gh, gz, None, None, None, None
 
@@ -1158,18 +1077,10 @@ class _LDSInferenceParams(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, g_lognorm, g_dxx, g_x, g_samples, g_init, g_pair):
-        plan = ctx.plan
-        if plan.epoch != ctx.epoch:
-            raise RuntimeError("LDSEStepPlan was launched again before backward(): the hand-off workspace of "
-                               "this forward pass is gone (use one plan per live autograd graph, or call "
-                               "backward before the next forward)")
-        eps, samples = ctx.saved_tensors
-        g_lognorm = torch.zeros_like(plan.lognorm) if g_lognorm is None else g_lognorm
-        gs = g_samples if (ctx.has_samples and g_samples is not None) else None
+        plan, g_lognorm, sampled = _backward_prologue(ctx, g_lognorm, g_samples)
         if not plan.inhomog:
             g_init = g_pair = None
-        gJ, gh, gp = plan.vjp(g_lognorm, g_dxx, g_x, gs, eps if gs is not None else None,
-                              samples if gs is not None else None, g_init, g_pair, param_out=True)
+        gJ, gh, gp = plan.vjp(g_lognorm, g_dxx, g_x, *sampled, g_init, g_pair, param_out=True)
         gz = g_lognorm[:, None].expand(plan.B, plan.T).clone() if ctx.has_logZ else None
         need = ctx.needs_input_grad[6:]
         gp = tuple(g.reshape(shape) if want else None for g, shape, want in zip(gp, ctx.param_shapes, need))
@@ -1208,15 +1119,10 @@ class _LDSInferenceDense(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, g_lognorm, g_x, g_samples, g_init, g_pair):
-        plan = ctx.plan
-        if plan.epoch != ctx.epoch:
-            raise RuntimeError("the plan of this forward pass was launched again before backward()")
-        eps, samples = ctx.saved_tensors
-        g_lognorm = torch.zeros_like(plan.lognorm) if g_lognorm is None else g_lognorm
-        gs = g_samples if (ctx.has_samples and g_samples is not None) else None
+        plan, g_lognorm, sampled = _backward_prologue(
+            ctx, g_lognorm, g_samples, message="the plan of this forward pass was launched again before backward()")
         dense = torch.empty(plan.B, plan.T, plan.n, plan.n, dtype=torch.float64, device=plan.device)
-        _, gh = plan.vjp(g_lognorm, None, g_x, gs, eps if gs is not None else None, samples if gs is not None else None,
-                         g_init, g_pair, dense_out=dense)
+        _, gh = plan.vjp(g_lognorm, None, g_x, *sampled, g_init, g_pair, dense_out=dense)
         gJ = 0.5 * (dense + dense.transpose(-1, -2))
         gz = g_lognorm[:, None].expand(plan.B, plan.T).clone() if ctx.has_logZ else None
         return gJ, gh, gz, None, None
@@ -1251,25 +1157,10 @@ def _natparam_inference_differentiable(natparam, node_params, eps, plan, pair_st
     if n > _lib.LDS_MAX_N:
         raise ValueError("natparam_grad=True: latent dimension <= %d (n = %d)" % (_lib.LDS_MAX_N, n))
     dev = node_h.device
-
-    def keep(x):
-        if not isinstance(x, torch.Tensor):
-            x = torch.as_tensor(x, dtype=torch.float64)
-        return x.to(device=dev, dtype=torch.float64)
-    init_J, init_h = keep(init_params[0]), keep(init_params[1])
-    init_logZ = sum(keep(z).reshape(()) for z in init_params[2:]) if len(init_params) > 2 \
-        else torch.zeros((), dtype=torch.float64, device=dev)
-    init_logZ = init_logZ.reshape(1)
+    init_J, init_h, init_logZ = _canonical_init_params(init_params, dev, graph=True)
     if tuple(init_J.shape) != (n, n) or tuple(init_h.shape) != (n,):
         raise ValueError("init_params shapes do not match the node potentials")
-    J11, J12, J22 = (keep(x) for x in pair_params[:3])
-    logZ_pair = keep(pair_params[3]).reshape(-1)
-    inhomog, pair_batched = J11.dim() >= 3, J11.dim() == 4
-    want = {2: (n, n), 3: (T - 1, n, n), 4: (B, T - 1, n, n)}.get(J11.dim())
-    if want is None or any(tuple(x.shape) != want for x in (J11, J12, J22)):
-        raise ValueError("pair_params must be (n,n), (T-1,n,n) or (B,T-1,n,n)")
-    if logZ_pair.numel() != (1 if not inhomog else (B * (T - 1) if pair_batched else T - 1)):
-        raise ValueError("pair logZ must have one entry per pair block")
+    J11, J12, J22, logZ_pair, inhomog, pair_batched = _canonical_pair_params(pair_params, B, T, n, dev, graph=True)
     sum_pairs = bool(pair_stats_grad) and not inhomog
     if sum_pairs:
         J11, J12, J22 = (x.expand(max(T - 1, 0), n, n) for x in (J11, J12, J22))
@@ -1347,9 +1238,7 @@ def lds_inference_differentiable(natparam, node_params, eps=None, plan=None, pai
         raise ValueError("lds_inference_differentiable: node potentials J, h of shape (B,T,n), or dense J (B,T,n,n)")
     B, T, n = node_h.shape
     init_J, init_h, init_logZ = _canonical_init_params(init_params, dev)
-    J11, J12, J22 = (_as_dev(x, dev) for x in pair_params[:3])
-    logZ_pair = _as_dev(pair_params[3], dev).reshape(-1)
-    inhomog, pair_batched = J11.dim() >= 3, J11.dim() == 4
+    J11, J12, J22, logZ_pair, inhomog, pair_batched = _canonical_pair_params(pair_params, B, T, n, dev)
     sum_pairs = bool(pair_stats_grad) and not inhomog
     if sum_pairs:
         J11, J12, J22 = (x.expand(max(T - 1, 0), n, n).contiguous() for x in (J11, J12, J22))

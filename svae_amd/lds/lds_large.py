@@ -31,6 +31,7 @@ Everything here is float64 on the GPU; there is no CPU path and no library (rocB
 import torch
 
 from .. import _lib
+from .lds_inference import require_same_launch
 
 MAX_S = 16       # samples per sequence per kernel launch (csrc/lds_vjp_tile.hip: TV_MAX_S)
 PHASE2_RANGES = 8        # ranges of steps phase 2 and the Cholesky adjoint are split into (see vjp_from_handoff_hip)
@@ -102,7 +103,7 @@ def start_phase0(plan, J12, pair_batched, S):
     nws = int(lib.svae_lds_tile_vjp_workspace_doubles(max(B, 1), T, n, S))
     # the VJP workspace belongs to the plan (one live autograd graph per plan): no allocation per step, and no second
     # block while the allocator waits for the helper streams of the previous step to release the first
-    ws = getattr(plan, "_vjp_ws", None)
+    ws = plan._vjp_ws
     if ws is None or ws.numel() < nws:
         ws = plan._vjp_ws = torch.empty(nws, **f64)
     dummy = plan.lognorm                      # (phase 0 reads none of the cotangents; the entry point wants the pointers)
@@ -159,7 +160,7 @@ def vjp_from_handoff_hip(plan, J12, pair_batched, ex, g_lognorm, g_dxx, g_x, sam
         ws = phase0[0]
         torch.cuda.current_stream(dev).wait_event(phase0[1])
     else:
-        ws, phase0 = getattr(plan, "_vjp_ws", None), None
+        ws, phase0 = plan._vjp_ws, None
         if ws is None or ws.numel() < nws:
             ws = plan._vjp_ws = torch.empty(nws, **f64)
     gJ, gh = torch.empty(B, T, n, **f64), torch.empty(B, T, n, **f64)
@@ -258,11 +259,9 @@ class LDSInferenceLarge(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g_lognorm, g_dxx, g_x, g_samples, g_init, g_pair):
         eps, samples = ctx.saved_tensors
-        plan = ctx.plan
+        plan = require_same_launch(ctx, "LDSEStepPlan was launched again before backward(): the hand-off workspace of "
+                                        "this forward pass is gone (use one plan per live autograd graph)")
         B, T = plan.B, plan.T
-        if plan.epoch != ctx.epoch:
-            raise RuntimeError("LDSEStepPlan was launched again before backward(): the hand-off workspace of "
-                               "this forward pass is gone (use one plan per live autograd graph)")
         gl = torch.zeros_like(plan.lognorm) if g_lognorm is None else g_lognorm
         gs = g_samples if (ctx.has_eps and g_samples is not None) else None
         gJ, gh = vjp_from_handoff_hip(plan, ctx.J12, ctx.pair_batched, ctx.ex, gl, g_dxx, g_x,

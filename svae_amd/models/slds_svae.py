@@ -40,8 +40,7 @@ from .. import _lib
 from ..distributions import expfam
 from ..parallel import allreduce_nested
 from ..hmm.hmm_inference import hmm_estep, hmm_logZ_differentiable, hmm_viterbi
-from ..lds.lds_inference import (LDSEStepPlan, lds_inference_differentiable, natural_lds_estep_general,
-                                     natural_lds_sample)
+from ..lds.lds_inference import LDSEStepPlan, _estep, lds_inference_differentiable, natural_lds_sample
 
 
 _STATUS = {}     # (path name, device) -> (1,) int32 status word, PERSISTENT per device: every call of the path ORs into it
@@ -718,7 +717,7 @@ def _lds_estep_batched_init(plan, lds_init, lds_pair, node, keep_factor=False, r
     potential is passed through the batched pair-parameter path: J11 of step 0 absorbs J0, and h0 is
     added to node_h[:,0]; log-normaliser constants are added back on the host.
     eps (B,T,S,n): E-step + backward sampler in ONE call (svae_lds_inference_f64, forward values only: lean records for
-    batches above 1024 sequences); the samples are left in plan._infer_samples.  inplace: J0 is added INTO the caller's
+    batches above 1024 sequences) -> (lognorm, stats, samples) then.  inplace: J0 is added INTO the caller's
     J11[:, 0] (the caller owns the per-step parameters and will not reuse them: saves a copy of (B,T-1,n,n))."""
     J0, h0, a0, b0 = lds_init                      # (B,n,n), (B,n), (B), (B)
     J11, J12, J22, lz = lds_pair                   # (B,T-1,...)
@@ -733,9 +732,9 @@ def _lds_estep_batched_init(plan, lds_init, lds_pair, node, keep_factor=False, r
         J11[:, 0] += J0                            # -1/2 x0' J0 x0 multiplies the same variable as J11[0]
         natparam = ((torch.zeros(n, n, dtype=torch.float64, device=dev), torch.zeros(n, dtype=torch.float64, device=dev), zero),
                     (J11.contiguous(), J12.contiguous(), J22.contiguous(), lz.contiguous()))
-        lognorm, stats = natural_lds_estep_general(natparam, (nJ, nh) + tuple(node[2:]), plan=plan,
-                                                   keep_factor=keep_factor, _infer_eps=eps)
-        return (lognorm + a0 if reference_compat else lognorm + a0 + b0), stats
+        lognorm, stats, samples = _estep(natparam, (nJ, nh) + tuple(node[2:]), plan, keep_factor=keep_factor, eps=eps)
+        lognorm = lognorm + a0 if reference_compat else lognorm + a0 + b0
+        return (lognorm, stats) if eps is None else (lognorm, stats, samples)
     raise NotImplementedError("SLDS needs T > 1")
 
 
@@ -806,9 +805,8 @@ def run_inference(prior_natparam, global_natparam, nn_potentials, num_samples, i
     elif n <= _lib.LDS_MAX_N and S <= 16:
         # final E-step + sampler in ONE call on the per-step parameters of the converged mean field (lean records above
         # 1024 sequences: csrc/lds_lean_estep.hpp, INH), J0 added into the mixed J11 in place
-        lognorm, (Ei, Ep, En) = _lds_estep_batched_init(plan, lds_init, lds_pair, node, keep_factor=True,
-                                                        reference_compat=reference_compat, eps=eps, inplace=True)
-        samples = plan._infer_samples
+        lognorm, (Ei, Ep, En), samples = _lds_estep_batched_init(plan, lds_init, lds_pair, node, keep_factor=True,
+                                                                 reference_compat=reference_compat, eps=eps, inplace=True)
     else:
         lognorm, (Ei, Ep, En) = _lds_estep_batched_init(plan, lds_init, lds_pair, node, keep_factor=True,
                                                         reference_compat=reference_compat)
@@ -877,9 +875,8 @@ def run_inference_withlabels(prior_natparam, global_natparam, potentials_and_lab
         Ei = (plan.E_init[:, :n * n].reshape(B, n, n), plan.E_init[:, n * n:])
         En = (plan.E_node_diagxx, plan.E_node_x)
     elif n <= _lib.LDS_MAX_N and S <= 16:
-        lognorm, (Ei, Ep, En) = _lds_estep_batched_init(plan, lds_init, lds_pair, node, keep_factor=True,
-                                                        reference_compat=reference_compat, eps=eps)
-        samples = plan._infer_samples
+        lognorm, (Ei, Ep, En), samples = _lds_estep_batched_init(plan, lds_init, lds_pair, node, keep_factor=True,
+                                                                 reference_compat=reference_compat, eps=eps)
     else:
         lognorm, (Ei, Ep, En) = _lds_estep_batched_init(plan, lds_init, lds_pair, node, keep_factor=True,
                                                         reference_compat=reference_compat)
