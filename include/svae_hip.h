@@ -25,7 +25,7 @@
 extern "C" {
 #endif
 
-#define SVAE_HIP_ABI_VERSION 15   /* 15: (+ svae_lds_ragged_perstep_workspace_bytes, svae_lds_ragged_perstep_estep_f64, svae_lds_ragged_perstep_inference_f64: per-sequence lengths with per-step pair parameters and a per-sequence init potential, added without a new number -- additions only) (+ svae_hmm_ragged_estep_f64, svae_hmm_ragged_viterbi_f64: per-sequence lengths for the HMM E-step and Viterbi, added without a new number -- additions only, compatible with every caller of 15) (+ svae_lds_estep_vjp_params_f64, svae_lds_param_vjp_workspace_bytes: cotangents of the init / pair natural parameters, added without a new number -- additions only) + svae_gmm_wide_mw_workspace_bytes, svae_gmm_wide_mw_begin, svae_gmm_wide_mw_step_f64, svae_gmm_wide_sample_f64, svae_gmm_wide_local_vjp_f64, svae_gmm_wide_global_step_f64 (the GMM local step for N <= 16; additions only), svae_lds_filter_vjp_f64, svae_lds_smoother_vjp_f64 (+ svae_lds_smoother_vjp_workspace_bytes), svae_lds_sample_vjp_f64 (the reference's three reverse-mode primitives on caller-held forward messages); 14: + svae_lds_estep_vjp_dense_f64 (cotangent of dense node potentials), svae_hmm_* up to K = 64, svae_lds_inference_f64 (E-step + sampler in one call; lean per-step records for large homogeneous batches), svae_lds_inference_is_lean, SVAE_OPT_LEAN_ON / _OFF / SVAE_OPT_INFER_RECORDS; 13: + svae_slds_pair_contract_f64 (the two contractions of the SLDS final pass over the per-step pair statistics in one pass); 12: svae_gmm_global_step_f64 writes kl[0..1] (as spelled | as shipped), svae_ipc_allreduce_f64 takes the mailbox stride and never writes `out` on a timeout, + svae_slds_lds_meanfield options; 11: + svae_lds_global_step_multi_f64 (K parameter sets in one launch: the SLDS global -> local maps), svae_lds_diag_sample_f64 (filter + sampler of an all-diagonal LDS: the SLDS initial path); 10: + svae_ipc_allreduce_f64 / svae_ipc_mailbox_bytes, svae_gmm_sample_f64, svae_gmm_local_vjp_f64, svae_gmm_global_step_f64 (the differentiable tail and the global side of the GMM local step); 9: keep bit SVAE_KEEP_SIGMA of svae_lds_estep_f64 (16 <= n <= 64) + svae_lds_tile_sigma_offset_bytes; 8: step ranges (t_begin, t_end) in svae_lds_tile_vjp_f64 / svae_lds_tile_noise_f64, SVAE_OPT_TILE_FORWARD / _BACKWARD; 7: + svae_slds_path_nodeparams_f64, svae_slds_mix_pair_natparam_f64; 6: per-call `options` word replaces the process-global svae_lds_set_* selectors (re-entrant library), + svae_slds_hmm_meanfield_f64, svae_slds_sweep_glue_f64, g_E_pair in svae_lds_tile_vjp_f64; 5: + svae_lds_set_prod_max_b; 4: + svae_slds_lds_meanfield_f64, svae_gmm_mw_*, svae_lds_global_step_f64, svae_lds_natgrad_f64, svae_lds_tile_vjp_f64; 2: + svae_lds_workspace_bytes_ex, svae_lds_estep_vjp_ex_f64, svae_hmm_*, tiled path (n <= 64) */
+#define SVAE_HIP_ABI_VERSION 15   /* 15: (+ svae_hmm_sample_workspace_bytes, svae_hmm_sample_f64, svae_hmm_ragged_sample_f64: HMM posterior sampling, uniform and with per-sequence lengths, added without a new number -- additions only) (+ svae_lds_ragged_perstep_workspace_bytes, svae_lds_ragged_perstep_estep_f64, svae_lds_ragged_perstep_inference_f64: per-sequence lengths with per-step pair parameters and a per-sequence init potential, added without a new number -- additions only) (+ svae_hmm_ragged_estep_f64, svae_hmm_ragged_viterbi_f64: per-sequence lengths for the HMM E-step and Viterbi, added without a new number -- additions only, compatible with every caller of 15) (+ svae_lds_estep_vjp_params_f64, svae_lds_param_vjp_workspace_bytes: cotangents of the init / pair natural parameters, added without a new number -- additions only) + svae_gmm_wide_mw_workspace_bytes, svae_gmm_wide_mw_begin, svae_gmm_wide_mw_step_f64, svae_gmm_wide_sample_f64, svae_gmm_wide_local_vjp_f64, svae_gmm_wide_global_step_f64 (the GMM local step for N <= 16; additions only), svae_lds_filter_vjp_f64, svae_lds_smoother_vjp_f64 (+ svae_lds_smoother_vjp_workspace_bytes), svae_lds_sample_vjp_f64 (the reference's three reverse-mode primitives on caller-held forward messages); 14: + svae_lds_estep_vjp_dense_f64 (cotangent of dense node potentials), svae_hmm_* up to K = 64, svae_lds_inference_f64 (E-step + sampler in one call; lean per-step records for large homogeneous batches), svae_lds_inference_is_lean, SVAE_OPT_LEAN_ON / _OFF / SVAE_OPT_INFER_RECORDS; 13: + svae_slds_pair_contract_f64 (the two contractions of the SLDS final pass over the per-step pair statistics in one pass); 12: svae_gmm_global_step_f64 writes kl[0..1] (as spelled | as shipped), svae_ipc_allreduce_f64 takes the mailbox stride and never writes `out` on a timeout, + svae_slds_lds_meanfield options; 11: + svae_lds_global_step_multi_f64 (K parameter sets in one launch: the SLDS global -> local maps), svae_lds_diag_sample_f64 (filter + sampler of an all-diagonal LDS: the SLDS initial path); 10: + svae_ipc_allreduce_f64 / svae_ipc_mailbox_bytes, svae_gmm_sample_f64, svae_gmm_local_vjp_f64, svae_gmm_global_step_f64 (the differentiable tail and the global side of the GMM local step); 9: keep bit SVAE_KEEP_SIGMA of svae_lds_estep_f64 (16 <= n <= 64) + svae_lds_tile_sigma_offset_bytes; 8: step ranges (t_begin, t_end) in svae_lds_tile_vjp_f64 / svae_lds_tile_noise_f64, SVAE_OPT_TILE_FORWARD / _BACKWARD; 7: + svae_slds_path_nodeparams_f64, svae_slds_mix_pair_natparam_f64; 6: per-call `options` word replaces the process-global svae_lds_set_* selectors (re-entrant library), + svae_slds_hmm_meanfield_f64, svae_slds_sweep_glue_f64, g_E_pair in svae_lds_tile_vjp_f64; 5: + svae_lds_set_prod_max_b; 4: + svae_slds_lds_meanfield_f64, svae_gmm_mw_*, svae_lds_global_step_f64, svae_lds_natgrad_f64, svae_lds_tile_vjp_f64; 2: + svae_lds_workspace_bytes_ex, svae_lds_estep_vjp_ex_f64, svae_hmm_*, tiled path (n <= 64) */
 #define SVAE_HMM_MAX_K 64   /* svae_hmm_estep_f64 / svae_slds_hmm_meanfield_f64: K <= 16 one DPP row per sequence; 17 <= K <= 64 one wavefront per sequence (round 6) */
 #define SVAE_LDS_MAX_N 15   /* register/DPP path: one 16-lane row per sequence, n+1 <= 16 */
 #define SVAE_LDS_TILE_MAX_N 64   /* 16 <= n <= 64: LDS-tiled MFMA path (keep: SVAE_KEEP_SIGMA or 0) */
@@ -542,6 +542,58 @@ int svae_hmm_ragged_viterbi_f64(int B, int T, int K, int pair_batched,
                                 const int32_t* lengths,
                                 int32_t* states, double* score /* or NULL */,
                                 int32_t* info, void* workspace, size_t ws_bytes, void* stream);
+
+/* Batched HMM posterior sampling: S state paths per chain, z_{0:T-1} ~ p(z | potentials), by forward filtering and
+ * backward sampling, on the LOG potentials svae_hmm_viterbi_f64 takes (entries may be -inf), K <= SVAE_HMM_MAX_K --
+ * csrc/hmm_sample.hip.  Additions to ABI 15 (no new number).  [pyhsmm's message interface, to which the reference
+ * delegates its HMM work, has the operation; the arithmetic is defined HERE.]  The caller supplies the randomness.
+ * For sequence b of length L (= T in the uniform call) and sample s:
+ *  Filtered distributions  a_t[k] = p(z_t = k | node_{0..t}), t < L: the scaled forward filter of the E-step kernels
+ *    (per-step max-shift of the node potentials, renormalisation to sum 1, log Z accumulated as mantissa/exponent pairs);
+ *    a step whose normaliser falls below 1e-200 is redone in log space.
+ *  Weights  t = L-1: w[k] = a_{L-1}[k];  t < L-1: w[k] = a_t[k] exp(pair[k][z_{t+1}] - M), M = the matrix' largest entry.
+ *    If sum_k w[k] < 1e-200 the weights of that draw are recomputed in log space:
+ *    w[k] = exp(log a_t[k] + pair[k][z_{t+1}] - max_k(log a_t[k] + pair[k][z_{t+1}])).
+ *  Selection  C[k] = w[0] + .. + w[k], fp64 additions IN INDEX ORDER (both kernel mappings implement exactly this order:
+ *    K <= 16 as K broadcast multiply-adds by 1.0 or 0.0, 17 <= K <= 64 as KP sequential adds of an LDS line that holds KP
+ *    zeros and then w), so C is non-decreasing and rises only where w[k] > 0.  thr = clamp(u[b,s,t], 0, 1) C[K-1]; a NaN u
+ *    counts as 0.  z_t = the number of k with C[k] <= thr; if that number is K (the product rounded up to the total),
+ *    z_t = the lowest k with C[k] = C[K-1].  [One test: z_t = #{k : C[k] <= thr and C[k] < C[K-1]}.]
+ *    Consequence: on a chain with finite log Z a drawn state always has positive weight -- a forbidden (-inf) transition
+ *    or observation is never sampled; u = 0 draws the lowest allowed state, u = 1 the highest.
+ *  Degenerate input: a chain with logZ = -inf, or NaN potentials, gives unspecified labels in 0..K-1: no fault, and no
+ *    effect on any other sequence (every data-dependent index is masked into range before it addresses LDS or memory).
+ *  in : init_params (K); pair_params (K,K) [j][k] = j -> k, or (B,K,K) if pair_batched; node_params (B,T,K);
+ *       S >= 1 samples per sequence; u (B,S,T) fp64 uniforms
+ *  out: states (B,S,T) int32, sample-major: states[:, s] is a (B,T) label array of the form svae_hmm_viterbi_f64 returns;
+ *       logZ (B) or NULL
+ *  workspace: svae_hmm_sample_workspace_bytes(B,T,K) = B T KP doubles (the filtered distributions, padding lanes 0;
+ *       KP = 16, 32 or 64 for K <= 16, <= 32, <= 64; no flags are needed: a draw decides its log-space redo from its own
+ *       total); 0 for B <= 0, T <= 0 or K outside 1..SVAE_HMM_MAX_K.  16-byte aligned.
+ *  Ragged form (svae_hmm_ragged_sample_f64, lengths (B) device int32), the conventions of the other ragged entries:
+ *    results up to L are those of the sequence cut at L; states[b, :, t >= L] = -1; node_params[b, L:] and u[b, :, L:]
+ *    are never read and may be NaN; no sequence sees another's length or data; a length outside 1..T is clamped to [1, T]
+ *    for addressing and ORs 1 into the device word `info`.
+ *  Returns 0, or (decided on the host before any HIP call, the first failing check)
+ *   both   : -1 B < 0, -2 T < 1, -3 K outside 1..SVAE_HMM_MAX_K, -4 pair_batched not 0 or 1, -5 init_params NULL,
+ *            -6 pair_params NULL, [B = 0 returns 0 here], -7 node_params NULL;
+ *   uniform: -8 S < 1, -9 u NULL, -10 states NULL, -11 workspace NULL, -12 ws_bytes too small, -13 workspace not
+ *            16-byte aligned;
+ *   ragged : -8 lengths NULL, -9 S < 1, -10 u NULL, -11 states NULL, -12 info NULL, -13 workspace NULL, -14 ws_bytes too
+ *            small, -15 workspace not 16-byte aligned;
+ *  -1000 launch error.  Two launches (filter, draw), asynchronous on `stream`, no internal allocation, safe under graph
+ *  capture.  B S T must be below 2^31. */
+size_t svae_hmm_sample_workspace_bytes(int B, int T, int K);
+int svae_hmm_sample_f64(int B, int T, int K, int S, int pair_batched,
+                        const double* init_params, const double* pair_params,
+                        const double* node_params, const double* u,
+                        int32_t* states, double* logZ /* or NULL */,
+                        void* workspace, size_t ws_bytes, void* stream);
+int svae_hmm_ragged_sample_f64(int B, int T, int K, int S, int pair_batched,
+                               const double* init_params, const double* pair_params,
+                               const double* node_params, const int32_t* lengths, const double* u,
+                               int32_t* states, double* logZ /* or NULL */,
+                               int32_t* info, void* workspace, size_t ws_bytes, void* stream);
 
 /* HMM step of the SLDS coordinate ascent on the rows `seq_index` lists (B of `rows`; NULL: rows 0..B-1; negative
  * entries = unused slots, which must follow the live ones -- the list svae_slds_sweep_glue_f64 writes):

@@ -3,6 +3,7 @@
   hmm_estep(natparam) -> (log_normalizer, (E_init, E_trans, E_states))      (:21-41)
   hmm_logZ(natparam)  -> log_normalizer                                      (:12-17, pyx:93-121)
   hmm_viterbi(natparam) -> most probable state path (and its score)          (:54-63; csrc/hmm_viterbi.hip)
+  hmm_sample(natparam, num_samples) -> state paths drawn from the posterior  (csrc/hmm_sample.hip)
 
 natparam = (init_params (K), pair_params (K,K), node_params (T,K)) are LOG potentials, as in the
 reference.  New: node_params may be (B,T,K) (and pair_params (B,K,K)); outputs then carry a leading
@@ -12,7 +13,8 @@ Per-sequence lengths: every function takes lengths= (B,) integers with (B,T,K) n
 sequence b occupying steps 0 .. lengths[b]-1.  logZ, E_init, E_trans, E_states[b, :L], states[b, :L] and the score are
 those of the sequence cut to its length; E_states[b, L:] is exactly 0, states[b, L:] is -1, and nothing stored at
 t >= L is read (it may be NaN).  A length outside 1..T is device data: clamped, and recorded in a persistent status
-word that check=True (or check_lengths_status) reads (svae_hmm_ragged_estep_f64 / svae_hmm_ragged_viterbi_f64).
+word that check=True (or check_lengths_status) reads (svae_hmm_ragged_estep_f64 / svae_hmm_ragged_viterbi_f64 /
+svae_hmm_ragged_sample_f64; sampled labels are (B,S,T) with states[b, :, L:] = -1, and u[b, :, L:] is not read either).
 """
 import numpy as np
 import torch
@@ -168,6 +170,74 @@ def hmm_viterbi(natparam, workspace=None, return_score=False, lengths=None, chec
         states = states[0]
         score = score[0] if return_score else None
     return (states, score) if return_score else states
+
+
+def hmm_sample(natparam, num_samples=1, u=None, generator=None, workspace=None, return_logZ=False, lengths=None,
+               check=False):
+    """State paths drawn from the posterior p(z | potentials) under the LOG potentials hmm_viterbi takes (entries may be
+    -inf), by forward filtering and backward sampling: labels torch.int32 (S,T), or (B,S,T) when node_params is (B,T,K),
+    S = num_samples; labels[:, s] is a (B,T) label array of the form hmm_viterbi returns.  With return_logZ also the
+    log-normaliser the filter computes (0-d, or (B)).  The arithmetic is defined in include/svae_hip.h
+    (svae_hmm_sample_f64): a state with a forbidden (-inf) transition or observation is never drawn.
+    u: the uniforms, (B,S,T) ((S,T) for the unbatched call); None draws torch.rand fp64 on the device with `generator`.
+    workspace: any contiguous device tensor of at least svae_hmm_sample_workspace_bytes(B,T,K) bytes.
+    lengths: (B,) integers, see the module docstring -- labels from a sequence's length on are -1."""
+    init_params, pair_params, node_params = natparam
+    lens = None if lengths is None else _lengths_arg(lengths, node_params)
+    dev = node_params.device if isinstance(node_params, torch.Tensor) and node_params.is_cuda \
+        else torch.device("cuda", torch.cuda.current_device())
+    init_params, pair_params, node = (_dev64(x, dev) for x in (init_params, pair_params, node_params))
+    batched = node.dim() == 3
+    if node.dim() not in (2, 3):
+        raise ValueError("node_params must be (T,K) or (B,T,K)")
+    if not batched:
+        node = node[None]
+    B, T, K = node.shape
+    if not (1 <= K <= HMM_MAX_K):
+        raise ValueError("number of states K=%d outside 1..%d" % (K, HMM_MAX_K))
+    if T < 1:
+        raise ValueError("node_params has no steps")
+    pair_batched = pair_params.dim() == 3
+    if tuple(init_params.shape) != (K,) or tuple(pair_params.shape[-2:]) != (K, K) or pair_params.dim() not in (2, 3) or \
+            (pair_batched and pair_params.shape[0] != B):
+        raise ValueError("init/pair parameter shapes do not match the node potentials")
+    S = int(num_samples)
+    if S != num_samples or S < 1:
+        raise ValueError("num_samples must be an integer >= 1, got %r" % (num_samples,))
+    if B * S * T >= 2 ** 31:
+        raise ValueError("B * num_samples * T = %d is not below 2^31" % (B * S * T))
+    if u is None:
+        u = torch.rand(B, S, T, dtype=torch.float64, device=dev, generator=generator)
+    else:
+        ushape = tuple(u.shape) if hasattr(u, "shape") else np.shape(u)
+        if ushape != ((B, S, T) if batched else (S, T)):
+            raise ValueError("u must have shape %r, got %r" % ((B, S, T) if batched else (S, T), ushape))
+        u = _dev64(u, dev).reshape(B, S, T)
+    lib = _lib.load()
+    if workspace is None:
+        wsb = int(lib.svae_hmm_sample_workspace_bytes(max(B, 1), T, K))
+        ws = torch.empty(wsb // 8, dtype=torch.float64, device=dev)
+    else:
+        ws = workspace
+        wsb = ws.numel() * ws.element_size()
+    states = torch.empty(B, S, T, dtype=torch.int32, device=dev)
+    logZ = torch.empty(B, dtype=torch.float64, device=dev) if return_logZ else None
+    p = _lib.ptr
+    if lens is not None:
+        rc = lib.svae_hmm_ragged_sample_f64(B, T, K, S, int(pair_batched), p(init_params), p(pair_params), p(node),
+                                            p(lens), p(u), p(states), p(logZ), p(_status_word(dev)), p(ws), wsb,
+                                            _lib.current_stream(dev))
+        _lib.check(rc, "svae_hmm_ragged_sample_f64")
+        if check:
+            check_lengths_status(dev)
+        return (states, logZ) if return_logZ else states
+    rc = lib.svae_hmm_sample_f64(B, T, K, S, int(pair_batched), p(init_params), p(pair_params), p(node), p(u),
+                                 p(states), p(logZ), p(ws), wsb, _lib.current_stream(dev))
+    _lib.check(rc, "svae_hmm_sample_f64")
+    if not batched:
+        states = states[0]
+        logZ = logZ[0] if return_logZ else None
+    return (states, logZ) if return_logZ else states
 
 
 class _HMMLogZ(torch.autograd.Function):

@@ -9,6 +9,7 @@
   run_inference                                   (:289-310)
   run_inference_withlabels(_differentiable)       (:313-334) the same with the discrete states given
   viterbi_labels                                  the segmentation: hmm_viterbi (svae_hmm_viterbi_f64) on the converged HMM factor
+  sample_labels                                   segmentations drawn from it: hmm_sample (svae_hmm_sample_f64) on the same factor
 
 The reference module is stale as shipped (imports svae.lds.niw/mniw, svae.hmm.dirichlet, lds_svae,
 none of which exist; hmm_estep needs the un-vendored pyhsmm).  Formulas are taken from it with
@@ -39,7 +40,7 @@ import torch
 from .. import _lib
 from ..distributions import expfam
 from ..parallel import allreduce_nested
-from ..hmm.hmm_inference import hmm_estep, hmm_logZ_differentiable, hmm_viterbi
+from ..hmm.hmm_inference import hmm_estep, hmm_logZ_differentiable, hmm_sample, hmm_viterbi
 from ..lds.lds_inference import LDSEStepPlan, _estep, lds_inference_differentiable, natural_lds_sample
 
 
@@ -845,6 +846,25 @@ def viterbi_labels(global_natparam, nn_potentials, init_eps=None, generator=None
     _, (hmm_nat, _), _, _ = optimize_local_meanfield(global_natparam, node, init_eps, tol, pair_stats=False,
                                                      reference_compat=reference_compat, lengths=lens)
     return hmm_viterbi(hmm_nat, return_score=True, lengths=lens)
+
+
+def sample_labels(global_natparam, nn_potentials, num_samples=1, init_eps=None, u=None, generator=None, tol=1e-2,
+                  reference_compat=True, lengths=None):
+    """Segmentations DRAWN from the converged discrete factor, where viterbi_labels returns its single most probable one:
+    the local mean field is optimised as in run_inference, then num_samples discrete paths are drawn from the converged
+    HMM factor with hmm_sample (forward filter, backward draw; u (B,S,T): its uniforms, None draws them with `generator`).
+    -> labels (B,S,T) int32; labels[:, s] is what run_inference_withlabels consumes.
+    lengths (B,): per-sequence lengths (module docstring); labels[b, :, L:] = -1, which
+    run_inference_withlabels(lengths=) takes as they are."""
+    dev = nn_potentials[1].device
+    lens = None if lengths is None else _slds_lengths(lengths, global_natparam, nn_potentials, False, "sample_labels")
+    node = tuple(_dev64(x, dev) for x in nn_potentials)
+    B, T, n = node[1].shape
+    if init_eps is None:
+        init_eps = torch.randn(B, T, 1, n, dtype=torch.float64, device=dev, generator=generator)
+    _, (hmm_nat, _), _, _ = optimize_local_meanfield(global_natparam, node, init_eps, tol, pair_stats=False,
+                                                     reference_compat=reference_compat, lengths=lens)
+    return hmm_sample(hmm_nat, num_samples=num_samples, u=u, generator=generator, lengths=lens)
 
 
 def run_inference_withlabels(prior_natparam, global_natparam, potentials_and_labels, num_samples, eps=None,
