@@ -480,7 +480,20 @@ int svae_lds_estep_vjp_params_f64(int B, int T, int n, int S, int inhomog, int p
  *       j -> k, or (B,K,K) if pair_batched; node_params (B,T,K) log node potentials
  *  out: logZ (B); E_init (B,K) = E[z_0]; E_trans (B,K,K) = sum_t E[z_t = j, z_{t+1} = k];
  *       E_states (B,T,K) = E[z_t]
- *  workspace: svae_hmm_workspace_bytes(B,T,K)
+ *  workspace: svae_hmm_workspace_bytes(B,T,K) = B T R doubles, R = 50 for K <= 16, KP + 2 above (KP = 32 or 64 padded
+ *       states); 0 for B <= 0, T <= 0 or K outside 1..SVAE_HMM_MAX_K.
+ *  Range: the recursions are SCALED (potentials shifted by their maximum and exponentiated, messages renormalised), and a
+ *  scaled step loses whatever falls below 2.3e-308 of its scale -- for good: a lost component is never rebuilt.  A
+ *  sequence keeps the scaled result only while every state's component of every step's unnormalised message stays >= 1e-250
+ *  (and every normaliser above 1e-200): what a step drops is then 1e-50 below the positive sum it is dropped from.  Every
+ *  other sequence is RECOMPUTED IN LOG SPACE by a second launch (the reference's own arithmetic, K log-sum-exps per step;
+ *  by its operation count -- K exp and a log per state and step where the scaled step has K multiply-adds -- roughly 10x a
+ *  scaled sequence's time, an estimate: no workload with flagged sequences has been timed; the launch costs a flag read
+ *  per sequence otherwise), so for finite or -inf potentials every sequence WITH A PATH OF FINITE SCORE has the log-space
+ *  result to rounding.  A sequence with no such path (log Z = -inf) is outside the contract: the log-space pass divides
+ *  every step's marginals by their own sum, and its outputs for that sequence are NaN; no other sequence is affected.  A state forbidden by a -1e4 or -inf potential sends its
+ *  sequence that way.  Which did is recorded: after the call, double R - 1 of a sequence's FIRST workspace record (entry
+ *  [b T R + R - 1]) is 1.0 if sequence b was recomputed, else 0.0.
  */
 size_t svae_hmm_workspace_bytes(int B, int T, int K);
 int svae_hmm_estep_f64(int B, int T, int K, int pair_batched,
@@ -517,8 +530,9 @@ int svae_hmm_viterbi_f64(int B, int T, int K, int pair_batched,
  * 0 .. L_b - 1 of its (T, K) block, L_b = lengths[b] (device int32).  Additions to ABI 15 (no new number).
  *  E-step : logZ[b], E_init[b], E_trans[b] and E_states[b, :L] are those of the sequence cut to L steps (E_trans sums the
  *           sequence's own L - 1 transitions: exactly 0 for L = 1; E_init = the marginal at t = 0); E_states[b, t >= L] is
- *           exactly 0.0.  K <= 16: the one-directional DPP-row kernel, rows of different lengths under per-row masks, log-space
- *           steps inline (one launch); 17 <= K <= 64: the wide kernel and its log-space redo launch, loops to L.
+ *           exactly 0.0.  K <= 16: the one-directional DPP-row kernel, rows of different lengths under per-row masks;
+ *           17 <= K <= 64: the wide kernel, loops to L; both with the log-space launch of the uniform call behind them
+ *           (the range criterion and the REDO word of svae_hmm_estep_f64, over the sequence's own L steps).
  *  Viterbi: states[b, :L] and score[b] are those of the cut sequence under the exact arithmetic defined above;
  *           states[b, t >= L] = -1.
  *  Nothing stored at t >= L is ever read: node potentials there may be NaN or +-inf.  No sequence sees another's length or
@@ -550,7 +564,10 @@ int svae_hmm_ragged_viterbi_f64(int B, int T, int K, int pair_batched,
  * For sequence b of length L (= T in the uniform call) and sample s:
  *  Filtered distributions  a_t[k] = p(z_t = k | node_{0..t}), t < L: the scaled forward filter of the E-step kernels
  *    (per-step max-shift of the node potentials, renormalisation to sum 1, log Z accumulated as mantissa/exponent pairs);
- *    a step whose normaliser falls below 1e-200 is redone in log space.
+ *    a step whose normaliser falls below 1e-200 is redone in log space.  (The normaliser is the ONLY criterion here, and
+ *    the other steps stay scaled: a component below 1e-308 of a step's scale -- behind a transition more than 745 nats
+ *    below the matrix' maximum, say -- is lost to the draws although logZ stays finite.  The E-step's criterion and its
+ *    all-log-space pass, above, have not been carried over to the sampler.)
  *  Weights  t = L-1: w[k] = a_{L-1}[k];  t < L-1: w[k] = a_t[k] exp(pair[k][z_{t+1}] - M), M = the matrix' largest entry.
  *    If sum_k w[k] < 1e-200 the weights of that draw are recomputed in log space:
  *    w[k] = exp(log a_t[k] + pair[k][z_{t+1}] - max_k(log a_t[k] + pair[k][z_{t+1}])).

@@ -27,7 +27,6 @@ struct HmmArgs {
   const double* __restrict__ cinit;       // (K)
   const double* __restrict__ lz;          // (K)
   double* __restrict__ node_out;          // (rows,T,K) or nullptr: the node potentials used
-  int redo_only;                          // hmm_estep_kernel behind hmm_estep2_kernel: only wavefronts with a flagged sequence run
 };
 // per-sequence lengths (svae_hmm_ragged_estep_f64): sequence b occupies steps 0 .. lengths[b]-1 of its (T, K) block; the
 // arrays and the workspace records keep stride T.  A separate type: the uniform kernels' arguments stay what they are.
@@ -35,6 +34,16 @@ struct HmmRaggedArgs : HmmArgs {
   const int32_t* __restrict__ lengths;    // (B) device data, clamped to [1, T] for addressing and trip counts
   int32_t* __restrict__ info;             // status word: bit 0 = a length outside 1..T
 };
+// DPP-row kernels (K <= 16, hmm_estep.hip): HMM_WS doubles per (sequence, step); entry HMM_REDO of the sequence's FIRST
+// record is its REDO flag (1.0: the scaled pass left its range, the log-space launch behind it recomputed the sequence).
+constexpr int HMM_WS = 50;
+constexpr int HMM_REDO = 49;
+// Range of the scaled recursions (every kernel unit): a step is trusted while every live state's unnormalised message
+// component -- (sum_j alpha^[j] P[j][k]) e[k], with alpha^ of sum <= 1 up to the unnormalised steps in between, P and e
+// shifted to a maximum of 1 -- stays >= HMM_LOW.  Then every term a scaled step drops (an entry of P or e, or a product,
+// below 2.3e-308) is more than 1e-50 below the positive sum it is dropped from, and every component keeps its relative
+// accuracy.  A sequence with one component below it (or a normaliser below 1e-200) is REDONE IN LOG SPACE, all of it.
+constexpr double HMM_LOW = 1e-250;
 // wide kernel (17 <= K <= 64, one wavefront per sequence): workspace record per (sequence, step) =
 // [alpha^_t or log alpha_t (KP) | normaliser c_t | REDO flag of the sequence (first record only)]
 constexpr int HMM_WIDE_MAX_K = 64;

@@ -16,14 +16,16 @@
 // step), alpha is renormalised to sum 1, and log Z accumulates the scales as mantissa/exponent
 // pairs (one log per sequence).  Forward quantities needed by the backward pass (alpha_t, e_t/c_t)
 // go through a caller-owned workspace of HMM_WS doubles per (sequence, step).
-// Dynamic range: a scaled step underflows when every path into the states the next observation allows
-// goes through transition potentials ~700 nats below the matrix' maximum (exp underflows to 0 where the
-// reference's log-space pass keeps e^-800).  Such a step (normaliser c_t below 1e-200: rare) is redone
-// in LOG SPACE for its sequence -- K log-sum-exps like the reference -- and flagged in the workspace; the
-// backward pass treats flagged steps in log space too: no NaN, and the reference's value whenever the
-// paths that matter at a flagged step carried more than 1e-300 of the mass one step earlier.  (Components
-// of alpha below that are flushed to zero by the scaled steps in between -- only an all-log-space pass,
-// 4x the work, would keep them.)
+// Dynamic range: a scaled step loses what falls below 2.3e-308 of its scale -- a transition entry more than ~708 nats
+// below the matrix' maximum, a likelihood that far below the step's best, a message component below that share of
+// the total -- and a component lost is never rebuilt: the chain stays in the wrong state with an ordinary normaliser.
+// So a sequence is trusted only while EVERY live component of every step's unnormalised message stays >= HMM_LOW =
+// 1e-250 (hmm_args.hpp: what a step drops is then 1e-50 below the positive sum it is dropped from) and every
+// normaliser above 1e-200.  Any other sequence -- a state forbidden by a -1e4 or -inf potential counts -- raises its
+// REDO flag in the workspace and is recomputed by the launch behind this one, ALL of it in log space, the reference's
+// own arithmetic (hmm_estep_wide.hip, ROW instantiation: one wavefront per flagged sequence, K log-sum-exps of 16
+// terms per step -- by the operation count roughly 10x a scaled sequence's time, not measured; the other workgroups
+// read one flag and leave).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -37,13 +39,16 @@
 #define SVAE_HMM_TWOEND 1      // two-ended kernel + one-directional fallback for flagged sequences (0: the one-directional kernel alone; A/B)
 #endif
 
+// hmm_estep_wide.hip: the all-log-space pass over the sequences the kernels of this file flagged
+extern "C" int svae_hmm_row_logspace_launch(const svae::HmmArgs* a, void* stream);
+extern "C" int svae_hmm_row_logspace_ragged_launch(const svae::HmmRaggedArgs* a, void* stream);
+
 namespace svae {
 
-// workspace record per (sequence, step).  One-directional kernel (hmm_estep_kernel): [alpha (16) | e/c or its log-space
-// stand-in (16) | flag | ..].  Two-ended kernel (hmm_estep2_kernel): [alpha^ | e | w = e o beta^] in slots of 8 (K <= 8) or
-// 16 lanes, then the maximum of the node potentials; entry HMM_REDO of the sequence's FIRST record is its REDO flag.
-constexpr int HMM_WS = 50;
-constexpr int HMM_REDO = 49;
+// workspace record per (sequence, step).  One-directional kernel (hmm_estep_kernel): [alpha (16) | e/c (16) | ..].
+// Two-ended kernel (hmm_estep2_kernel): [alpha^ | e | w = e o beta^] in slots of 8 (K <= 8) or
+// 16 lanes, then the maximum of the node potentials; entry HMM_REDO of the sequence's FIRST record is its REDO flag
+// (hmm_args.hpp).  The log-space launch overwrites entries 0 .. 15 of a flagged sequence's records with log alpha_t.
 constexpr double HMM_TINY = 1e-200;
 
 // Maximum over the 16 lanes of a DPP row, in every lane: four rotate-and-max steps (row_ror:8/4/2/1 on the two halves
@@ -66,10 +71,11 @@ __device__ __forceinline__ double row_max16(double x) {
 // is the longest of them (wave-uniform) and every row runs under its own mask, by SELECTS, not by a neutral tail (an
 // identity transition would have to replace the register-resident P / PT per row and step): the row's loads are clamped
 // to its last step L-1 -- nothing stored at t >= L is read --, a step at t >= L is computed on that clamped data and
-// dropped (alpha, the logZ accumulators and their renormalisation, the `tiny` test and every workspace store are
+// dropped (alpha, the logZ accumulators and their renormalisation, the range test `bad` and every workspace store are
 // conditional on t < L, so a row's results depend on its own length and data only), the backward pass leaves beta = 1
-// and the xi sums alone while t >= L-1, and E_states from L on is zeroed after the last cross-lane operation.  The
-// log-space steps stay inline, so a ragged call is one launch.  All of it is `if constexpr`: the uniform instantiations
+// and the xi sums alone while t >= L-1, and E_states from L on is zeroed after the last cross-lane operation.  A row's
+// REDO flag depends on its own live steps only; the log-space launch behind the kernel cuts at the same length.
+// All of it is `if constexpr`: the uniform instantiations
 // compile to what they were.
 template <int K, bool FUSED = false, bool RAG = false>
 __global__ __launch_bounds__(64) void hmm_estep_kernel(const std::conditional_t<RAG, HmmRaggedArgs, HmmArgs> a) {
@@ -102,12 +108,6 @@ __global__ __launch_bounds__(64) void hmm_estep_kernel(const std::conditional_t<
     m = m2 > m ? m2 : m;
     TW = __builtin_amdgcn_readfirstlane(m);
   }
-  if (a.redo_only) {
-    // fallback pass behind the two-ended kernel: only for sequences it flagged (a step whose normaliser underflowed)
-    const double redo = a.ws[((long)b * T) * HMM_WS + HMM_REDO];
-    if (!__any(redo != 0.0)) return;
-  }
-
   // transition matrix in both layouts, shifted by its maximum (the shift goes into logZ)
   const double* pp = a.pair_params + (long)b * a.pair_stride;
   double lp[K], lpT[K];
@@ -149,8 +149,8 @@ __global__ __launch_bounds__(64) void hmm_estep_kernel(const std::conditional_t<
   }
   double* nout = a.node_out ? a.node_out + ((long)b * T) * K + cc : nullptr;
   double* wsb = a.ws + ((long)b * T) * HMM_WS + c;
-  double* wflag = a.ws + ((long)b * T) * HMM_WS + 32;
   double one = 1.0;
+  bool bad = false;            // this lane saw a component below HMM_LOW or a normaliser below HMM_TINY
 
   // ---- forward ------------------------------------------------------------------------------------
   double lzM = 1.0;            // product of scales (mantissa) ...
@@ -181,44 +181,12 @@ __global__ __launch_bounds__(64) void hmm_estep_kernel(const std::conditional_t<
     double cs = 0.0;
     dpp_fence(al);
     static_for<0, K>([&](auto k) { mac_bc<k>(cs, al, one); });            // c_t = sum_k
-    double rc = rcp_nr(cs);                 // (v_rcp_f64 + two Newton steps: no fp64 divide on the serial chain)
-    double u_st = e * rc, shift = m + (t > 0 ? pmax : 0.0), flag = 0.0;
-    const bool tiny = live && !(cs > HMM_TINY);
-    if (__any(tiny)) {
-      // log-space redo of this step for the rows that underflowed (wave-uniform branch; rows that did
-      // not underflow keep their scaled result)
-      const double la = alpha > 0.0 ? ::log(alpha) : NEG_BIG;       // alpha_{t-1}
-      double lpred = 0.0;
-      if (t > 0) {
-        double sj[K], m2 = NEG_BIG;
-        static_for<0, K>([&](auto j) {
-          const double lpj = col ? pp[j * K + cc] : NEG_BIG;        // log P[j][c], reloaded (rare path)
-          sj[j] = bcast<j>(la) + lpj;
-          m2 = fmax(m2, sj[j]);
-        });
-        double sum = 0.0;
-        static_for<0, K>([&](auto j) { sum += exp(sj[j] - m2); });
-        lpred = m2 + ::log(sum);
-      }
-      const double lal = col ? lpred + nd : NEG_BIG;
-      double M = NEG_BIG;
-      static_for<0, K>([&](auto k) { M = fmax(M, bcast<k>(lal)); });
-      const double al2 = col ? exp(lal - M) : 0.0;
-      double cs2 = 0.0;
-      static_for<0, K>([&](auto k) { cs2 += bcast<k>(al2); });
-      if (tiny) {
-        cs = cs2;
-        rc = rcp_nr(cs2);
-        al = al2;
-        shift = M;
-        flag = 1.0;
-        u_st = nd - M - ::log(cs2);          // log of (likelihood / normaliser): the backward pass adds log P
-      }
-    }
+    const double rc = rcp_nr(cs);           // (v_rcp_f64 + two Newton steps: no fp64 divide on the serial chain)
+    const double u_st = e * rc, shift = m + (t > 0 ? pmax : 0.0);
+    bad = bad || (live && ((col && !(al >= HMM_LOW)) || !(cs > HMM_TINY)));
     if constexpr (RAG) {
       alpha = live ? al * rc : alpha;
       if (valid && live) { wsb[(long)t * HMM_WS] = alpha; wsb[(long)t * HMM_WS + 16] = u_st; }
-      if (valid && live && c == 0) wflag[(long)t * HMM_WS] = flag;
       lzM = live ? lzM * __builtin_amdgcn_frexp_mant(cs) : lzM;
       lzE += live ? __builtin_amdgcn_frexp_exp(cs) : 0;
       lzS = live ? lzS + shift : lzS;
@@ -229,7 +197,6 @@ __global__ __launch_bounds__(64) void hmm_estep_kernel(const std::conditional_t<
     } else {
     alpha = al * rc;
     if (valid) { wsb[(long)t * HMM_WS] = alpha; wsb[(long)t * HMM_WS + 16] = u_st; }
-    if (valid && c == 0) wflag[(long)t * HMM_WS] = flag;
     lzM *= __builtin_amdgcn_frexp_mant(cs);
     lzE += __builtin_amdgcn_frexp_exp(cs);
     lzS += shift;
@@ -237,14 +204,16 @@ __global__ __launch_bounds__(64) void hmm_estep_kernel(const std::conditional_t<
     }
   }
   if (valid && c == 0) a.logZ[b] = lzS + ::log(lzM) + (double)lzE * 0.6931471805599453094;
+  {
+    // the row's REDO flag, written either way: the log-space launch behind this kernel reads it
+    const bool redo = ((__ballot(bad) >> (lane & 48)) & 0xffffull) != 0;
+    if (valid && c == 0) a.ws[((long)b * T) * HMM_WS + HMM_REDO] = redo ? 1.0 : 0.0;
+  }
 
   // ---- backward + statistics ----------------------------------------------------------------------
   double beta = col ? 1.0 : 0.0;
-  double acc[K];                       // xi sums without the transition factor (scaled steps)
+  double acc[K];                       // xi sums without the transition factor
   static_for<0, K>([&](auto j) { acc[j] = 0.0; });
-  double accS[K];                      // xi sums of the log-space steps (complete terms)
-  static_for<0, K>([&](auto j) { accS[j] = 0.0; });
-  bool any_slow = false;
   double* oS = a.E_states + ((long)b * T) * K + cc;
   {
     const double gam = alpha * beta;      // t = T-1  (RAG: the row's own last step, where alpha froze)
@@ -257,57 +226,14 @@ __global__ __launch_bounds__(64) void hmm_estep_kernel(const std::conditional_t<
   auto rec_hi = [&](int t) -> long { return RAG ? (long)(t < TL - 1 ? t : (TL > 1 ? TL - 1 : 0)) : (long)t; };
   auto rec_lo = [&](int t) -> long { return RAG ? (long)(t < TL - 2 ? t : (TL > 2 ? TL - 2 : 0)) : (long)t; };
   double u_n = TW > 1 ? wsb[rec_hi(TW - 1) * HMM_WS + 16] : 0.0, al_n = TW > 1 ? wsb[rec_lo(TW - 2) * HMM_WS] : 0.0;
-  double f_n = TW > 1 ? wflag[rec_hi(TW - 1) * HMM_WS] : 0.0;
   for (int t = TW - 2; t >= 0; --t) {
-    const double u = u_n;                              // e_{t+1} / c_{t+1}  (flagged step: its log-space stand-in)
+    const double u = u_n;                              // e_{t+1} / c_{t+1}
     const double al = al_n;
     const bool act = !RAG || t <= TL - 2;
-    const bool slow = act && f_n != 0.0;
     {
       const int tp = t > 0 ? t - 1 : 0;                // unconditional (clamped) prefetch of step t-1
       u_n = wsb[rec_hi(tp + 1) * HMM_WS + 16];
       al_n = wsb[rec_lo(tp) * HMM_WS];
-      f_n = wflag[rec_hi(tp + 1) * HMM_WS];
-    }
-    if (__any(slow)) {
-      // step t+1 was redone in log space: beta_t[j] = sum_k exp(log P[j][k] + ul[k] + log beta[k]),
-      // xi_t[j][k] = alpha_t[j] * that term  (K exponentials per lane; rows not flagged take the scaled
-      // formulas below through the selects)
-      any_slow = true;
-      const double lw = (col && beta > 0.0) ? u + ::log(beta) : NEG_BIG;     // lane k
-      double bn2 = 0.0, term[K];
-      static_for<0, K>([&](auto k) {
-        const double lpk = col ? pp[cc * K + k] : NEG_BIG;                   // log P[c][k]
-        // (clamped: a state the forward pass excludes may have a future e^800 times likelier than the
-        //  states that carry the mass; its beta only ever multiplies an alpha or a likelihood of exactly 0)
-        const double x = lpk + bcast<k>(lw);
-        term[k] = x > -745.0 ? fmin(exp(fmin(x, 700.0)), 1e300) : 0.0;
-        bn2 += term[k];                                                      // lane j = c: sum over k
-      });
-      // xi: lane k of accS[j] += alpha_t[j] * term_{lane j}[k]: transpose through broadcasts
-      if (slow) {
-        static_for<0, K>([&](auto j) {
-          // value at (j, k) lives in lane j, register k; lane k needs it: K x K broadcasts (rare path)
-          double row = 0.0;
-          static_for<0, K>([&](auto k) {
-            const double v = bcast<j>(term[k]);       // (unconditional: the source lane must be active)
-            row = (c == k) ? v : row;
-          });
-          accS[j] += bcast<j>(al) * row;
-        });
-      }
-      double w0 = (slow || !act) ? 0.0 : u * beta, al0 = (slow || !act) ? 0.0 : al;
-      dpp_fence(w0);
-      dpp_fence(al0);
-      double bn = 0.0;
-      static_for<0, K>([&](auto k) { mac_bc<k>(bn, w0, PT[k]); });
-      static_for<0, K>([&](auto j) { mac_bc<j>(acc[j], al0, w0); });
-      if constexpr (RAG) beta = act ? (slow ? fmin(bn2, 1e300) : bn) : beta;
-      else beta = slow ? fmin(bn2, 1e300) : bn;
-      const double gam = al * beta;
-      if (valid && col && act) oS[(long)t * K] = gam;
-      if (t == 0 && valid && col && act) a.E_init[(long)b * K + c] = gam;
-      continue;
     }
     double w = u * beta;
     double al_f = al;
@@ -324,8 +250,7 @@ __global__ __launch_bounds__(64) void hmm_estep_kernel(const std::conditional_t<
     if (t == 0 && valid && col && act) a.E_init[(long)b * K + c] = gam;
   }
   if (valid && col) {
-    static_for<0, K>([&](auto j) { a.E_trans[(long)b * K * K + j * K + c] = __builtin_fma(acc[j], P[j], accS[j]); });
-    (void)any_slow;
+    static_for<0, K>([&](auto j) { a.E_trans[(long)b * K * K + j * K + c] = acc[j] * P[j]; });
   }
   if constexpr (RAG) {
     // E_states from the row's length on: zeros, the 16 lanes of the row over the contiguous tail (after the last
@@ -352,9 +277,13 @@ __global__ __launch_bounds__(64) void hmm_estep_kernel(const std::conditional_t<
 // against 1 - 2 us of memory latency); no branch inside the steady-state loops (hipcc's wait counts degrade to
 // vmcnt(0) across one).  The records are compact -- [alpha^ | e | w] in slots of 8 lanes for K <= 8 -- inside the common
 // record stride: half the traffic of full-width slots at 2048 sequences.
-// A normaliser below HMM_TINY anywhere (the one-directional kernel's log-space case) raises the sequence's REDO flag:
-// the one-directional kernel is launched behind this one with redo_only = 1 and recomputes the flagged wavefronts,
-// log-space steps and all (its wavefronts exit at once otherwise).  Same mapping: one DPP row per sequence, lane = state.
+// Range (see the head of the file): a live component of the forward message alpha^_t or of the backward message w_t
+// below HMM_LOW, or a normaliser below HMM_TINY, anywhere raises the sequence's REDO flag -- a compare and an OR beside
+// the dependent chain, no branch.  The threshold is absolute: between two renormalisations a message's sum only leaves
+// [HMM_LOW, 16^3], so what an unnormalised step drops (below 16^3 * 2.3e-308) is still 1e-50 below every component kept.
+// alpha^ and w both keep their relative accuracy then, and phase 3 (Z_t > HMM_TINY) loses at most 1e-100 of a step's
+// posterior mass.  The log-space launch behind this kernel recomputes the flagged sequences (hmm_estep_wide.hip, ROW
+// instantiation; its other workgroups leave at once).  Same mapping: one DPP row per sequence, lane = state.
 constexpr int HMM2_D = 8;
 #ifndef SVAE_HMM2_NORM
 #define SVAE_HMM2_NORM 4
@@ -467,8 +396,8 @@ __global__ __launch_bounds__(64 * HMM2_WAVES) void hmm_estep2_kernel(const HmmAr
     long lzE = 0;
     const double colone = col ? 1.0 : 0.0;
     // (the message is renormalised every HMM2_NORM-th step only -- the sum, its reciprocal and the scaling are half of a
-    //  step's dependent chain; phase 3 normalises per step anyway, so any positive scaling of alpha^_t will do.  Between
-    //  two renormalisations the message can shrink by at most (1e-200)^(HMM2_NORM - 1) before the next sum flags the sequence)
+    //  step's dependent chain; phase 3 normalises per step anyway, so any positive scaling of alpha^_t will do.  Every
+    //  step, normalised or not, checks its components against HMM_LOW)
     auto fstep = [&](int t, double e, double m, auto norm, auto renorm) {
       double p0 = 0.0, p1 = 0.0;                        // two accumulators: half the dependent chain
       dpp_fence(alpha);
@@ -476,6 +405,7 @@ __global__ __launch_bounds__(64 * HMM2_WAVES) void hmm_estep2_kernel(const HmmAr
       const double first = t == 0 ? 1.0 : 0.0;          // (alpha starts at 0: pred_0 = 1 in the live lanes)
       const double pred = __builtin_fma(first, colone, p0 + p1);
       double al = pred * e;
+      bad = bad || (col && !(al >= HMM_LOW));
       if constexpr (decltype(norm)::value) {
         double c0 = 0.0, c1 = 0.0;
         dpp_fence(al);
@@ -525,6 +455,7 @@ __global__ __launch_bounds__(64 * HMM2_WAVES) void hmm_estep2_kernel(const HmmAr
   } else if (wv == 1) {
     // w_{T-1} = e_{T-1} (beta_{T-1} = 1);  t = T-2 .. 1:  beta^_t = P w_{t+1} / sum,  w_t = e_t o beta^_t
     double w = col ? wsb[(long)(T - 1) * HMM_WS + OE] : 0.0;
+    bad = bad || (col && !(w >= HMM_LOW));
     if (st) wsb[(long)(T - 1) * HMM_WS + OW] = w;
     auto bstep = [&](int t, double e, auto norm) {
       double q0 = 0.0, q1 = 0.0;
@@ -540,6 +471,7 @@ __global__ __launch_bounds__(64 * HMM2_WAVES) void hmm_estep2_kernel(const HmmAr
         q *= rcp_nr(d);
       }
       w = e * q;
+      bad = bad || (col && !(w >= HMM_LOW));
       if (st) wsb[(long)t * HMM_WS + OW] = w;
     };
     const int nsteps = T - 2 > 0 ? T - 2 : 0;            // step i: t = T-2-i  (t >= 1)
@@ -620,7 +552,8 @@ __global__ __launch_bounds__(64 * HMM2_WAVES) void hmm_estep2_kernel(const HmmAr
       if (T == 1 && st) a.E_init[(long)b * K + c] = al;
     }
   }
-  if (bad && valid && c == 0) wsr[HMM_REDO] = 1.0;
+  // (`bad` is per lane: the row's sixteen bits of the ballot)
+  if (((__ballot(bad) >> (lane & 48)) & 0xffffull) != 0 && valid && c == 0) wsr[HMM_REDO] = 1.0;
   if (wv > 0) static_for<0, K>([&](auto j) { xacc[((wv - 1) * 16 + j) * 64 + lane] = acc[j]; });
   __syncthreads();
   if (wv == 0 && st)
@@ -631,32 +564,28 @@ __global__ __launch_bounds__(64 * HMM2_WAVES) void hmm_estep2_kernel(const HmmAr
     });
 }
 
+// the scaled pass, then the log-space pass over the sequences it flagged.  The scaled pass is the two-ended kernel
+// where there is a step for each of its wavefronts (T >= HMM2_WAVES; SVAE_HMM_TWOEND = 0: nowhere), else the
+// one-directional kernel: one wavefront does all there is
 template <int K>
 static int launch_hmm(const HmmArgs& a, hipStream_t s) {
-#if SVAE_HMM_TWOEND
-  {
-    HmmArgs r = a;
-    r.redo_only = 1;
-    if (a.pair_contr) {
-      hipLaunchKernelGGL((hmm_estep2_kernel<K, true>), dim3((a.B + 3) / 4), dim3(64 * HMM2_WAVES), 0, s, a);
-      hipLaunchKernelGGL((hmm_estep_kernel<K, true>), dim3((a.B + 3) / 4), dim3(64), 0, s, r);
-    } else {
-      hipLaunchKernelGGL((hmm_estep2_kernel<K, false>), dim3((a.B + 3) / 4), dim3(64 * HMM2_WAVES), 0, s, a);
-      hipLaunchKernelGGL((hmm_estep_kernel<K, false>), dim3((a.B + 3) / 4), dim3(64), 0, s, r);
-    }
-    return hipGetLastError() == hipSuccess ? 0 : -1000;
+  if (SVAE_HMM_TWOEND && a.T >= HMM2_WAVES) {
+    if (a.pair_contr) hipLaunchKernelGGL((hmm_estep2_kernel<K, true>), dim3((a.B + 3) / 4), dim3(64 * HMM2_WAVES), 0, s, a);
+    else hipLaunchKernelGGL((hmm_estep2_kernel<K, false>), dim3((a.B + 3) / 4), dim3(64 * HMM2_WAVES), 0, s, a);
+  } else {
+    if (a.pair_contr) hipLaunchKernelGGL((hmm_estep_kernel<K, true>), dim3((a.B + 3) / 4), dim3(64), 0, s, a);
+    else hipLaunchKernelGGL((hmm_estep_kernel<K, false>), dim3((a.B + 3) / 4), dim3(64), 0, s, a);
   }
-#endif
-  if (a.pair_contr) hipLaunchKernelGGL((hmm_estep_kernel<K, true>), dim3((a.B + 3) / 4), dim3(64), 0, s, a);
-  else hipLaunchKernelGGL((hmm_estep_kernel<K, false>), dim3((a.B + 3) / 4), dim3(64), 0, s, a);
-  return hipGetLastError() == hipSuccess ? 0 : -1000;
+  if (hipGetLastError() != hipSuccess) return -1000;
+  return svae_hmm_row_logspace_launch(&a, s);
 }
 
-// per-sequence lengths: the one-directional kernel alone (log-space steps inline: one launch, no redo pass)
+// per-sequence lengths: the one-directional kernel, then the log-space pass over the rows it flagged
 template <int K>
 static int launch_hmm_ragged(const HmmRaggedArgs& a, hipStream_t s) {
   hipLaunchKernelGGL((hmm_estep_kernel<K, false, true>), dim3((a.B + 3) / 4), dim3(64), 0, s, a);
-  return hipGetLastError() == hipSuccess ? 0 : -1000;
+  if (hipGetLastError() != hipSuccess) return -1000;
+  return svae_hmm_row_logspace_ragged_launch(&a, s);
 }
 
 // ---- glue of one SLDS coordinate-ascent sweep (slds_svae.py:159-175), after the HMM and the fused LDS kernels ----------
@@ -978,7 +907,7 @@ extern "C" int svae_hmm_estep_f64(int B, int T, int K, int pair_batched,
   a.logZ = logZ; a.E_init = E_init; a.E_trans = E_trans; a.E_states = E_states;
   a.ws = (double*)workspace;
   a.seq_index = nullptr; a.n = 0; a.pair_contr = nullptr; a.lds_E_init = nullptr; a.init_J = nullptr; a.init_h = nullptr;
-  a.cinit = nullptr; a.lz = nullptr; a.node_out = nullptr; a.redo_only = 0;
+  a.cinit = nullptr; a.lz = nullptr; a.node_out = nullptr;
   return hmm_dispatch(a, stream);
 }
 
@@ -1012,7 +941,7 @@ extern "C" int svae_slds_hmm_meanfield_f64(int B, int rows, int T, int K, int n,
   a.ws = (double*)workspace;
   a.seq_index = seq_index; a.n = n;
   a.pair_contr = node_params ? nullptr : pair_contr; a.lds_E_init = lds_E_init; a.init_J = init_J; a.init_h = init_h;
-  a.cinit = cinit; a.lz = lz; a.node_out = node_out; a.redo_only = 0;
+  a.cinit = cinit; a.lz = lz; a.node_out = node_out;
   return hmm_dispatch(a, stream);
 }
 
@@ -1150,7 +1079,7 @@ extern "C" int svae_hmm_ragged_estep_f64(int B, int T, int K, int pair_batched,
   a.logZ = logZ; a.E_init = E_init; a.E_trans = E_trans; a.E_states = E_states;
   a.ws = (double*)workspace;
   a.seq_index = nullptr; a.n = 0; a.pair_contr = nullptr; a.lds_E_init = nullptr; a.init_J = nullptr; a.init_h = nullptr;
-  a.cinit = nullptr; a.lz = nullptr; a.node_out = nullptr; a.redo_only = 0;
+  a.cinit = nullptr; a.lz = nullptr; a.node_out = nullptr;
   a.lengths = lengths; a.info = info;
   if (K > 16) return svae_hmm_wide_ragged_launch(&a, stream);
   hipStream_t s = (hipStream_t)stream;

@@ -2,6 +2,7 @@
 
   hmm_estep(natparam) -> (log_normalizer, (E_init, E_trans, E_states))      (:21-41)
   hmm_logZ(natparam)  -> log_normalizer                                      (:12-17, pyx:93-121)
+  redone_sequences(workspace, B, T, K) -> which sequences of that E-step took the log-space route
   hmm_viterbi(natparam) -> most probable state path (and its score)          (:54-63; csrc/hmm_viterbi.hip)
   hmm_sample(natparam, num_samples) -> state paths drawn from the posterior  (csrc/hmm_sample.hip)
 
@@ -113,6 +114,23 @@ def hmm_estep(natparam, workspace=None, lengths=None, check=False):
     if not batched:
         return logZ[0], (E_init[0], E_trans[0], E_states[0])
     return logZ, (E_init, E_trans, E_states)
+
+
+def redone_sequences(workspace, B, T, K):
+    """Which sequences of the last hmm_estep call on `workspace` left the range of the scaled recursions and were
+    recomputed in log space: a (B,) bool tensor read from the REDO words the kernels write into the first record of
+    every sequence (csrc/hmm_args.hpp: record stride and flag entry 50 / 49 for K <= 16, KP + 2 / KP + 1 with KP = 32 or 64
+    padded states above).  A fallback is never silent: by its operation count a sequence costs roughly 10x more on that route (an estimate, not
+    a measurement), and this says which did.
+    For an indexed launch (the SLDS sweep) B counts the rows of the arrays, not the slots of the launch."""
+    if not (1 <= K <= HMM_MAX_K):
+        raise ValueError("number of states K=%d outside 1..%d" % (K, HMM_MAX_K))
+    kp = 32 if K <= 32 else 64
+    rec, flag = (50, 49) if K <= 16 else (kp + 2, kp + 1)
+    ws = workspace.reshape(-1)
+    if ws.dtype != torch.float64 or ws.numel() < B * T * rec:
+        raise ValueError("workspace is not the float64 workspace of a (B=%d, T=%d, K=%d) E-step" % (B, T, K))
+    return ws[:B * T * rec].view(B, T * rec)[:, flag] != 0
 
 
 def hmm_logZ(natparam, lengths=None):

@@ -107,8 +107,8 @@ def test_hmm_forced_transition_through_a_tiny_entry():
 
 def test_hmm_two_ended_kernel_with_one_flagged_sequence_among_many():
     """hmm_estep2_kernel (alpha and beta recursions on two wavefronts, each with its own scaling) serves every sequence
-    whose normalisers stay above 1e-200; a sequence that underflows is flagged and redone by the one-directional kernel
-    (log-space steps), wavefront by wavefront: here sequence 6 of 11 (third of its wavefront) is the forced-transition
+    whose message components stay above 1e-250 (and normalisers above 1e-200); any other sequence is flagged and redone
+    in log space by the launch behind it, sequence by sequence: here sequence 6 of 11 (third of its wavefront) is the forced-transition
     chain of the test above, the others are ordinary -- all of them must match the log-space oracle."""
     from svae_amd.hmm.hmm_inference import hmm_estep
     K, T, B = 3, 12, 11
