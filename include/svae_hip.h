@@ -25,7 +25,7 @@
 extern "C" {
 #endif
 
-#define SVAE_HIP_ABI_VERSION 15   /* 15: (+ svae_hmm_sample_workspace_bytes, svae_hmm_sample_f64, svae_hmm_ragged_sample_f64: HMM posterior sampling, uniform and with per-sequence lengths, added without a new number -- additions only) (+ svae_lds_ragged_perstep_workspace_bytes, svae_lds_ragged_perstep_estep_f64, svae_lds_ragged_perstep_inference_f64: per-sequence lengths with per-step pair parameters and a per-sequence init potential, added without a new number -- additions only) (+ svae_hmm_ragged_estep_f64, svae_hmm_ragged_viterbi_f64: per-sequence lengths for the HMM E-step and Viterbi, added without a new number -- additions only, compatible with every caller of 15) (+ svae_lds_estep_vjp_params_f64, svae_lds_param_vjp_workspace_bytes: cotangents of the init / pair natural parameters, added without a new number -- additions only) + svae_gmm_wide_mw_workspace_bytes, svae_gmm_wide_mw_begin, svae_gmm_wide_mw_step_f64, svae_gmm_wide_sample_f64, svae_gmm_wide_local_vjp_f64, svae_gmm_wide_global_step_f64 (the GMM local step for N <= 16; additions only), svae_lds_filter_vjp_f64, svae_lds_smoother_vjp_f64 (+ svae_lds_smoother_vjp_workspace_bytes), svae_lds_sample_vjp_f64 (the reference's three reverse-mode primitives on caller-held forward messages); 14: + svae_lds_estep_vjp_dense_f64 (cotangent of dense node potentials), svae_hmm_* up to K = 64, svae_lds_inference_f64 (E-step + sampler in one call; lean per-step records for large homogeneous batches), svae_lds_inference_is_lean, SVAE_OPT_LEAN_ON / _OFF / SVAE_OPT_INFER_RECORDS; 13: + svae_slds_pair_contract_f64 (the two contractions of the SLDS final pass over the per-step pair statistics in one pass); 12: svae_gmm_global_step_f64 writes kl[0..1] (as spelled | as shipped), svae_ipc_allreduce_f64 takes the mailbox stride and never writes `out` on a timeout, + svae_slds_lds_meanfield options; 11: + svae_lds_global_step_multi_f64 (K parameter sets in one launch: the SLDS global -> local maps), svae_lds_diag_sample_f64 (filter + sampler of an all-diagonal LDS: the SLDS initial path); 10: + svae_ipc_allreduce_f64 / svae_ipc_mailbox_bytes, svae_gmm_sample_f64, svae_gmm_local_vjp_f64, svae_gmm_global_step_f64 (the differentiable tail and the global side of the GMM local step); 9: keep bit SVAE_KEEP_SIGMA of svae_lds_estep_f64 (16 <= n <= 64) + svae_lds_tile_sigma_offset_bytes; 8: step ranges (t_begin, t_end) in svae_lds_tile_vjp_f64 / svae_lds_tile_noise_f64, SVAE_OPT_TILE_FORWARD / _BACKWARD; 7: + svae_slds_path_nodeparams_f64, svae_slds_mix_pair_natparam_f64; 6: per-call `options` word replaces the process-global svae_lds_set_* selectors (re-entrant library), + svae_slds_hmm_meanfield_f64, svae_slds_sweep_glue_f64, g_E_pair in svae_lds_tile_vjp_f64; 5: + svae_lds_set_prod_max_b; 4: + svae_slds_lds_meanfield_f64, svae_gmm_mw_*, svae_lds_global_step_f64, svae_lds_natgrad_f64, svae_lds_tile_vjp_f64; 2: + svae_lds_workspace_bytes_ex, svae_lds_estep_vjp_ex_f64, svae_hmm_*, tiled path (n <= 64) */
+#define SVAE_HIP_ABI_VERSION 15   /* 15: (+ svae_hmm_estep_vjp_workspace_bytes, svae_hmm_estep_vjp_f64, svae_hmm_ragged_estep_vjp_f64: the reverse-mode derivative of the HMM E-step, uniform and with per-sequence lengths, added without a new number -- additions only) (+ svae_hmm_sample_workspace_bytes, svae_hmm_sample_f64, svae_hmm_ragged_sample_f64: HMM posterior sampling, uniform and with per-sequence lengths, added without a new number -- additions only) (+ svae_lds_ragged_perstep_workspace_bytes, svae_lds_ragged_perstep_estep_f64, svae_lds_ragged_perstep_inference_f64: per-sequence lengths with per-step pair parameters and a per-sequence init potential, added without a new number -- additions only) (+ svae_hmm_ragged_estep_f64, svae_hmm_ragged_viterbi_f64: per-sequence lengths for the HMM E-step and Viterbi, added without a new number -- additions only, compatible with every caller of 15) (+ svae_lds_estep_vjp_params_f64, svae_lds_param_vjp_workspace_bytes: cotangents of the init / pair natural parameters, added without a new number -- additions only) + svae_gmm_wide_mw_workspace_bytes, svae_gmm_wide_mw_begin, svae_gmm_wide_mw_step_f64, svae_gmm_wide_sample_f64, svae_gmm_wide_local_vjp_f64, svae_gmm_wide_global_step_f64 (the GMM local step for N <= 16; additions only), svae_lds_filter_vjp_f64, svae_lds_smoother_vjp_f64 (+ svae_lds_smoother_vjp_workspace_bytes), svae_lds_sample_vjp_f64 (the reference's three reverse-mode primitives on caller-held forward messages); 14: + svae_lds_estep_vjp_dense_f64 (cotangent of dense node potentials), svae_hmm_* up to K = 64, svae_lds_inference_f64 (E-step + sampler in one call; lean per-step records for large homogeneous batches), svae_lds_inference_is_lean, SVAE_OPT_LEAN_ON / _OFF / SVAE_OPT_INFER_RECORDS; 13: + svae_slds_pair_contract_f64 (the two contractions of the SLDS final pass over the per-step pair statistics in one pass); 12: svae_gmm_global_step_f64 writes kl[0..1] (as spelled | as shipped), svae_ipc_allreduce_f64 takes the mailbox stride and never writes `out` on a timeout, + svae_slds_lds_meanfield options; 11: + svae_lds_global_step_multi_f64 (K parameter sets in one launch: the SLDS global -> local maps), svae_lds_diag_sample_f64 (filter + sampler of an all-diagonal LDS: the SLDS initial path); 10: + svae_ipc_allreduce_f64 / svae_ipc_mailbox_bytes, svae_gmm_sample_f64, svae_gmm_local_vjp_f64, svae_gmm_global_step_f64 (the differentiable tail and the global side of the GMM local step); 9: keep bit SVAE_KEEP_SIGMA of svae_lds_estep_f64 (16 <= n <= 64) + svae_lds_tile_sigma_offset_bytes; 8: step ranges (t_begin, t_end) in svae_lds_tile_vjp_f64 / svae_lds_tile_noise_f64, SVAE_OPT_TILE_FORWARD / _BACKWARD; 7: + svae_slds_path_nodeparams_f64, svae_slds_mix_pair_natparam_f64; 6: per-call `options` word replaces the process-global svae_lds_set_* selectors (re-entrant library), + svae_slds_hmm_meanfield_f64, svae_slds_sweep_glue_f64, g_E_pair in svae_lds_tile_vjp_f64; 5: + svae_lds_set_prod_max_b; 4: + svae_slds_lds_meanfield_f64, svae_gmm_mw_*, svae_lds_global_step_f64, svae_lds_natgrad_f64, svae_lds_tile_vjp_f64; 2: + svae_lds_workspace_bytes_ex, svae_lds_estep_vjp_ex_f64, svae_hmm_*, tiled path (n <= 64) */
 #define SVAE_HMM_MAX_K 64   /* svae_hmm_estep_f64 / svae_slds_hmm_meanfield_f64: K <= 16 one DPP row per sequence; 17 <= K <= 64 one wavefront per sequence (round 6) */
 #define SVAE_LDS_MAX_N 15   /* register/DPP path: one 16-lane row per sequence, n+1 <= 16 */
 #define SVAE_LDS_TILE_MAX_N 64   /* 16 <= n <= 64: LDS-tiled MFMA path (keep: SVAE_KEEP_SIGMA or 0) */
@@ -611,6 +611,54 @@ int svae_hmm_ragged_sample_f64(int B, int T, int K, int S, int pair_batched,
                                const double* node_params, const int32_t* lengths, const double* u,
                                int32_t* states, double* logZ /* or NULL */,
                                int32_t* info, void* workspace, size_t ws_bytes, void* stream);
+
+/* Reverse-mode derivative of the batched HMM E-step (svae_hmm_estep_f64 / svae_hmm_ragged_estep_f64), K <=
+ * SVAE_HMM_MAX_K -- csrc/hmm_estep_vjp.hip, which states the arithmetic.  Additions to ABI 15 (no new number).  The
+ * cotangents of all four outputs are pulled back to all three inputs: with phi(z) = g_init[z_0] + sum_t g_trans[z_t,
+ * z_{t+1}] + sum_t g_states[t, z_t], gamma_t and xi_t the state and pair marginals of sequence b (length L = T in the
+ * uniform call),
+ *    d_node[b,t,k] = gamma_t[k] (g_logZ[b] + E[phi | z_t = k] - E[phi]),   d_init[b] = d_node[b,0],
+ *    d_pair[b,i,j] = sum_{t < L-1} xi_t[i,j] (g_logZ[b] + E[phi | z_t = i, z_{t+1} = j] - E[phi])
+ *  (the Hessian of log Z applied to the cotangents of the statistics, plus g_logZ times the statistics).  A -inf
+ *  potential has gradient exactly 0; a finite cotangent at a position of probability 0 contributes exactly 0.  A
+ *  sequence with log Z = -inf is outside the contract, as for the E-step.
+ *  in : init_params (K); pair_params (K,K) or (B,K,K) if pair_batched; node_params (B,T,K);
+ *       g_logZ (B), g_init (B,K), g_trans (B,K,K), g_states (B,T,K): each may be NULL = a zero cotangent
+ *  out: d_init (B,K), d_pair (B,K,K), d_node (B,T,K), all per sequence: for shared parameters the caller sums d_init
+ *       (and d_pair, if not pair_batched) over the batch
+ *  Range: the E-step's contract -- every sequence with a path of finite score gets the log-space result to rounding.
+ *       The scaled kernels raise a sequence's route flag when a live component of an unnormalised message falls below
+ *       1e-250 or a normaliser below 1e-200, in the forward or in the backward sweep; the log-space launch behind them
+ *       recomputes those sequences, all of each.
+ *  workspace: svae_hmm_estep_vjp_workspace_bytes(B,T,K) = (B T 2 KP + B) doubles rounded up to 128 bytes, KP = 16, 32 or
+ *       64 for K <= 16, <= 32, <= 64: per step [a_t | r_t] (on the log-space route log a_t), then B route flags (1.0 =
+ *       the sequence was redone in log space); 0 for B <= 0, T <= 0 or K outside 1..SVAE_HMM_MAX_K.  16-byte aligned.
+ *  Ragged form (svae_hmm_ragged_estep_vjp_f64, lengths (B) device int32), the conventions of the other ragged entries:
+ *    the gradients are those of the sequence cut at L; d_node[b, t >= L] is exactly 0; node_params[b, L:] and
+ *    g_states[b, L:] are never read and may be NaN; a length outside 1..T is clamped to [1, T] and ORs 1 into `info`.
+ *  Returns 0, or (decided on the host before any HIP call, the first failing check)
+ *   both   : -1 B < 0, -2 T < 1, -3 K outside 1..SVAE_HMM_MAX_K, -4 pair_batched not 0 or 1, -5 init_params NULL,
+ *            -6 pair_params NULL, [B = 0 returns 0 here], -7 node_params NULL;
+ *   uniform: -8 d_init NULL, -9 d_pair NULL, -10 d_node NULL, -11 workspace NULL, -12 ws_bytes too small, -13 workspace
+ *            not 16-byte aligned;
+ *   ragged : -8 lengths NULL, -9 d_init NULL, -10 d_pair NULL, -11 d_node NULL, -12 info NULL, -13 workspace NULL,
+ *            -14 ws_bytes too small, -15 workspace not 16-byte aligned;
+ *  -1000 launch error.  Two launches (scaled, log-space redo), asynchronous on `stream`, no internal allocation, safe
+ *  under graph capture. */
+size_t svae_hmm_estep_vjp_workspace_bytes(int B, int T, int K);
+int svae_hmm_estep_vjp_f64(int B, int T, int K, int pair_batched,
+                           const double* init_params, const double* pair_params, const double* node_params,
+                           const double* g_logZ /* or NULL */, const double* g_init /* or NULL */,
+                           const double* g_trans /* or NULL */, const double* g_states /* or NULL */,
+                           double* d_init, double* d_pair, double* d_node,
+                           void* workspace, size_t ws_bytes, void* stream);
+int svae_hmm_ragged_estep_vjp_f64(int B, int T, int K, int pair_batched,
+                                  const double* init_params, const double* pair_params, const double* node_params,
+                                  const int32_t* lengths,
+                                  const double* g_logZ /* or NULL */, const double* g_init /* or NULL */,
+                                  const double* g_trans /* or NULL */, const double* g_states /* or NULL */,
+                                  double* d_init, double* d_pair, double* d_node,
+                                  int32_t* info, void* workspace, size_t ws_bytes, void* stream);
 
 /* HMM step of the SLDS coordinate ascent on the rows `seq_index` lists (B of `rows`; NULL: rows 0..B-1; negative
  * entries = unused slots, which must follow the live ones -- the list svae_slds_sweep_glue_f64 writes):

@@ -1,0 +1,1 @@
+from .hmm_inference import hmm_estep_differentiable, hmm_estep_vjp, vjp_redone_sequences  # noqa: F401

@@ -5,6 +5,8 @@
   redone_sequences(workspace, B, T, K) -> which sequences of that E-step took the log-space route
   hmm_viterbi(natparam) -> most probable state path (and its score)          (:54-63; csrc/hmm_viterbi.hip)
   hmm_sample(natparam, num_samples) -> state paths drawn from the posterior  (csrc/hmm_sample.hip)
+  hmm_estep_differentiable(natparam) -> hmm_estep's outputs, with gradients of all four to all three inputs
+                                                                             (csrc/hmm_estep_vjp.hip)
 
 natparam = (init_params (K), pair_params (K,K), node_params (T,K)) are LOG potentials, as in the
 reference.  New: node_params may be (B,T,K) (and pair_params (B,K,K)); outputs then carry a leading
@@ -280,3 +282,122 @@ def hmm_logZ_differentiable(natparam, lengths=None):
     the same launch: exactly 0 from a sequence's length on."""
     init_params, pair_params, node_params = natparam
     return _HMMLogZ.apply(node_params, init_params, pair_params, lengths)
+
+
+def hmm_estep_vjp(natparam, cotangents, workspace=None, lengths=None, check=False):
+    """The reverse-mode derivative of hmm_estep (svae_hmm_estep_vjp_f64, include/svae_hip.h): cotangents = (g_logZ,
+    (g_init, g_trans, g_states)) in the shapes hmm_estep returns, each may be None (zero).  Returns the PER-SEQUENCE
+    gradients (d_init (B,K), d_pair (B,K,K), d_node (B,T,K)) -- without the leading axis for unbatched (T,K) node
+    potentials --; a shared init or pair parameter's gradient is their sum over the batch.
+    workspace: a contiguous float64 device tensor of at least svae_hmm_estep_vjp_workspace_bytes(B,T,K) bytes; afterwards
+    vjp_redone_sequences(workspace, B, T, K) says which sequences took the log-space route."""
+    init_params, pair_params, node_params = natparam
+    lens = None if lengths is None else _lengths_arg(lengths, node_params)
+    dev = node_params.device if isinstance(node_params, torch.Tensor) and node_params.is_cuda \
+        else torch.device("cuda", torch.cuda.current_device())
+    init_params, pair_params, node = (_dev64(x, dev) for x in (init_params, pair_params, node_params))
+    batched = node.dim() == 3
+    if node.dim() not in (2, 3):
+        raise ValueError("node_params must be (T,K) or (B,T,K)")
+    if not batched:
+        node = node[None]
+    B, T, K = node.shape
+    if not (1 <= K <= HMM_MAX_K):
+        raise ValueError("number of states K=%d outside 1..%d" % (K, HMM_MAX_K))
+    if T < 1:
+        raise ValueError("node_params has no steps")
+    pair_batched = pair_params.dim() == 3
+    if tuple(init_params.shape) != (K,) or tuple(pair_params.shape[-2:]) != (K, K) or pair_params.dim() not in (2, 3) or \
+            (pair_batched and pair_params.shape[0] != B):
+        raise ValueError("init/pair parameter shapes do not match the node potentials")
+    g_logZ, (g_init, g_trans, g_states) = cotangents
+    cots = []
+    for name, x, shape in (("g_logZ", g_logZ, (B,)), ("g_init", g_init, (B, K)), ("g_trans", g_trans, (B, K, K)),
+                           ("g_states", g_states, (B, T, K))):
+        if x is not None:
+            want = shape if batched else shape[1:]
+            if tuple(x.shape) != want:
+                raise ValueError("%s must have shape %r, got %r" % (name, want, tuple(x.shape)))
+            x = _dev64(x, dev).reshape(shape)
+        cots.append(x)
+    lib = _lib.load()
+    f64 = dict(dtype=torch.float64, device=dev)
+    wsb = int(lib.svae_hmm_estep_vjp_workspace_bytes(max(B, 1), T, K))
+    if workspace is None:
+        ws = torch.empty(wsb // 8, **f64)
+    else:
+        ws = workspace
+        wsb = ws.numel() * ws.element_size()
+    d_init, d_pair, d_node = torch.empty(B, K, **f64), torch.empty(B, K, K, **f64), torch.empty(B, T, K, **f64)
+    p = _lib.ptr
+    if lens is not None:
+        rc = lib.svae_hmm_ragged_estep_vjp_f64(B, T, K, int(pair_batched), p(init_params), p(pair_params), p(node), p(lens),
+                                               p(cots[0]), p(cots[1]), p(cots[2]), p(cots[3]),
+                                               p(d_init), p(d_pair), p(d_node), p(_status_word(dev)), p(ws), wsb,
+                                               _lib.current_stream(dev))
+        _lib.check(rc, "svae_hmm_ragged_estep_vjp_f64")
+        if check:
+            check_lengths_status(dev)
+        return d_init, d_pair, d_node
+    rc = lib.svae_hmm_estep_vjp_f64(B, T, K, int(pair_batched), p(init_params), p(pair_params), p(node),
+                                    p(cots[0]), p(cots[1]), p(cots[2]), p(cots[3]),
+                                    p(d_init), p(d_pair), p(d_node), p(ws), wsb, _lib.current_stream(dev))
+    _lib.check(rc, "svae_hmm_estep_vjp_f64")
+    if not batched:
+        return d_init[0], d_pair[0], d_node[0]
+    return d_init, d_pair, d_node
+
+
+def vjp_redone_sequences(workspace, B, T, K):
+    """Which sequences of the last hmm_estep_vjp call on `workspace` left the range of the scaled recursions and were
+    recomputed in log space: a (B,) bool tensor read from the route flags behind the workspace's records
+    (csrc/hmm_estep_vjp_kernel.hpp: B T 2 KP doubles of records, KP = 16, 32 or 64, then one flag per sequence).  The
+    counterpart of redone_sequences for the E-step's derivative."""
+    if not (1 <= K <= HMM_MAX_K):
+        raise ValueError("number of states K=%d outside 1..%d" % (K, HMM_MAX_K))
+    kp = 16 if K <= 16 else (32 if K <= 32 else 64)
+    ws = workspace.reshape(-1)
+    if ws.dtype != torch.float64 or ws.numel() < B * T * 2 * kp + B:
+        raise ValueError("workspace is not the float64 workspace of a (B=%d, T=%d, K=%d) E-step derivative" % (B, T, K))
+    return ws[B * T * 2 * kp:B * T * 2 * kp + B] != 0
+
+
+class _HMMEStep(torch.autograd.Function):
+    """hmm_estep with its reverse-mode derivative: forward is hmm_estep unchanged, backward one call of
+    svae_hmm_estep_vjp_f64 (or its ragged form) on the saved potentials."""
+
+    @staticmethod
+    def forward(ctx, init_params, pair_params, node_params, lengths, check):
+        logZ, (E_init, E_trans, E_states) = hmm_estep((init_params, pair_params, node_params), lengths=lengths, check=check)
+        ctx.save_for_backward(init_params, pair_params, node_params)
+        ctx.lengths = lengths
+        return logZ, E_init, E_trans, E_states
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g_logZ, g_init, g_trans, g_states):
+        init_params, pair_params, node_params = ctx.saved_tensors
+        d_init, d_pair, d_node = hmm_estep_vjp((init_params, pair_params, node_params),
+                                               (g_logZ, (g_init, g_trans, g_states)), lengths=ctx.lengths)
+        if node_params.dim() == 3:
+            d_init = d_init.sum(0)                    # shared parameters receive the batch sum
+            if pair_params.dim() == 2:
+                d_pair = d_pair.sum(0)
+        need = ctx.needs_input_grad
+        like = lambda d, x: d.to(device=x.device, dtype=x.dtype)          # noqa: E731
+        return (like(d_init, init_params) if need[0] else None, like(d_pair, pair_params) if need[1] else None,
+                like(d_node, node_params) if need[2] else None, None, None)
+
+
+def hmm_estep_differentiable(natparam, lengths=None, check=False):
+    """hmm_estep -> (logZ, (E_init, E_trans, E_states)) with gradients of all four outputs flowing to whichever of
+    init_params (K), pair_params (K,K) or (B,K,K) and node_params (T,K) or (B,T,K) require them (torch tensors on the
+    device).  The outputs are those of hmm_estep, bit for bit; the backward pass is one call of svae_hmm_estep_vjp_f64
+    (once differentiable): a shared init or pair parameter receives the sum over the batch, a per-sequence pair parameter
+    its own block.  With lengths= the gradient is that of every sequence cut to its length: exactly 0 from there on."""
+    init_params, pair_params, node_params = natparam
+    for x in (init_params, pair_params, node_params):
+        if not isinstance(x, torch.Tensor):
+            raise TypeError("hmm_estep_differentiable takes torch tensors")
+    logZ, E_init, E_trans, E_states = _HMMEStep.apply(init_params, pair_params, node_params, lengths, check)
+    return logZ, (E_init, E_trans, E_states)
