@@ -25,7 +25,7 @@
 extern "C" {
 #endif
 
-#define SVAE_HIP_ABI_VERSION 15   /* 15: (+ svae_hmm_estep_vjp_workspace_bytes, svae_hmm_estep_vjp_f64, svae_hmm_ragged_estep_vjp_f64: the reverse-mode derivative of the HMM E-step, uniform and with per-sequence lengths, added without a new number -- additions only) (+ svae_hmm_sample_workspace_bytes, svae_hmm_sample_f64, svae_hmm_ragged_sample_f64: HMM posterior sampling, uniform and with per-sequence lengths, added without a new number -- additions only) (+ svae_lds_ragged_perstep_workspace_bytes, svae_lds_ragged_perstep_estep_f64, svae_lds_ragged_perstep_inference_f64: per-sequence lengths with per-step pair parameters and a per-sequence init potential, added without a new number -- additions only) (+ svae_hmm_ragged_estep_f64, svae_hmm_ragged_viterbi_f64: per-sequence lengths for the HMM E-step and Viterbi, added without a new number -- additions only, compatible with every caller of 15) (+ svae_lds_estep_vjp_params_f64, svae_lds_param_vjp_workspace_bytes: cotangents of the init / pair natural parameters, added without a new number -- additions only) + svae_gmm_wide_mw_workspace_bytes, svae_gmm_wide_mw_begin, svae_gmm_wide_mw_step_f64, svae_gmm_wide_sample_f64, svae_gmm_wide_local_vjp_f64, svae_gmm_wide_global_step_f64 (the GMM local step for N <= 16; additions only), svae_lds_filter_vjp_f64, svae_lds_smoother_vjp_f64 (+ svae_lds_smoother_vjp_workspace_bytes), svae_lds_sample_vjp_f64 (the reference's three reverse-mode primitives on caller-held forward messages); 14: + svae_lds_estep_vjp_dense_f64 (cotangent of dense node potentials), svae_hmm_* up to K = 64, svae_lds_inference_f64 (E-step + sampler in one call; lean per-step records for large homogeneous batches), svae_lds_inference_is_lean, SVAE_OPT_LEAN_ON / _OFF / SVAE_OPT_INFER_RECORDS; 13: + svae_slds_pair_contract_f64 (the two contractions of the SLDS final pass over the per-step pair statistics in one pass); 12: svae_gmm_global_step_f64 writes kl[0..1] (as spelled | as shipped), svae_ipc_allreduce_f64 takes the mailbox stride and never writes `out` on a timeout, + svae_slds_lds_meanfield options; 11: + svae_lds_global_step_multi_f64 (K parameter sets in one launch: the SLDS global -> local maps), svae_lds_diag_sample_f64 (filter + sampler of an all-diagonal LDS: the SLDS initial path); 10: + svae_ipc_allreduce_f64 / svae_ipc_mailbox_bytes, svae_gmm_sample_f64, svae_gmm_local_vjp_f64, svae_gmm_global_step_f64 (the differentiable tail and the global side of the GMM local step); 9: keep bit SVAE_KEEP_SIGMA of svae_lds_estep_f64 (16 <= n <= 64) + svae_lds_tile_sigma_offset_bytes; 8: step ranges (t_begin, t_end) in svae_lds_tile_vjp_f64 / svae_lds_tile_noise_f64, SVAE_OPT_TILE_FORWARD / _BACKWARD; 7: + svae_slds_path_nodeparams_f64, svae_slds_mix_pair_natparam_f64; 6: per-call `options` word replaces the process-global svae_lds_set_* selectors (re-entrant library), + svae_slds_hmm_meanfield_f64, svae_slds_sweep_glue_f64, g_E_pair in svae_lds_tile_vjp_f64; 5: + svae_lds_set_prod_max_b; 4: + svae_slds_lds_meanfield_f64, svae_gmm_mw_*, svae_lds_global_step_f64, svae_lds_natgrad_f64, svae_lds_tile_vjp_f64; 2: + svae_lds_workspace_bytes_ex, svae_lds_estep_vjp_ex_f64, svae_hmm_*, tiled path (n <= 64) */
+#define SVAE_HIP_ABI_VERSION 15   /* 15: (+ svae_lds_ragged_perstep_inference_keep_f64, svae_lds_ragged_perstep_vjp_f64: the forward records and the reverse sweeps of the per-step ragged LDS, added without a new number -- additions only) (+ svae_hmm_estep_vjp_workspace_bytes, svae_hmm_estep_vjp_f64, svae_hmm_ragged_estep_vjp_f64: the reverse-mode derivative of the HMM E-step, uniform and with per-sequence lengths, added without a new number -- additions only) (+ svae_hmm_sample_workspace_bytes, svae_hmm_sample_f64, svae_hmm_ragged_sample_f64: HMM posterior sampling, uniform and with per-sequence lengths, added without a new number -- additions only) (+ svae_lds_ragged_perstep_workspace_bytes, svae_lds_ragged_perstep_estep_f64, svae_lds_ragged_perstep_inference_f64: per-sequence lengths with per-step pair parameters and a per-sequence init potential, added without a new number -- additions only) (+ svae_hmm_ragged_estep_f64, svae_hmm_ragged_viterbi_f64: per-sequence lengths for the HMM E-step and Viterbi, added without a new number -- additions only, compatible with every caller of 15) (+ svae_lds_estep_vjp_params_f64, svae_lds_param_vjp_workspace_bytes: cotangents of the init / pair natural parameters, added without a new number -- additions only) + svae_gmm_wide_mw_workspace_bytes, svae_gmm_wide_mw_begin, svae_gmm_wide_mw_step_f64, svae_gmm_wide_sample_f64, svae_gmm_wide_local_vjp_f64, svae_gmm_wide_global_step_f64 (the GMM local step for N <= 16; additions only), svae_lds_filter_vjp_f64, svae_lds_smoother_vjp_f64 (+ svae_lds_smoother_vjp_workspace_bytes), svae_lds_sample_vjp_f64 (the reference's three reverse-mode primitives on caller-held forward messages); 14: + svae_lds_estep_vjp_dense_f64 (cotangent of dense node potentials), svae_hmm_* up to K = 64, svae_lds_inference_f64 (E-step + sampler in one call; lean per-step records for large homogeneous batches), svae_lds_inference_is_lean, SVAE_OPT_LEAN_ON / _OFF / SVAE_OPT_INFER_RECORDS; 13: + svae_slds_pair_contract_f64 (the two contractions of the SLDS final pass over the per-step pair statistics in one pass); 12: svae_gmm_global_step_f64 writes kl[0..1] (as spelled | as shipped), svae_ipc_allreduce_f64 takes the mailbox stride and never writes `out` on a timeout, + svae_slds_lds_meanfield options; 11: + svae_lds_global_step_multi_f64 (K parameter sets in one launch: the SLDS global -> local maps), svae_lds_diag_sample_f64 (filter + sampler of an all-diagonal LDS: the SLDS initial path); 10: + svae_ipc_allreduce_f64 / svae_ipc_mailbox_bytes, svae_gmm_sample_f64, svae_gmm_local_vjp_f64, svae_gmm_global_step_f64 (the differentiable tail and the global side of the GMM local step); 9: keep bit SVAE_KEEP_SIGMA of svae_lds_estep_f64 (16 <= n <= 64) + svae_lds_tile_sigma_offset_bytes; 8: step ranges (t_begin, t_end) in svae_lds_tile_vjp_f64 / svae_lds_tile_noise_f64, SVAE_OPT_TILE_FORWARD / _BACKWARD; 7: + svae_slds_path_nodeparams_f64, svae_slds_mix_pair_natparam_f64; 6: per-call `options` word replaces the process-global svae_lds_set_* selectors (re-entrant library), + svae_slds_hmm_meanfield_f64, svae_slds_sweep_glue_f64, g_E_pair in svae_lds_tile_vjp_f64; 5: + svae_lds_set_prod_max_b; 4: + svae_slds_lds_meanfield_f64, svae_gmm_mw_*, svae_lds_global_step_f64, svae_lds_natgrad_f64, svae_lds_tile_vjp_f64; 2: + svae_lds_workspace_bytes_ex, svae_lds_estep_vjp_ex_f64, svae_hmm_*, tiled path (n <= 64) */
 #define SVAE_HMM_MAX_K 64   /* svae_hmm_estep_f64 / svae_slds_hmm_meanfield_f64: K <= 16 one DPP row per sequence; 17 <= K <= 64 one wavefront per sequence (round 6) */
 #define SVAE_LDS_MAX_N 15   /* register/DPP path: one 16-lane row per sequence, n+1 <= 16 */
 #define SVAE_LDS_TILE_MAX_N 64   /* 16 <= n <= 64: LDS-tiled MFMA path (keep: SVAE_KEEP_SIGMA or 0) */
@@ -1010,7 +1010,8 @@ int svae_lds_ragged_natgrad_f64(int n, const double* packed_stats, const double*
  * samples[b,L:] are 0; J11 / J12 / J22 / logZ_pair at t >= L-1 (any sequence's with pair_batched = 0 only through another
  * sequence's longer length), node_*[b,L:] and eps[b,L:] are never read (they may be NaN); no result of sequence b depends on
  * another sequence's length.  A length outside 1..T raises the status word `info` (b+1) and is clamped to 1..T for
- * addressing.  There are no VJP sweeps on these records.
+ * addressing.  The reverse sweeps run on the records of svae_lds_ragged_perstep_inference_keep_f64 (keep_vjp = 1):
+ * svae_lds_ragged_perstep_vjp_f64 below; the records of the two entries without keep_vjp carry no cross moments.
  *
  * Workspace: the layout of svae_lds_workspace_bytes(B,T,n), then (256-byte aligned) the table, 2 n^2 doubles. */
 size_t svae_lds_ragged_perstep_workspace_bytes(int B, int T, int n);
@@ -1041,6 +1042,47 @@ int svae_lds_ragged_perstep_inference_f64(int B, int T, int n, int S, int pair_b
                                           double* lognorm, double* E_init, double* E_pair,
                                           double* E_node_diagxx, double* E_node_x,
                                           int32_t* info, void* workspace, size_t ws_bytes, void* stream);
+
+/* svae_lds_ragged_perstep_inference_f64 with keep_vjp: keep_vjp = 1 keeps the factor region AND the cross moments W~_t of
+ * all T steps (the KEEPW instantiation of the kernel: a compile-time property, not a branch), then runs the ragged sampler
+ * when S > 0; the records of steps t >= L are those of the decoupled tail, finite.  keep_vjp = 0 is
+ * svae_lds_ragged_perstep_inference_f64.  The forward outputs are the same bits either way.  Error codes of that entry;
+ * -23 keep_vjp outside {0, 1}. */
+int svae_lds_ragged_perstep_inference_keep_f64(int B, int T, int n, int S, int pair_batched, int init_batched, int keep_vjp,
+                                               unsigned options,
+                                               const double* init_J, const double* init_h, const double* init_logZ,
+                                               const double* J11, const double* J12, const double* J22, const double* logZ_pair,
+                                               const double* node_J, const double* node_h, const double* node_logZ,
+                                               const int32_t* lengths, const double* eps, double* samples,
+                                               double* lognorm, double* E_init, double* E_pair,
+                                               double* E_node_diagxx, double* E_node_x,
+                                               int32_t* info, void* workspace, size_t ws_bytes, void* stream);
+
+/* The VJP sweeps w.r.t. the node potentials on the records of the last svae_lds_ragged_perstep_inference_keep_f64
+ * (keep_vjp = 1) call with the same (B,T,n), pair_batched, J12 and `lengths`: the packed ragged sweeps, one route at every
+ * batch size.  J12 (T-1,n,n) or, pair_batched = 1, (B,T-1,n,n): pair t of sequence b reads the caller's block for
+ * t <= L-2 and the zero block of the table in `workspace` behind it -- nothing stored at pairs t >= L-1 is read.
+ * Cotangents of lognorm (B), E_node_diagxx / E_node_x (B,T,n or NULL), E_init (B, n n + n, or NULL), the per-step E_pair
+ * (B,T-1,3,n,n or NULL; with the forward outputs E_pair and E_node_x) and samples (B,T,S,n or NULL, S <= 16, with eps and
+ * samples).  g_E_pair is read under the forward pass's block masks: blocks 0 and 1 of pair t for t <= L-2, block 2 of pair
+ * t-1 for t <= L-1.  Per sequence b: g_node_J[b,:L] and g_node_h[b,:L] are those of the sequence cut at L (pair parameters
+ * [:L-1], node potentials [:L], the init potential whole); g_node_*[b,L:] are exactly 0; g_E_node_*[b,L:], g_samples[b,L:],
+ * eps[b,L:], samples[b,L:], g_E_pair[b,L-1:] and J12 at t >= L-1 are never used (they may be NaN); no result of sequence b
+ * depends on another sequence's length; a length outside 1..T is clamped for addressing.  g_node_logZ[b,t] = g_lognorm[b]
+ * for t < L, else 0 (host side).  Returns 0, or before any HIP call: -1 B, -2 T, -3 n outside 1..SVAE_LDS_MAX_N,
+ * -32 pair_batched outside {0, 1}, -31 lengths NULL, -4 S outside 1..16 with g_samples, -5 J12 NULL with T > 1,
+ * -6 g_lognorm, -8 g_E_pair without E_pair / E_node_x, -10 g_samples without eps / samples, -12 / -13 outputs,
+ * -24 options, -14 workspace NULL or shorter than svae_lds_ragged_perstep_workspace_bytes, -16 vjp_workspace shorter than
+ * svae_lds_vjp_workspace_bytes; B = 0 returns 0 after the checks up to options. */
+int svae_lds_ragged_perstep_vjp_f64(int B, int T, int n, int S, int pair_batched, unsigned options,
+                                    const double* J12, const double* g_lognorm,
+                                    const double* g_E_node_diagxx, const double* g_E_node_x,
+                                    const double* g_E_init, const double* g_E_pair,
+                                    const double* g_samples, const double* eps, const double* samples,
+                                    const double* E_pair, const double* E_node_x,
+                                    const int32_t* lengths, double* g_node_J, double* g_node_h,
+                                    const void* workspace, size_t ws_bytes,
+                                    void* vjp_workspace, size_t vjp_ws_bytes, void* stream);
 
 #ifdef __cplusplus
 }

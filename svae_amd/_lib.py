@@ -168,6 +168,13 @@ SIGNATURES = {
     "svae_lds_ragged_perstep_inference_f64": (ctypes.c_int, [ctypes.c_int] * 6 + [ctypes.c_uint] + [_c_double_p] * 10
                                               + [_c_int_p] + [_c_double_p] * 7
                                               + [_c_int_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]),
+    # ... its forward records for the reverse sweeps (keep_vjp) and the sweeps themselves
+    "svae_lds_ragged_perstep_inference_keep_f64": (ctypes.c_int, [ctypes.c_int] * 7 + [ctypes.c_uint] + [_c_double_p] * 10
+                                                   + [_c_int_p] + [_c_double_p] * 7
+                                                   + [_c_int_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]),
+    "svae_lds_ragged_perstep_vjp_f64": (ctypes.c_int, [ctypes.c_int] * 5 + [ctypes.c_uint] + [_c_double_p] * 11 + [_c_int_p]
+                                        + [_c_double_p] * 2 + [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p,
+                                                               ctypes.c_size_t, ctypes.c_void_p]),
 }
 
 _lib = None

@@ -137,6 +137,12 @@ struct VjpArgs {
   int pg_only;                           // 1: that launch leaves g_node_J / g_node_h alone (another sweep 2 has written them)
   const int32_t* __restrict__ lengths = nullptr;   // ragged launches: (B) per-sequence lengths; J12 is then the two-entry table [real | 0]
 };
+// ragged sweeps on the records of a per-step ragged E-step (svae_lds_ragged_perstep_vjp_f64): J12 is the caller's (T-1,n,n) or
+// (B,T-1,n,n) array (pair_t_stride = n n, pair_seq_stride), read at pairs t <= lengths[b] - 2 only; pairs behind them read
+// qzero.  A derived struct, as LdsPerstepArgs: the kernarg layout of every other launch stays as it is.
+struct VjpPerstepArgs : VjpArgs {
+  const double* __restrict__ qzero = nullptr;   // (n,n) zeros: the first block of the table lds_ragged_qtable_kernel leaves behind the workspace
+};
 // extra scratch of svae_lds_estep_vjp_params_f64 (doubles): g_P, g_R, then -- homogeneous pair parameters -- the per-step
 // batch sums [T-1][3][n*n] that the second reduction pass adds up over time
 constexpr long pg_gp_doubles(int B, int T, int n) { return (long)B * T * n * n; }

@@ -659,22 +659,22 @@ extern "C" int svae_lds_ragged_estep_f64(int B, int T, int n, int inhomog, int p
 
 // per-step pair parameters (T-1,n,n) or, pair_batched, (B,T-1,n,n), and an init potential per batch or, init_batched, per
 // sequence: the packed E-step in its INHOMOG + RAG instantiation; the decoupling set's blocks come from a table behind the
-// uniform workspace layout
-extern "C" int svae_lds_ragged_perstep_estep_f64(int B, int T, int n, int pair_batched, int init_batched, int keep,
-                                                 unsigned options,
-                                                 const double* init_J, const double* init_h, const double* init_logZ,
-                                                 const double* J11, const double* J12, const double* J22, const double* logZ_pair,
-                                                 const double* node_J, const double* node_h, const double* node_logZ,
-                                                 const int32_t* lengths,
-                                                 double* lognorm, double* E_init, double* E_pair,
-                                                 double* E_node_diagxx, double* E_node_x,
-                                                 int32_t* info, void* workspace, size_t ws_bytes, void* stream) {
+// uniform workspace layout.  keep_bits: the bits of `keep` the calling entry point accepts (-23 for any other)
+static int ragged_perstep_estep(int B, int T, int n, int pair_batched, int init_batched, int keep, int keep_bits,
+                                unsigned options,
+                                const double* init_J, const double* init_h, const double* init_logZ,
+                                const double* J11, const double* J12, const double* J22, const double* logZ_pair,
+                                const double* node_J, const double* node_h, const double* node_logZ,
+                                const int32_t* lengths,
+                                double* lognorm, double* E_init, double* E_pair,
+                                double* E_node_diagxx, double* E_node_x,
+                                int32_t* info, void* workspace, size_t ws_bytes, void* stream) {
   if (B < 0) return -1;
   if (T < 1) return -2;
   if (n < 1 || n > SVAE_LDS_MAX_N) return -3;
   if ((pair_batched & ~1) != 0 || (init_batched & ~1) != 0) return -32;
   if (!lengths) return -31;
-  if ((keep & ~1) != 0) return -23;               /* bit 1, the cross moments of the VJP: no sweeps for this route */
+  if ((keep & ~keep_bits) != 0) return -23;
   svae::LdsPerstepArgs a{};
   svae::set_estep_args(a, B, T, n, pair_batched, init_J, init_h, init_logZ, J11, J12, J22, logZ_pair, node_J, node_h, node_logZ,
                        lognorm, E_init, E_pair, E_node_diagxx, E_node_x, info, workspace);
@@ -689,11 +689,27 @@ extern "C" int svae_lds_ragged_perstep_estep_f64(int B, int T, int n, int pair_b
   if (hipGetLastError() != hipSuccess) return -1000;
   /* T = 1: no pair is ever addressed (pair 0 <= L-2 needs L >= 2 > T); the table stands in for the NULL arrays */
   if (T == 1) a.J11 = a.J12 = a.J22 = qtab;
-  a.ws2 = kept_regions(workspace, B, T, n, keep).factor;
+  const Kept kept = kept_regions(workspace, B, T, n, keep);
+  a.ws2 = kept.factor; a.ws3 = kept.cross;        /* (cross moments: with the factor only, the KEEPW instantiation) */
   a.lengths = lengths;
   a.qtab = qtab;
   a.init_batched = init_batched;
   return estep_units[n]->ragged_perstep(a, stream);
+}
+
+extern "C" int svae_lds_ragged_perstep_estep_f64(int B, int T, int n, int pair_batched, int init_batched, int keep,
+                                                 unsigned options,
+                                                 const double* init_J, const double* init_h, const double* init_logZ,
+                                                 const double* J11, const double* J12, const double* J22, const double* logZ_pair,
+                                                 const double* node_J, const double* node_h, const double* node_logZ,
+                                                 const int32_t* lengths,
+                                                 double* lognorm, double* E_init, double* E_pair,
+                                                 double* E_node_diagxx, double* E_node_x,
+                                                 int32_t* info, void* workspace, size_t ws_bytes, void* stream) {
+  /* keep bit 1, the cross moments of the VJP, is refused here: svae_lds_ragged_perstep_inference_keep_f64 keeps them */
+  return ragged_perstep_estep(B, T, n, pair_batched, init_batched, keep, 1, options, init_J, init_h, init_logZ, J11, J12, J22,
+                              logZ_pair, node_J, node_h, node_logZ, lengths, lognorm, E_init, E_pair, E_node_diagxx, E_node_x,
+                              info, workspace, ws_bytes, stream);
 }
 
 static int ragged_sample(int B, int T, int n, int S, const double* eps, double* samples, const int32_t* lengths,
@@ -740,6 +756,68 @@ extern "C" int svae_lds_ragged_perstep_inference_f64(int B, int T, int n, int S,
                                                    stream);
   if (rc != 0 || S == 0 || B == 0) return rc;
   return ragged_sample(B, T, n, S, eps, samples, lengths, workspace, stream);
+}
+
+// svae_lds_ragged_perstep_inference_f64 with keep_vjp: the E-step keeps the factor region and the cross moments W~_t (its
+// KEEPW instantiation), then the ragged sampler runs when S > 0 -- the records svae_lds_ragged_perstep_vjp_f64 reads
+extern "C" int svae_lds_ragged_perstep_inference_keep_f64(int B, int T, int n, int S, int pair_batched, int init_batched,
+                                                          int keep_vjp, unsigned options,
+                                                          const double* init_J, const double* init_h, const double* init_logZ,
+                                                          const double* J11, const double* J12, const double* J22,
+                                                          const double* logZ_pair,
+                                                          const double* node_J, const double* node_h, const double* node_logZ,
+                                                          const int32_t* lengths, const double* eps, double* samples,
+                                                          double* lognorm, double* E_init, double* E_pair,
+                                                          double* E_node_diagxx, double* E_node_x,
+                                                          int32_t* info, void* workspace, size_t ws_bytes, void* stream) {
+  if (n < 1 || n > SVAE_LDS_MAX_N) return -3;
+  if (S < 0 || (S > 0 && (!eps || !samples))) return -4;
+  if (keep_vjp != 0 && keep_vjp != 1) return -23;
+  const int rc = ragged_perstep_estep(B, T, n, pair_batched, init_batched, keep_vjp ? 3 : (S > 0 ? 1 : 0), 3, options, init_J,
+                                      init_h, init_logZ, J11, J12, J22, logZ_pair, node_J, node_h, node_logZ, lengths, lognorm,
+                                      E_init, E_pair, E_node_diagxx, E_node_x, info, workspace, ws_bytes, stream);
+  if (rc != 0 || S == 0 || B == 0) return rc;
+  return ragged_sample(B, T, n, S, eps, samples, lengths, workspace, stream);
+}
+
+// the packed ragged sweeps on the records of svae_lds_ragged_perstep_inference_keep_f64(keep_vjp = 1): J12 is the caller's
+// per-step array, the zero block of the tail's pairs is the one the forward pass left behind the workspace
+extern "C" int svae_lds_ragged_perstep_vjp_f64(int B, int T, int n, int S, int pair_batched, unsigned options,
+                                               const double* J12, const double* g_lognorm,
+                                               const double* g_E_node_diagxx, const double* g_E_node_x,
+                                               const double* g_E_init, const double* g_E_pair,
+                                               const double* g_samples, const double* eps, const double* samples,
+                                               const double* E_pair, const double* E_node_x,
+                                               const int32_t* lengths, double* g_node_J, double* g_node_h,
+                                               const void* workspace, size_t ws_bytes,
+                                               void* vjp_workspace, size_t vjp_ws_bytes, void* stream) {
+  if (B < 0) return -1;
+  if (T < 1) return -2;
+  if (n < 1 || n > SVAE_LDS_MAX_N) return -3;
+  if ((pair_batched & ~1) != 0) return -32;
+  if (!lengths) return -31;
+  if (g_samples && (S < 1 || S > 16)) return -4;
+  if (T > 1 && !J12) return -5;
+  if (!g_lognorm) return -6;
+  if (g_E_pair && (!E_pair || !E_node_x)) return -8;      /* S~_{t+1} is read back from the forward outputs */
+  if (g_samples && (!eps || !samples)) return -10;
+  if (!g_node_J) return -12;
+  if (!g_node_h) return -13;
+  Selection sel;
+  if (!decode_options(options, B, &sel)) return -24;
+  if (B == 0) return 0;
+  if (!workspace || ws_bytes < svae_lds_ragged_perstep_workspace_bytes(B, T, n)) return -14;
+  if (!vjp_workspace || vjp_ws_bytes < svae_lds_vjp_workspace_bytes(B, T, n)) return -16;
+  svae::VjpPerstepArgs a{};
+  static_cast<svae::VjpArgs&>(a) = vjp_args(B, T, n, S, 0, g_lognorm, g_E_node_diagxx, g_E_node_x, g_samples, eps, samples,
+                                            g_node_J, g_node_h, workspace, vjp_workspace);
+  a.J12 = J12;
+  a.pair_t_stride = (long)n * n;
+  a.pair_seq_stride = pair_batched ? (long)(T - 1) * n * n : 0;
+  a.g_E_init = g_E_init; a.g_E_pair = T > 1 ? g_E_pair : nullptr; a.E_pair = E_pair; a.E_node_x = E_node_x;
+  a.lengths = lengths;
+  a.qzero = (const double*)((const char*)workspace + ragged_table_offset_bytes(B, T, n));   /* [0 | -1/2 I], left by the forward pass */
+  return vjp_units[n]->vjp_ragged_perstep(a, stream);
 }
 
 extern "C" int svae_lds_ragged_vjp_f64(int B, int T, int n, int S, int inhomog, int pair_batched, unsigned options,

@@ -192,10 +192,15 @@ __device__ __forceinline__ void load_row(const double* __restrict__ p, double (&
 // pairs t <= L-2 -- (T-1,n,n), or (B,T-1,n,n) with pair_seq_stride -- and the table a.qtab = [0 | -1/2 I] at pairs t >= L-1: per
 // step a pointer select between the two, so nothing the caller stored at t >= L-1 is read (logZ_pair included).  The init
 // potential may come per sequence (a.init_batched); the per-step pair statistics of pairs t >= L-1 are written as 0.
-template <int N, bool INHOMOG, bool CHOL, bool FILT = false, bool RAG = false>
+// KEEPW (RAG with INHOMOG and CHOL only; svae_lds_ragged_perstep_inference_keep_f64): the launch also keeps the cross moments
+// W~_t of all T steps in a.ws3 for the reverse sweeps (lds_vjp_kernel.hpp) -- the tail's are those of the decoupled chain,
+// finite.  A compile-time property: the store sits between the two DPP stages of the backward step, and as a run-time
+// branch it would put a block entry there.
+template <int N, bool INHOMOG, bool CHOL, bool FILT = false, bool RAG = false, bool KEEPW = false>
 __global__ __launch_bounds__(64) void lds_estep_kernel(const std::conditional_t<RAG && INHOMOG, LdsPerstepArgs, LdsArgs> a) {
   static_assert(N >= 1 && N <= SVAE_LDS_MAX_N, "n+1 lanes must fit a 16-lane DPP row");
   static_assert(!(RAG && FILT), "ragged launches: whole E-step");
+  static_assert(!KEEPW || (RAG && INHOMOG && CHOL), "KEEPW: the per-step ragged E-step with its factor region");
   constexpr bool PERSTEP = INHOMOG || RAG;      // the pair blocks are (re)loaded every step
   constexpr bool RPS = RAG && INHOMOG;          // ragged launch with per-step pair blocks
   constexpr int IL = SVAE_IL;
@@ -479,6 +484,10 @@ __global__ __launch_bounds__(64) void lds_estep_kernel(const std::conditional_t<
     double W[N + 1];
     static_for<0, N + 1>([&](auto i) { W[i] = 0.0; });
     static_for<0, (N + 1 + IL - 1) / IL>([&](auto g) { rows_src_bcast<IL, g * IL, N + 1, N>(W, S, H); });
+    if constexpr (KEEPW) {  // W~_t kept unconditionally (rows 0..N, lanes 0..N): no branch on a.ws3, no block entry
+      double* w3 = a.ws3 + ((long)bq * T + t) * (N + 1) * HS + c;
+      if (sth) static_for<0, N + 1>([&](auto i) { w3[i * HS] = W[i]; });
+    } else
     if constexpr (!RPS) {   // (RPS keeps no cross moments: without the branch no block entry sits between the two DPP stages)
     if (a.ws3) {   // VJP mode: keep W~_t (rows 0..N, lanes 0..N)
       double* w3 = a.ws3 + ((long)bq * T + t) * (N + 1) * HS + c;
@@ -616,7 +625,11 @@ static int launch_estep_ragged(const LdsArgs& a, hipStream_t stream) {
 template <int N>
 static int launch_estep_ragged_perstep(const LdsPerstepArgs& a, hipStream_t stream) {
   dim3 grid((a.B + 3) / 4), block(64);
-  if (a.ws2 != nullptr) hipLaunchKernelGGL((lds_estep_kernel<N, true, true, false, true>), grid, block, 0, stream, a);
+  if (a.ws3 != nullptr) {    // records for the reverse sweeps: factor region and cross moments together
+    if (a.ws2 == nullptr) return -1002;
+    hipLaunchKernelGGL((lds_estep_kernel<N, true, true, false, true, true>), grid, block, 0, stream, a);
+  }
+  else if (a.ws2 != nullptr) hipLaunchKernelGGL((lds_estep_kernel<N, true, true, false, true>), grid, block, 0, stream, a);
   else hipLaunchKernelGGL((lds_estep_kernel<N, true, false, false, true>), grid, block, 0, stream, a);
   return hipGetLastError() == hipSuccess ? 0 : -1000;
 }

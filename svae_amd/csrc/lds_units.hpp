@@ -44,6 +44,8 @@ struct VjpUnit {
   int (*vjp)(const VjpArgs&, void* stream);
   int (*vjp_lean)(const VjpArgs&, void* stream);      // LEAN.  the two sweeps on the lean records of svae_lds_inference_f64
   int (*vjp_ragged)(const VjpArgs&, void* stream);    // svae_lds_ragged_vjp_f64: the packed sweeps, ragged instantiations
+  // svae_lds_ragged_perstep_vjp_f64: the packed ragged sweeps on per-step pair parameters, statistics cotangents included
+  int (*vjp_ragged_perstep)(const VjpPerstepArgs&, void* stream);
 };
 
 // ---- host helpers of the E-step-like entry points (lds_estep.hip, lds_estep_xl.hip) ---------------------------------

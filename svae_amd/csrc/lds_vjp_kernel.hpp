@@ -409,10 +409,13 @@ __device__ __forceinline__ void s1_role0_pair_consumer(const VjpArgs& a, const d
 // RAG (a.lengths; packed one-workgroup form only): the cotangents, eps and x_{t+1} of steps t >= lengths[b] are never used
 // (select, not multiply: they may be NaN), so the adjoint records of the tail stay finite and those of the real steps are
 // the truncated chain's.
+// RAG with STATC (records of the per-step ragged E-step, svae_lds_ragged_perstep_vjp_f64): the cotangents of E_init and of the
+// per-step E_pair under the forward pass's block masks -- blocks 0 and 1 of pair t for t <= lengths[b] - 2, block 2 of pair
+// t-1 for t <= lengths[b] - 1 -- again by select: g_E_pair[b, lengths[b]-1:] may be NaN.
 template <int N, bool SAMP, bool STATC, bool SPLIT, bool PROD, int ROLE, bool RAG = false>
 __device__ __forceinline__ void lds_vjp_sweep1_body(const VjpArgs& a, double* tabs, double* ring, double* mail,
                                                     const int grp) {
-  static_assert(!RAG || (!STATC && !SPLIT && !PROD && ROLE == 2), "ragged launches: the packed sweep");
+  static_assert(!RAG || (!SPLIT && !PROD && ROLE == 2), "ragged launches: the packed sweep");
   constexpr int HS = ws_h_stride(N), PS = ws_p_stride(N), WS = ws_step_doubles(N);
   constexpr int AS = vjp_step_doubles(N);
   constexpr int W3 = (N + 1) * HS, R1 = N * HS + N * N + N;
@@ -698,11 +701,13 @@ __device__ __forceinline__ void lds_vjp_sweep1_body(const VjpArgs& a, double* ta
         double q = 0.0;
         if (a.g_E_pair && t < T - 1) {
           const double* gp = a.g_E_pair + ((long)b * (T - 1) + t) * 3 * nn;
-          q += gp[i * N + cc] + gp[cc * N + i];
+          const double v = gp[i * N + cc] + gp[cc * N + i];
+          q += (!RAG || t <= len - 2) ? v : 0.0;
         }
         if (a.g_E_pair && t > 0) {
           const double* gp = a.g_E_pair + ((long)b * (T - 1) + t - 1) * 3 * nn + 2 * nn;
-          q += gp[i * N + cc] + gp[cc * N + i];
+          const double v = gp[i * N + cc] + gp[cc * N + i];
+          q += (!RAG || t <= len - 1) ? v : 0.0;
         }
         if (a.g_E_init && t == 0) {
           const double* gi = a.g_E_init + (long)b * (nn + N);
@@ -722,8 +727,8 @@ __device__ __forceinline__ void lds_vjp_sweep1_body(const VjpArgs& a, double* ta
         const double* gc = a.g_E_pair + ((long)b * (T - 1) + t) * 3 * nn + nn;
         static_for<0, N>([&](auto i) {
           const double v = gc[i * N + cc], vt = gc[cc * N + i];
-          Cb[i] = col ? v : 0.0;                      // row i of Cb
-          CbT[i] = col ? vt : 0.0;                    // row i of Cb'
+          Cb[i] = (col && (!RAG || t <= len - 2)) ? v : 0.0;       // row i of Cb
+          CbT[i] = (col && (!RAG || t <= len - 2)) ? vt : 0.0;     // row i of Cb'
         });
       }
     }
@@ -923,10 +928,14 @@ __global__ __launch_bounds__(64 * VJP_S1_WAVES) void lds_vjp_sweep1_prod_kernel(
 // RAG (a.lengths; packed form only): J12 of pair t is entry (t <= lengths[b] - 2 ? 0 : 1) of the two-entry table [real | 0]
 // -- the tail's adjoint reaches the last real step through a zero block -- and the gradients at t >= lengths[b] are written
 // as 0 (the tail's own, g_lognorm E[x_t^2] = g_lognorm, belongs to a potential that does not exist).
-template <int N, bool SAMP, bool SPLIT, bool PROD, bool PGR = false, bool RAG = false>
-__device__ __forceinline__ void lds_vjp_sweep2_body(const VjpArgs& a) {
+// RPS (RAG on per-step pair parameters, VjpPerstepArgs): J12 of pair t by a pointer select, as the forward kernel does it --
+// the caller's block t (of sequence b with pair_seq_stride) for t <= lengths[b] - 2, else the zero block qz; nothing the
+// caller stored at pairs t >= lengths[b] - 1 is read.
+template <int N, bool SAMP, bool SPLIT, bool PROD, bool PGR = false, bool RAG = false, bool RPS = false>
+__device__ __forceinline__ void lds_vjp_sweep2_body(const VjpArgs& a, const double* qz = nullptr) {
   static_assert(!(PGR && PROD), "the packed sweep writes the parameter cotangents");
   static_assert(!RAG || (!SPLIT && !PROD && !PGR), "ragged launches: the packed sweep");
+  static_assert(!RPS || RAG, "per-step pair parameters with lengths");
   constexpr int HS = ws_h_stride(N), PS = ws_p_stride(N), WS = ws_step_doubles(N);
   constexpr int AS = vjp_step_doubles(N);
   constexpr int REC = WS + AS;                 // doubles per (sequence, step) in a ring slot
@@ -1067,7 +1076,8 @@ __device__ __forceinline__ void lds_vjp_sweep2_body(const VjpArgs& a) {
     // [Xbar | cbar] -= J12_t [Abar | hbar]_{t+1}
     if (t < T - 1) {
       if (RAG || a.pair_t_stride != 0) {
-        const double* pj = RAG ? pJ12 + (t <= len - 2 ? 0 : N * N) : pJ12 + (long)t * a.pair_t_stride;
+        const double* pj = RPS ? (t <= len - 2 ? pJ12 + (long)t * N * N : qz)
+                               : RAG ? pJ12 + (t <= len - 2 ? 0 : N * N) : pJ12 + (long)t * a.pair_t_stride;
         static_for<0, N>([&](auto i) { const double v = pj[i * N + (col ? c : 0)]; J12c[i] = col ? -v : 0.0; });
         dpp_fence(J12c);
       }
@@ -1398,6 +1408,11 @@ template <int N, bool SAMP, bool SPLIT, bool PGR = false, bool RAG = false>
 __global__ __launch_bounds__(64) void lds_vjp_sweep2_kernel(const VjpArgs a) {
   lds_vjp_sweep2_body<N, SAMP, SPLIT, false, PGR, RAG>(a);
 }
+// the ragged sweep on per-step pair parameters (RPS)
+template <int N, bool SAMP>
+__global__ __launch_bounds__(64) void lds_vjp_sweep2_perstep_kernel(const VjpPerstepArgs a) {
+  lds_vjp_sweep2_body<N, SAMP, false, false, false, true, true>(a, a.qzero);
+}
 // consumer wavefront + four producer wavefronts
 template <int N, bool SAMP, bool SPLIT>
 __global__ __launch_bounds__(320) void lds_vjp_sweep2_prod_kernel(const VjpArgs a) {
@@ -1414,6 +1429,25 @@ static int launch_vjp_ragged(const VjpArgs& a, hipStream_t stream) {
   } else {
     hipLaunchKernelGGL((lds_vjp_sweep1_kernel<N, false, false, false, true>), grid, block, 0, stream, a);
     hipLaunchKernelGGL((lds_vjp_sweep2_kernel<N, false, false, false, true>), grid, block, 0, stream, a);
+  }
+  return hipGetLastError() == hipSuccess ? 0 : -1000;
+}
+
+// per-sequence lengths on the records of the per-step ragged E-step (a.lengths, a.qzero; J12 the caller's per-step array):
+// the packed sweeps at every batch size, sweep 1 with the statistics cotangents when one is given
+template <int N>
+static int launch_vjp_ragged_perstep(const VjpPerstepArgs& a, hipStream_t stream) {
+  dim3 grid((a.B + 3) / 4), block(64);
+  const bool statc = a.g_E_init || a.g_E_pair;
+  const VjpArgs& a1 = a;                       // sweep 1 does not touch J12
+  if (a.g_samples) {
+    if (statc) hipLaunchKernelGGL((lds_vjp_sweep1_kernel<N, true, true, false, true>), grid, block, 0, stream, a1);
+    else hipLaunchKernelGGL((lds_vjp_sweep1_kernel<N, true, false, false, true>), grid, block, 0, stream, a1);
+    hipLaunchKernelGGL((lds_vjp_sweep2_perstep_kernel<N, true>), grid, block, 0, stream, a);
+  } else {
+    if (statc) hipLaunchKernelGGL((lds_vjp_sweep1_kernel<N, false, true, false, true>), grid, block, 0, stream, a1);
+    else hipLaunchKernelGGL((lds_vjp_sweep1_kernel<N, false, false, false, true>), grid, block, 0, stream, a1);
+    hipLaunchKernelGGL((lds_vjp_sweep2_perstep_kernel<N, false>), grid, block, 0, stream, a);
   }
   return hipGetLastError() == hipSuccess ? 0 : -1000;
 }

@@ -20,7 +20,11 @@
 static int vjp(const svae::VjpArgs& a, void* stream) { return svae::launch_vjp<SVAE_N>(a, (hipStream_t)stream); }
 static int vjp_lean(const svae::VjpArgs& a, void* stream) { return svae::launch_vjp_lean<SVAE_N>(a, (hipStream_t)stream); }
 static int vjp_ragged(const svae::VjpArgs& a, void* stream) { return svae::launch_vjp_ragged<SVAE_N>(a, (hipStream_t)stream); }
+static int vjp_ragged_perstep(const svae::VjpPerstepArgs& a, void* stream) {
+  return svae::launch_vjp_ragged_perstep<SVAE_N>(a, (hipStream_t)stream);
+}
 
 #ifndef __HIP_DEVICE_COMPILE__   /* host data: a const table with a constant initialiser would be emitted for the device too */
-extern "C" const svae::VjpUnit SVAE_CAT(svae_lds_vjp_unit_n, SVAE_N) = {.vjp = vjp, .vjp_lean = vjp_lean, .vjp_ragged = vjp_ragged};
+extern "C" const svae::VjpUnit SVAE_CAT(svae_lds_vjp_unit_n, SVAE_N) = {.vjp = vjp, .vjp_lean = vjp_lean, .vjp_ragged = vjp_ragged,
+  .vjp_ragged_perstep = vjp_ragged_perstep};
 #endif

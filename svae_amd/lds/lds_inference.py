@@ -168,12 +168,15 @@ class LDSEStepPlan(object):
         self.epoch = -1
         self._kept()             # (epoch 0: nothing launched, nothing kept)
 
-    def _kept(self, J12=None, pair_batched=False, has_factor=False, has_cross=False, lean=False, infer_S=None, lengths=None):
+    def _kept(self, J12=None, pair_batched=False, has_factor=False, has_cross=False, lean=False, infer_S=None, lengths=None,
+              perstep=False):
         """What the launch that just succeeded left behind, all of it at once -- called after EVERY forward launch and from
         nowhere else, so that no field survives from the launch before.  has_factor / has_cross: the records `sample()` /
         `vjp()` read; lean: `infer()` kept lean records; infer_S: the number of samples `infer()` drew (it fixes the record
-        format), None after every other launch; lengths: (B,) int32 device tensor while the records are ragged ones."""
+        format), None after every other launch; lengths: (B,) int32 device tensor while the records are ragged ones;
+        perstep: ragged records of per-step pair parameters (the sweeps of svae_lds_ragged_perstep_vjp_f64 read them)."""
         self.epoch += 1
+        self._perstep = bool(perstep)
         self.has_factor, self.has_cross, self.lean, self._infer_S = bool(has_factor), bool(has_cross), bool(lean), infer_S
         self._J12, self._pair_batched, self._lengths = J12, bool(pair_batched), lengths
         # E_pair's fourth entry after a ragged launch: the sequence's own number of pairs
@@ -283,9 +286,11 @@ class LDSEStepPlan(object):
         self._kept(J12, pair_batched, has_factor=keep_factor, lengths=lengths)       # (no cross moments: vjp() refuses)
 
     def infer_ragged_perstep(self, init_J, init_h, init_logZ, J11, J12, J22, logZ_pair, node_J, node_h, node_logZ=None,
-                             lengths=None, pair_batched=False, init_batched=False, eps=None, out=None):
+                             lengths=None, pair_batched=False, init_batched=False, eps=None, out=None, keep_vjp=False):
         """launch_ragged_perstep + the ragged sampler in one call (svae_lds_ragged_perstep_inference_f64).  eps (B,T,S,n) or
-        None -> samples (0 at t >= lengths[b]; eps there is never read) or None."""
+        None -> samples (0 at t >= lengths[b]; eps there is never read) or None.
+        keep_vjp=True (svae_lds_ragged_perstep_inference_keep_f64): the same outputs, and the launch keeps the factor region
+        and the cross moments, so that `vjp()` can follow -- with g_E_init / g_E_pair, without dense_out / param_out."""
         S = 0
         if eps is not None:
             eps = self._checked_eps(eps)
@@ -294,6 +299,11 @@ class LDSEStepPlan(object):
         lengths = self._ragged_perstep(lengths, "infer_ragged_perstep", pair_batched, init_batched, model)
         if S and out is None:
             out = torch.empty_like(eps)
+        if keep_vjp:
+            self._forward("svae_lds_ragged_perstep_inference_keep_f64", (self.B, self.T, self.n, S, int(bool(pair_batched)),
+                          int(bool(init_batched)), 1, self.options), model + (lengths, eps, out))
+            self._kept(J12, pair_batched, has_factor=True, has_cross=True, lengths=lengths, perstep=True)
+            return out if eps is not None else None
         self._forward("svae_lds_ragged_perstep_inference_f64", (self.B, self.T, self.n, S, int(bool(pair_batched)),
                       int(bool(init_batched)), self.options), model + (lengths, eps, out))
         self._kept(J12, pair_batched, has_factor=S > 0, lengths=lengths)
@@ -454,7 +464,9 @@ class LDSEStepPlan(object):
         node gradients are the same bits as without it.
         lengths: after a launch with per-sequence lengths the sweeps are the ragged ones (svae_lds_ragged_vjp_f64) with the
         lengths of that launch -- passing them again is optional (they must be the same); the cotangents at
-        t >= lengths[b] are never used, the gradients there are 0.  No statistics cotangents, dense_out or param_out."""
+        t >= lengths[b] are never used, the gradients there are 0.  No statistics cotangents, dense_out or param_out.
+        After infer_ragged_perstep(..., keep_vjp=True) the sweeps are those of svae_lds_ragged_perstep_vjp_f64: g_E_init and
+        the per-step g_E_pair are accepted (g_E_pair[b, lengths[b]-1:] is never used), dense_out / param_out are not."""
         self._no_xl("vjp()")
         ragged = self._lengths is not None
         if lengths is not None and not ragged:
@@ -465,7 +477,7 @@ class LDSEStepPlan(object):
             if param_out or dense_out is not None:
                 raise ValueError("vjp() after a launch with lengths: no parameter gradients (param_out / natparam_grad) and "
                                  "no dense node-potential cotangents")
-            if g_E_init is not None or g_E_pair is not None:
+            if (g_E_init is not None or g_E_pair is not None) and not self._perstep:
                 raise ValueError("vjp() after a launch with lengths: no cotangents of E_init / E_pair (pair_stats_grad)")
         lean = self.lean
         if param_out:
@@ -520,6 +532,11 @@ class LDSEStepPlan(object):
         gh = torch.empty(B, T, n, **f64)
         p = _lib.ptr
         workspaces = [p(self.ws), self.ws_bytes, p(self.vjp_ws), self.vjp_ws_bytes, _lib.current_stream(self.device)]
+        if ragged and self._perstep:
+            self._call("svae_lds_ragged_perstep_vjp_f64", [B, T, n, S, int(self._pair_batched), self.options] + _lib.ptrs(
+                (self._J12, g_lognorm, g_E_node_diagxx, g_E_node_x, g_E_init, g_E_pair, g_samples, eps, samples,
+                 self.E_pair, self.E_node_x, self._lengths, gJ, gh)) + workspaces)
+            return gJ, gh
         if ragged:
             self._call("svae_lds_ragged_vjp_f64", [B, T, n, S, 0, 0, self.options] + _lib.ptrs(
                 (g_lognorm, g_E_node_diagxx, g_E_node_x, g_samples, eps, samples, self._lengths, gJ, gh)) + workspaces)
@@ -1062,6 +1079,37 @@ class _LDSInference(torch.autograd.Function):
                 gz = torch.where(plan.live(), gz, torch.zeros_like(gz))
             return gJ, gh, gz, None, None, None, None, None
         return gJ, gh, gz, None, None, None, None
+
+
+class _LDSRaggedPerstepInference(torch.autograd.Function):
+    """_LDSInference for a ragged batch with per-step pair parameters (the final pass of the ragged SLDS): forward
+    infer_ragged_perstep(keep_vjp=True), backward ONE vjp() call with the cotangents of E_init and of the per-step E_pair.
+    Differentiable w.r.t. the node potentials, once; the pair parameters and the init potential are fixed inputs."""
+
+    @staticmethod
+    def forward(ctx, node_J, node_h, node_logZ, eps, plan, params, lengths, pair_batched, init_batched):
+        samples = plan.infer_ragged_perstep(*params, node_J, node_h, node_logZ, lengths=lengths, pair_batched=pair_batched,
+                                            init_batched=init_batched, eps=eps, keep_vjp=True)
+        if samples is None:
+            samples = torch.zeros(0, dtype=torch.float64, device=plan.device)
+        ctx.plan, ctx.has_logZ, ctx.has_samples = plan, node_logZ is not None, eps is not None
+        ctx.epoch = plan.epoch
+        ctx.set_materialize_grads(False)
+        ctx.save_for_backward(eps if eps is not None else samples, samples)
+        # (copies: vjp() reads S~_{t+1} back from the plan's own E_pair / E_node_x, which must not move)
+        return (plan.lognorm.clone(), plan.E_node_diagxx.clone(), plan.E_node_x.clone(), samples, plan.E_init.clone(),
+                plan.E_pair.clone())
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g_lognorm, g_dxx, g_x, g_samples, g_init, g_pair):
+        plan, g_lognorm, sampled = _backward_prologue(ctx, g_lognorm, g_samples)
+        gJ, gh = plan.vjp(g_lognorm, g_dxx, g_x, *sampled, g_init, g_pair)
+        gz = None
+        if ctx.has_logZ:            # (select: the cotangent of a step that does not exist is not propagated)
+            gz = g_lognorm[:, None].expand(plan.B, plan.T)
+            gz = torch.where(plan.live(), gz, torch.zeros_like(gz))
+        return gJ, gh, gz, None, None, None, None, None, None
 
 
 class _LDSInferenceParams(torch.autograd.Function):

@@ -33,6 +33,9 @@ Every result up to L is that of the sequence cut at L; samples, node statistics 
 statistics from L-1 on are exactly 0, labels from L on are -1 (and ignored on input); nothing stored from L on is read (it
 may be NaN).  The SLDS has no one-step sequence: a length outside 2..T is clamped on the device and recorded in a status
 word that check_info() reports; the host never reads `lengths`.
+Gradients of a ragged batch: run_inference_ragged_differentiable and run_inference_withlabels_ragged_differentiable (the
+`lengths=` of their uniform namesakes keeps refusing): the ragged ascent on detached values, then the final pass through
+the ragged per-step E-step with kept records and its reverse sweeps; gradients w.r.t. nn_potentials at t >= L are exactly 0.
 """
 import numpy as np
 import torch
@@ -41,7 +44,8 @@ from .. import _lib
 from ..distributions import expfam
 from ..parallel import allreduce_nested
 from ..hmm.hmm_inference import hmm_estep, hmm_logZ_differentiable, hmm_sample, hmm_viterbi
-from ..lds.lds_inference import LDSEStepPlan, _estep, lds_inference_differentiable, natural_lds_sample
+from ..lds.lds_inference import LDSEStepPlan, _LDSRaggedPerstepInference, _estep, lds_inference_differentiable, \
+    natural_lds_sample
 
 
 _STATUS = {}     # (path name, device) -> (1,) int32 status word, PERSISTENT per device: every call of the path ORs into it
@@ -1038,10 +1042,10 @@ def run_inference_differentiable(prior_natparam, global_natparam, nn_potentials,
     each (B,T,n): the local mean field is optimised on detached values (the reference's `unbox`),
     then the final pass is differentiated through the E-step / sampler VJP kernels and the HMM
     kernel.  -> (samples (B,T,S,n), expected_stats, global_vlb, local_vlb).
-    lengths: not supported (the VJP sweeps have no form for per-step pair parameters with lengths): ValueError."""
+    lengths: not taken here -- ValueError; a ragged batch trains through run_inference_ragged_differentiable."""
     if lengths is not None:
-        raise ValueError("run_inference_differentiable(lengths=): no gradients for a ragged SLDS batch -- the VJP sweeps for "
-                         "per-step pair parameters with lengths are not built (run_inference(lengths=) gives forward values)")
+        raise ValueError("run_inference_differentiable(lengths=): not taken by this function -- the gradients of a ragged "
+                         "SLDS batch come from run_inference_ragged_differentiable(..., lengths, ...)")
     dev = nn_potentials[1].device
     node_d = tuple(_dev64(x, dev) for x in nn_potentials)
     B, T, n = node_d[1].shape
@@ -1069,10 +1073,10 @@ def run_inference_withlabels_differentiable(prior_natparam, global_natparam, pot
     mean-field step runs on detached values (the reference's `unbox`, :319), the final E-step + sampler is
     differentiated through the VJP kernels.  The signature make_gradfun calls with `recognize` returning
     (nn_potentials, labels).  -> (samples (B,T,S,n), expected_stats, global_vlb, local_vlb).
-    lengths: not supported (see run_inference_differentiable): ValueError."""
+    lengths: not taken here -- ValueError; see run_inference_withlabels_ragged_differentiable."""
     if lengths is not None:
-        raise ValueError("run_inference_withlabels_differentiable(lengths=): no gradients for a ragged SLDS batch -- the VJP "
-                         "sweeps for per-step pair parameters with lengths are not built")
+        raise ValueError("run_inference_withlabels_differentiable(lengths=): not taken by this function -- the gradients of a "
+                         "ragged SLDS batch come from run_inference_withlabels_ragged_differentiable(..., lengths, ...)")
     nn_potentials, labels = potentials_and_labels
     dev = nn_potentials[1].device
     node_d = tuple(_dev64(x, dev) for x in nn_potentials)
@@ -1088,6 +1092,100 @@ def run_inference_withlabels_differentiable(prior_natparam, global_natparam, pot
     pair_stats = tuple(E_pair[:, :, i].detach() for i in range(3))
     expected_stats = get_global_stats(hmm_stats, init_stats, pair_stats)
     local_vlb = (lognorm - ((nJ * dxx).sum((1, 2)) + (nh * ex).sum((1, 2)))).sum()
+    expected_stats, local_vlb = allreduce_nested(expected_stats, local_vlb, group)
+    global_vlb = slds_prior_vlb(host_params[0], host_params[1], dev)
+    return samples, expected_stats, global_vlb, local_vlb
+
+
+def _ragged_lds_final_pass_differentiable(lds_natparam, nn_potentials, eps, lens, reference_compat=True):
+    """_lds_final_pass_differentiable for a ragged batch: the per-step ragged E-step + sampler with kept records
+    (_LDSRaggedPerstepInference) on FIXED mean-field natural parameters, the per-sequence init potential passed whole (no
+    fold into J11[:, 0], the wrong pair for a sequence whose pair 0 is the decoupling set).
+    -> (lognorm (B), (E diag xx', E x), samples, (E_init, E_pair), plan)"""
+    nJ, nh = nn_potentials[0], nn_potentials[1]
+    dev = nh.device
+    B, T, n = nh.shape
+    (J0, h0, a0, b0), pair = lds_natparam
+    c = lambda x: x.detach().to(device=dev, dtype=torch.float64).contiguous()
+    params = (c(J0), c(h0), c(a0) if reference_compat else c(a0 + b0)) + tuple(c(x) for x in pair)
+    plan = _ragged_plan(B, T, n, dev)
+    g = lambda x: x.to(device=dev, dtype=torch.float64).contiguous()
+    lognorm, dxx, ex, samples, E_init, E_pair = _LDSRaggedPerstepInference.apply(
+        g(nJ), g(nh), None, eps if eps.shape[2] > 0 else None, plan, params, lens, True, True)
+    return lognorm, (dxx, ex), samples if eps.shape[2] > 0 else eps, (E_init, E_pair), plan
+
+
+def run_inference_ragged_differentiable(prior_natparam, global_natparam, nn_potentials, lengths, num_samples, init_eps=None,
+                                        eps=None, generator=None, tol=1e-2, group=None, reference_compat=True):
+    """run_inference_differentiable for one padded batch of sequences with per-sequence lengths (B,) (module docstring;
+    n <= 15, K <= 64, diagonal (B,T,n) potentials): the ragged ascent of optimize_local_meanfield(lengths=) on detached
+    values, then the final pass with gradients attached to nn_potentials = (J, h) -- the per-step ragged LDS E-step +
+    sampler with kept records and its reverse sweeps, the HMM bound through get_arhmm_local_nodeparams and
+    hmm_logZ_differentiable(lengths=), the local bound with the potentials at t >= L removed by select.
+    -> (samples (B,T,S,n), expected_stats, global_vlb, local_vlb), the values of run_inference(lengths=); the gradients
+    w.r.t. nn_potentials[b, L:] are exactly 0 and nothing stored there (NaN included) reaches a value or a gradient."""
+    dev = nn_potentials[1].device
+    lens = _slds_lengths(lengths, global_natparam, nn_potentials, False, "run_inference_ragged_differentiable")
+    node_d = tuple(_dev64(x, dev) for x in nn_potentials)
+    B, T, n = node_d[1].shape
+    if init_eps is None:
+        init_eps = torch.randn(B, T, 1, n, dtype=torch.float64, device=dev, generator=generator)
+    host_params = (_HostParamsLater(global_natparam), _HostParamsLater(prior_natparam))
+    maps = global_to_local_maps(global_natparam, dev)
+    (hmm_stats, _), (hmm_nat, lds_nat), _, _ = optimize_local_meanfield(
+        global_natparam, node_d, init_eps, tol, pair_stats=False, reference_compat=reference_compat, local_maps=maps,
+        lengths=lens)
+    if eps is None:
+        eps = torch.randn(B, T, int(num_samples), n, dtype=torch.float64, device=dev, generator=generator)
+    samples, (init_stats, E_pair), local_vlb = ragged_final_pass_differentiable(
+        hmm_nat, lds_nat, (nn_potentials[0], nn_potentials[1]), _dev64(eps, dev), lens, maps, reference_compat)
+    # (E_states[b, L:] and E_pair[b, L-1:] are exactly 0: the weighted sums and the pair count need no mask)
+    expected_stats = get_global_stats(hmm_stats, tuple(x.detach() for x in init_stats), E_pair.detach())
+    expected_stats, local_vlb = allreduce_nested(expected_stats, local_vlb, group)
+    global_vlb = slds_prior_vlb(host_params[0], host_params[1], dev)
+    return samples, expected_stats, global_vlb, local_vlb
+
+
+def ragged_final_pass_differentiable(hmm_natparam, lds_natparam, nn_potentials, eps, lens, local_maps, reference_compat=True):
+    """final_pass_differentiable for a ragged batch, on FIXED mean-field natural parameters (lens: (B,) int32 device
+    tensor, 2 <= lens <= T).  The HMM node potentials come from get_arhmm_local_nodeparams, the torch route (one GEMM whose
+    backward is a GEMM): the statistics of pairs t >= L-1 are exact zeros, the rows they give are never read by
+    hmm_logZ_differentiable(lengths=) and receive a zero cotangent.
+    -> (samples, ((E x0 x0', E x0), E_pair (B,T-1,3,n,n)), local_vlb)"""
+    nJ, nh = nn_potentials[0], nn_potentials[1]
+    B, T, n = nh.shape
+    lognorm, (dxx, ex), samples, (E_init, E_pair), _ = _ragged_lds_final_pass_differentiable(
+        lds_natparam, (nJ, nh), eps, lens, reference_compat)
+    _, _, dense_init, dense_pair = local_maps
+    init_stats = (E_init[:, :n * n].reshape(B, n, n), E_init[:, n * n:])
+    node_hmm = get_arhmm_local_nodeparams(dense_init, dense_pair, init_stats, E_pair)
+    hmm_vlb = hmm_logZ_differentiable((hmm_natparam[0], hmm_natparam[1], node_hmm), lengths=lens)
+    lds_vlb = lognorm - _masked_vlb_terms((nJ, nh), dxx, ex, lens)
+    return samples, (init_stats, E_pair), (hmm_vlb + lds_vlb).sum()
+
+
+def run_inference_withlabels_ragged_differentiable(prior_natparam, global_natparam, potentials_and_labels, lengths,
+                                                   num_samples, eps=None, generator=None, group=None, reference_compat=True):
+    """run_inference_withlabels_differentiable for one padded batch with per-sequence lengths (B,): the labelled mean-field
+    step of optimize_local_meanfield_withlabels(lengths=) on detached values (labels[b, L:] are ignored, -1 included), the
+    final ragged E-step + sampler differentiated through the reverse sweeps (no statistics cotangents).
+    -> (samples (B,T,S,n), expected_stats, global_vlb, local_vlb), the values of run_inference_withlabels(lengths=); the
+    gradients w.r.t. nn_potentials[b, L:] are exactly 0."""
+    nn_potentials, labels = potentials_and_labels
+    dev = nn_potentials[1].device
+    lens = _slds_lengths(lengths, global_natparam, nn_potentials, False, "run_inference_withlabels_ragged_differentiable")
+    node_d = tuple(_dev64(x, dev) for x in nn_potentials)
+    B, T, n = node_d[1].shape
+    host_params = (_HostParamsLater(global_natparam), _HostParamsLater(prior_natparam))
+    (hmm_stats, _), (_, lds_nat), _ = optimize_local_meanfield_withlabels(global_natparam, node_d, labels, lengths=lens)
+    if eps is None:
+        eps = torch.randn(B, T, int(num_samples), n, dtype=torch.float64, device=dev, generator=generator)
+    nJ, nh = nn_potentials[0], nn_potentials[1]
+    lognorm, (dxx, ex), samples, (E_init, E_pair), _ = _ragged_lds_final_pass_differentiable(
+        lds_nat, (nJ, nh), _dev64(eps, dev), lens, reference_compat)
+    init_stats = (E_init[:, :n * n].reshape(B, n, n).detach(), E_init[:, n * n:].detach())
+    expected_stats = get_global_stats(hmm_stats, init_stats, E_pair.detach())
+    local_vlb = (lognorm - _masked_vlb_terms((nJ, nh), dxx, ex, lens)).sum()
     expected_stats, local_vlb = allreduce_nested(expected_stats, local_vlb, group)
     global_vlb = slds_prior_vlb(host_params[0], host_params[1], dev)
     return samples, expected_stats, global_vlb, local_vlb
