@@ -563,14 +563,23 @@ int svae_hmm_ragged_viterbi_f64(int B, int T, int K, int pair_batched,
  * delegates its HMM work, has the operation; the arithmetic is defined HERE.]  The caller supplies the randomness.
  * For sequence b of length L (= T in the uniform call) and sample s:
  *  Filtered distributions  a_t[k] = p(z_t = k | node_{0..t}), t < L: the scaled forward filter of the E-step kernels
- *    (per-step max-shift of the node potentials, renormalisation to sum 1, log Z accumulated as mantissa/exponent pairs);
- *    a step whose normaliser falls below 1e-200 is redone in log space.  (The normaliser is the ONLY criterion here, and
- *    the other steps stay scaled: a component below 1e-308 of a step's scale -- behind a transition more than 745 nats
- *    below the matrix' maximum, say -- is lost to the draws although logZ stays finite.  The E-step's criterion and its
- *    all-log-space pass, above, have not been carried over to the sampler.)
+ *    (per-step max-shift of the node potentials, renormalisation to sum 1, log Z accumulated as mantissa/exponent pairs),
+ *    under the E-step's RANGE contract (svae_hmm_estep_f64, above; csrc/hmm_args.hpp, HMM_LOW): a sequence keeps its scaled
+ *    filter only while every live state's component of every step's unnormalised message (sum_j a_{t-1}[j] P[j][k]) e_t[k]
+ *    -- P and e shifted to a maximum of 1; at t = 0 the shifted, exponentiated init + node_0 -- stays >= 1e-250 and every
+ *    normaliser above 1e-200.  Any other sequence (a transition more than ~575 nats below the matrix' maximum on a path
+ *    that matters or not, E[log pi] of a sparse Dirichlet row, a state forbidden by -1e4 or -inf) is filtered again, ALL
+ *    of it, in log space -- x_t[k] = logsumexp_j(la_{t-1}[j] + pair[j][k]) + node_t[k], la_t = x_t - logsumexp_k x_t[k],
+ *    log Z = the sum of those normalisers (csrc/hmm_sample_log.hip) -- and its draws use the log-space weights below at
+ *    every step.  So for finite or -inf log-potentials every sequence has the paths of the log-space definition to
+ *    rounding.  Example: K = 2, T = 4, init (0, 0), pair ((0, -800), (0, 0)), node ((0, -inf), (0, 0), (-inf, 0),
+ *    (0, log 2)): the chain starts in state 0, must be in state 1 at t = 2 and gets there through the -800 entry at either
+ *    step; log Z = -800 + log 6, and the draws have the marginals (1, 0), (1/2, 1/2), (0, 1), (1/3, 2/3).
  *  Weights  t = L-1: w[k] = a_{L-1}[k];  t < L-1: w[k] = a_t[k] exp(pair[k][z_{t+1}] - M), M = the matrix' largest entry.
  *    If sum_k w[k] < 1e-200 the weights of that draw are recomputed in log space:
  *    w[k] = exp(log a_t[k] + pair[k][z_{t+1}] - max_k(log a_t[k] + pair[k][z_{t+1}])).
+ *    A sequence whose filter was redone in log space draws EVERY step with these weights, from the stored log a_t
+ *    (t = L-1: w[k] = exp(log a_{L-1}[k] - max_k log a_{L-1}[k])).
  *  Selection  C[k] = w[0] + .. + w[k], fp64 additions IN INDEX ORDER (both kernel mappings implement exactly this order:
  *    K <= 16 as K broadcast multiply-adds by 1.0 or 0.0, 17 <= K <= 64 as KP sequential adds of an LDS line that holds KP
  *    zeros and then w), so C is non-decreasing and rises only where w[k] > 0.  thr = clamp(u[b,s,t], 0, 1) C[K-1]; a NaN u
@@ -584,9 +593,15 @@ int svae_hmm_ragged_viterbi_f64(int B, int T, int K, int pair_batched,
  *       S >= 1 samples per sequence; u (B,S,T) fp64 uniforms
  *  out: states (B,S,T) int32, sample-major: states[:, s] is a (B,T) label array of the form svae_hmm_viterbi_f64 returns;
  *       logZ (B) or NULL
- *  workspace: svae_hmm_sample_workspace_bytes(B,T,K) = B T KP doubles (the filtered distributions, padding lanes 0;
- *       KP = 16, 32 or 64 for K <= 16, <= 32, <= 64; no flags are needed: a draw decides its log-space redo from its own
- *       total); 0 for B <= 0, T <= 0 or K outside 1..SVAE_HMM_MAX_K.  16-byte aligned.
+ *  workspace: svae_hmm_sample_workspace_bytes(B,T,K) = B T KP doubles, KP = 16, 32 or 64 for K <= 16, <= 32, <= 64; 0
+ *       for B <= 0, T <= 0 or K outside 1..SVAE_HMM_MAX_K.  16-byte aligned.  One record of KP doubles per (sequence,
+ *       step), and the records say themselves which route a sequence took: a SCALED record holds a_t (padding lanes 0) --
+ *       it sums to 1, so it has a strictly positive entry and none below 0; a LOG record holds log a_t, normalised and
+ *       clamped to <= 0 (padding lanes -inf) -- it has no positive entry.  Between the launches a sequence the scaled
+ *       filter flagged carries -1 in every live lane of its step-0 record; the log-space launch replaces all of its
+ *       records 0 .. L-1 and its logZ; the draw tests the first record it reads (step L-1): no live entry > 0 = a log
+ *       record.  Afterwards "no live entry > 0 in the step-0 record" tells which sequences were redone (Python:
+ *       hmm_inference.sample_redone_sequences).  A redone sequence costs K log-sum-exps of KP terms per step.
  *  Ragged form (svae_hmm_ragged_sample_f64, lengths (B) device int32), the conventions of the other ragged entries:
  *    results up to L are those of the sequence cut at L; states[b, :, t >= L] = -1; node_params[b, L:] and u[b, :, L:]
  *    are never read and may be NaN; no sequence sees another's length or data; a length outside 1..T is clamped to [1, T]
@@ -598,8 +613,9 @@ int svae_hmm_ragged_viterbi_f64(int B, int T, int K, int pair_batched,
  *            16-byte aligned;
  *   ragged : -8 lengths NULL, -9 S < 1, -10 u NULL, -11 states NULL, -12 info NULL, -13 workspace NULL, -14 ws_bytes too
  *            small, -15 workspace not 16-byte aligned;
- *  -1000 launch error.  Two launches (filter, draw), asynchronous on `stream`, no internal allocation, safe under graph
- *  capture.  B S T must be below 2^31. */
+ *  -1000 launch error.  Three launches (scaled filter; log-space filter, whose workgroups leave at once where the sequence
+ *  is not flagged; draw), asynchronous on `stream`, no internal allocation, safe under graph capture.  B S T must be below
+ *  2^31. */
 size_t svae_hmm_sample_workspace_bytes(int B, int T, int K);
 int svae_hmm_sample_f64(int B, int T, int K, int S, int pair_batched,
                         const double* init_params, const double* pair_params,

@@ -4,17 +4,21 @@
 // What it replaces (reference = mattjj/svae): nothing the reference vendors -- its HMM work goes to pyhsmm's message
 // interface, which has the operation; the arithmetic is DEFINED here (include/svae_hip.h, svae_hmm_sample_f64):
 //   filter   a_t[k] = p(z_t = k | node_{0..t}): scaled forward recursion, per-step max-shift of the node potentials,
-//            renormalisation to sum 1, log Z accumulated as mantissa/exponent pairs; a step whose normaliser falls below
-//            1e-200 is redone in log space, inline.
+//            renormalisation to sum 1, log Z accumulated as mantissa/exponent pairs; a sequence with a live component of
+//            an unnormalised message below 1e-250 or a normaliser below 1e-200 (the E-step's range, hmm_args.hpp) is
+//            filtered again, all of it, in log space (hmm_sample_log.hip) and stores log a_t.
 //   weights  t = T-1: w = a_{T-1};  t < T-1: w[k] = a_t[k] exp(pair[k][z_{t+1}] - M), M = the matrix' largest entry;
-//            a total below 1e-200: w[k] = exp(log a_t[k] + pair[k][z_{t+1}] - max_k(..)), inline.
+//            a total below 1e-200, and every step of a sequence whose record is log a_t:
+//            w[k] = exp(log a_t[k] + pair[k][z_{t+1}] - max_k(..)), inline.
 //   select   C[k] = w[0] + .. + w[k], fp64 adds IN INDEX ORDER;  thr = clamp(u, 0, 1) C[K-1] (NaN u = 0);
 //            z_t = #{k : C[k] <= thr}, and the lowest k with C[k] = C[K-1] if that count is K.
 //            Both rules are one test, (C[k] <= thr and C[k] < C[K-1]): C only rises where w[k] > 0, so on a chain with
 //            finite log Z the drawn state has positive weight -- a forbidden transition or observation is never drawn.
 // The caller supplies the uniforms u (B,S,T), as eps of the LDS sampler.
 //
-// One entry = two launches, each in Viterbi's two mappings (hmm_sample_kernel.hpp):
+// One entry = three launches: filter and draw, each in Viterbi's two mappings (hmm_sample_kernel.hpp), and between them
+// the log-space filter of hmm_sample_log.hip, one wavefront per sequence, which leaves at once where the scaled filter
+// raised no flag (the flag is the sequence's step-0 record itself: hmm_sample_kernel.hpp):
 //   filter   K <= 16: one 16-lane DPP row per sequence, four per wavefront; 17 .. 64: one wavefront per sequence.  The
 //            forward half of the one-directional E-step kernels, restated (hmm_estep.hip and hmm_estep_wide.hip are not
 //            touched and share no code with this unit).  Writes a_t, KP = 16 / 32 / 64 doubles per step (padding 0), to the
@@ -35,17 +39,22 @@
 #include "dpp.hpp"
 #include "hmm_sample_kernel.hpp"      // the four kernel templates; this unit instantiates the uniform (RAGGED = false) ones
 
+// hmm_sample_log.hip: the log-space filter, at work on the sequences the scaled filter flagged
+extern "C" int svae_hmm_sample_log_launch(const svae::SampleArgs* a, void* stream);
+
 namespace svae {
 
 template <int K>
 static void launch_sample_row(const SampleArgs& a, hipStream_t s) {
   hipLaunchKernelGGL((hmm_filter_row_kernel<K, false>), dim3((a.B + 3) / 4), dim3(64), 0, s, a);
+  svae_hmm_sample_log_launch(&a, s);
   const long R = (long)a.B * a.S;
   hipLaunchKernelGGL((hmm_draw_row_kernel<K, false>), dim3((unsigned)((R + 3) / 4)), dim3(64), 0, s, a);
 }
 template <int KP>
 static void launch_sample_wide(const SampleArgs& a, hipStream_t s) {
   hipLaunchKernelGGL((hmm_filter_wide_kernel<KP, false>), dim3(a.B), dim3(64), 0, s, a);
+  svae_hmm_sample_log_launch(&a, s);
   hipLaunchKernelGGL((hmm_draw_wide_kernel<KP, false>), dim3((unsigned)((long)a.B * a.S)), dim3(64), 0, s, a);
 }
 

@@ -5,6 +5,13 @@
 // The filter kernels are the forward half of the one-directional E-step kernels (hmm_estep.hip: hmm_estep_kernel;
 // hmm_estep_wide.hip), restated here: they store the filtered distribution alone, KP doubles per step, and nothing the
 // backward pass of the E-step needs.  No code is shared with those units.
+// Range (hmm_args.hpp, HMM_LOW; the E-step's contract): the filter kernels flag a sequence when a live component of a
+// step's unnormalised message (sum_j a_{t-1}[j] P[j][k]) e_t[k] -- at t = 0 of exp(init + node_0 - max) -- falls below
+// 1e-250, or a normaliser below 1e-200: one compare and one OR per step beside the dependent chain, no branch.  A
+// flagged sequence's step-0 record is overwritten with -1 in every live lane; the log-space launch of
+// hmm_sample_log.hip recognises it there (a scaled record sums to 1: it has a positive entry and none below 0),
+// recomputes ALL of the sequence and leaves log a_t (normalised, <= 0, padding lanes -inf) in every record.  The draw
+// kernels tell the two kinds of record apart by the first one they read, step L-1: no live entry > 0 = a log record.
 // RAGGED: sequence b occupies steps 0 .. L-1 of its (T, K) block, L = lengths[b] clamped to [1, T] (a value outside
 // raises the status word, in the filter launch).  The filter freezes at L-1, loads are clamped to L-1 -- nothing stored
 // at t >= L is read --, the draw starts at the chain's own L-1 and labels at t >= L are stored as -1.  Every RAGGED
@@ -16,6 +23,7 @@
 #include <type_traits>
 
 #include "dpp.hpp"
+#include "hmm_args.hpp"
 
 namespace svae {
 
@@ -28,7 +36,8 @@ struct SampleArgs {
   const double* u;            // (B,S,T) uniforms
   int32_t* states;            // (B,S,T)
   double* logZ;               // (B) or nullptr
-  double* ws;                 // (B,T,KP) filtered distributions a_t, padding lanes 0
+  double* ws;                 // (B,T,KP) filtered distributions a_t, padding lanes 0; a sequence redone in log space:
+                              // log a_t <= 0, padding lanes -inf
 };
 struct SampleRaggedArgs : SampleArgs {
   const int32_t* lengths;     // (B)
@@ -38,7 +47,8 @@ template <bool RAGGED>
 using SampleArgsT = std::conditional_t<RAGGED, SampleRaggedArgs, SampleArgs>;
 
 constexpr int sample_kp(int K) { return K <= 16 ? 16 : (K <= 32 ? 32 : 64); }
-constexpr double SMP_TINY = 1e-200;   // a normaliser (filter) or a weight total (draw) below it: that step in log space
+constexpr double SMP_TINY = 1e-200;   // a normaliser below it (filter): the sequence is redone in log space; a weight
+                                      // total below it (draw): that draw's weights in log space
 constexpr int SMP_AHEAD = 8;          // filter: node potentials in flight, steps
 
 // Maximum over the 16 lanes of a DPP row, in every lane (row_ror:8/4/2/1 on the two halves of the double)
@@ -126,6 +136,7 @@ __global__ __launch_bounds__(64) void hmm_filter_row_kernel(const SampleArgsT<RA
   long lzE = 0;                // ... exponent
   double lzS = 0.0;            // sum of the subtracted maxima
   double alpha = 0.0;
+  bool low = false, tiny = false;   // a message component (padding lanes too, masked at the end) / a normaliser left the range
 
   auto step = [&](auto first, int t, double ndraw) __attribute__((always_inline)) {
     constexpr bool FIRST = decltype(first)::value;
@@ -142,41 +153,15 @@ __global__ __launch_bounds__(64) void hmm_filter_row_kernel(const SampleArgsT<RA
       dpp_fence(alpha);
       static_for<0, K>([&](auto j) { mac_bc<j>(pred, alpha, P[j]); });     // sum_j a_{t-1}[j] P[j][k]
     }
-    double al = pred * e;
+    double al = pred * e;                   // the unnormalised message component
     double cs = 0.0;
     dpp_fence(al);
     static_for<0, K>([&](auto k) { mac_bc<k>(cs, al, one); });
-    double rc = rcp_nr(cs);
-    double shift = m + (FIRST ? 0.0 : pmax);
-    const bool tiny = live && !(cs > SMP_TINY);
-    if (__any(tiny)) {
-      // log-space redo of this step for the rows that underflowed (wave-uniform branch, rare)
-      const double la = alpha > 0.0 ? ::log(alpha) : NEG_INF;
-      double lpred = 0.0;
-      if constexpr (!FIRST) {
-        double sj[K], m2 = NEG_INF;
-        static_for<0, K>([&](auto j) {
-          const double lpj = col ? pp[j * K + cc] : NEG_INF;
-          sj[j] = bcast<j>(la) + lpj;
-          m2 = __builtin_fmax(m2, sj[j]);
-        });
-        double sum = 0.0;
-        static_for<0, K>([&](auto j) { sum += exp(sj[j] - m2); });
-        lpred = m2 > NEG_INF ? m2 + ::log(sum) : NEG_INF;
-      }
-      const double lal = col ? lpred + nd : NEG_INF;
-      double M = NEG_INF;
-      static_for<0, K>([&](auto k) { M = __builtin_fmax(M, bcast<k>(lal)); });
-      const double al2 = (col && M > NEG_INF) ? exp(lal - M) : 0.0;
-      double cs2 = 0.0;
-      static_for<0, K>([&](auto k) { cs2 += bcast<k>(al2); });
-      if (tiny) {
-        cs = cs2;
-        rc = rcp_nr(cs2);
-        al = al2;
-        shift = M;
-      }
-    }
+    const double rc = rcp_nr(cs);
+    const double shift = m + (FIRST ? 0.0 : pmax);
+    // the range criterion (a NaN fails both compares); steps past the length never flag
+    low = low || (live && !(al >= HMM_LOW));
+    tiny = tiny || (live && !(cs > SMP_TINY));
     if constexpr (RAGGED) {
       alpha = live ? al * rc : alpha;
       if (valid && live) wsb[(long)t * 16] = alpha;
@@ -210,6 +195,9 @@ __global__ __launch_bounds__(64) void hmm_filter_row_kernel(const SampleArgsT<RA
     static_for<0, SMP_AHEAD>([&](auto u) { cur[u] = nxt[u]; });
   }
   if (valid && c == 0 && a.logZ) a.logZ[b] = lzS + ::log(lzM) + (double)lzE * 0.6931471805599453094;
+  // a flagged row marks its step-0 record for the log-space launch (which also rewrites logZ)
+  const bool redo = ((unsigned)(__ballot((low && col) || tiny) >> (lane & 48)) & 0xffffu) != 0;
+  if (valid && redo && col) wsb[0] = -1.0;
 }
 
 // ---- filter, 17 <= K <= 64: one wavefront per sequence ----------------------------------------------------------------
@@ -246,11 +234,13 @@ __global__ __launch_bounds__(64) void hmm_filter_wide_kernel(const SampleArgsT<R
 
   double lzM, lzS, al;
   long lzE;
+  bool flag;                                          // this lane saw the sequence leave the range of the scaled recursion
   {
     const double x = st ? a.init_params[cc] + nd[0] : NEG_INF;
     const double m = smp_wave_max(x);
     const double w = (st && m > NEG_INF) ? exp(x - m) : 0.0;
     const double s = smp_wave_sum(w);
+    flag = (st && !(w >= HMM_LOW)) || !(s > SMP_TINY);
     al = w * rcp_nr(s);
     lzS = m;
     lzM = __builtin_amdgcn_frexp_mant(s);
@@ -281,25 +271,10 @@ __global__ __launch_bounds__(64) void hmm_filter_wide_kernel(const SampleArgsT<R
           v0 = __builtin_fma(line[i], Pc[i], v0);
           v1 = __builtin_fma(line[i + 1], Pc[i + 1], v1);
         }
-        double w = (v0 + v1) * e;
-        double cs = smp_wave_sum(w);
-        double shift = m + pmax;
-        if (!(cs > SMP_TINY)) {
-          // log-space redo of this step (wave-uniform branch, rare): the matrix column is read again
-          const double la = al > 0.0 ? ::log(al) : NEG_INF;
-          __builtin_amdgcn_wave_barrier();
-          line[lane] = la;
-          smp_lds_sync();
-          double m2 = NEG_INF;
-          for (int i = 0; i < K; ++i) m2 = __builtin_fmax(m2, line[i] + pp[i * K + cc]);
-          double sum = 0.0;
-          for (int i = 0; i < K; ++i) sum += exp(line[i] + pp[i * K + cc] - m2);
-          const double lal = (st && m2 > NEG_INF) ? m2 + ::log(sum) + x : NEG_INF;
-          const double M = smp_wave_max(lal);
-          w = (st && M > NEG_INF) ? exp(lal - M) : 0.0;
-          cs = smp_wave_sum(w);
-          shift = M;
-        }
+        const double w = (v0 + v1) * e;               // the unnormalised message component
+        const double cs = smp_wave_sum(w);
+        const double shift = m + pmax;
+        flag = flag || (st && !(w >= HMM_LOW)) || !(cs > SMP_TINY);    // (a NaN fails both compares)
         al = w * rcp_nr(cs);
         lzM *= __builtin_amdgcn_frexp_mant(cs);
         lzE += __builtin_amdgcn_frexp_exp(cs);
@@ -312,6 +287,8 @@ __global__ __launch_bounds__(64) void hmm_filter_wide_kernel(const SampleArgsT<R
     for (int u = 0; u < AHEAD; ++u) cur[u] = nxt[u];
   }
   if (lane == 0 && a.logZ) a.logZ[b] = lzS + ::log(lzM) + (double)lzE * 0.6931471805599453094;
+  // a flagged sequence marks its step-0 record for the log-space launch (which also rewrites logZ)
+  if (__any(flag) && st) wsb[0] = -1.0;
 }
 
 // ---- draw, K <= 16: one DPP row per (sequence, sample) ----------------------------------------------------------------
@@ -378,6 +355,9 @@ __global__ __launch_bounds__(64) void hmm_draw_row_kernel(const SampleArgsT<RAGG
   double A[16], An[16];
   load_a(blk, A);
   double uv = load_u(blk);
+  // the kind of this row's record, from the first one the draw reads: a scaled a_t sums to 1, log a_t is <= 0 throughout
+  // (step blk 16 + 15 is at or past the row's last one: A[15] is the record of step TL-1)
+  const bool islog = ((unsigned)(__ballot(col && A[15] > 0.0) >> rsh) & 0xffffu) == 0;
   for (; blk >= 0; --blk) {
     const int bn = blk > 0 ? blk - 1 : 0;
     load_a(bn, An);
@@ -398,12 +378,15 @@ __global__ __launch_bounds__(64) void hmm_draw_row_kernel(const SampleArgsT<RAGG
         dpp_fence(w);
         static_for<0, K>([&](auto j) { mac_bc<j>(C, w, ge[j]); });         // C[c] = w[0] + .. + w[c], in index order
         double tot = bcast_fenced<K - 1>(C);
-        const bool under = live && !last && tot < SMP_TINY;
+        // (a row whose record is log a_t has no positive weight here: its total is <= 0 or NaN at every step, the last
+        //  one included, where a scaled row's total is 1 -- the one compare of the chain serves both)
+        const bool under = live && !(tot >= SMP_TINY);
         if (__any(under)) {
-          // the weights of this draw in log space (wave-uniform branch, rare); the matrix entry is read again
+          // the weights of this draw in log space (wave-uniform branch; every step of a row whose record is log a_t,
+          // else rare); the matrix entry is read again
           const int zc = (z & 15) < K ? (z & 15) : K - 1;
-          const double la = A[i] > 0.0 ? ::log(A[i]) : NEG_INF;
-          const double x = col ? la + pp[cc * K + zc] : NEG_INF;
+          const double la = islog ? A[i] : (A[i] > 0.0 ? ::log(A[i]) : NEG_INF);
+          const double x = col ? la + (last ? 0.0 : pp[cc * K + zc]) : NEG_INF;
           const double mx = smp_row_max16(x);
           const double w2 = (col && mx > NEG_INF) ? exp(x - mx) : 0.0;
           double C2 = 0.0;
@@ -490,16 +473,20 @@ __global__ __launch_bounds__(64) void hmm_draw_wide_kernel(const SampleArgsT<RAG
     return C;
   };
   auto load_a = [&](int t) -> double { return af[(long)(t < 0 ? 0 : (t < TL ? t : TL - 1)) * KP]; };
-
   constexpr int AHEAD = 8;
   int z = 0;
-  for (int t0 = ((TL - 1) >> 6) << 6; t0 >= 0; t0 -= 64) {
+  bool islog = false;                                 // (wave-uniform) the chain's record is log a_t
+  const int tfirst = ((TL - 1) >> 6) << 6;
+  for (int t0 = tfirst; t0 >= 0; t0 -= 64) {
     const int tu = t0 + lane;
     const double uv = ur[tu < TL ? tu : TL - 1];
     int lab = 0;
     double cur[AHEAD], nxt[AHEAD];
 #pragma unroll
     for (int q = 0; q < AHEAD; ++q) cur[q] = load_a(t0 + 56 + q);
+    // the kind of this chain's record, from the first one the draw reads: a scaled a_t sums to 1, log a_t is <= 0
+    // throughout (step tfirst + 63 is at or past the chain's last one: the load is the record of step TL-1)
+    if (t0 == tfirst) islog = !__any(st && cur[AHEAD - 1] > 0.0);
     for (int i0 = 56; i0 >= 0; i0 -= AHEAD) {
 #pragma unroll
       for (int q = 0; q < AHEAD; ++q) nxt[q] = load_a(t0 + i0 - AHEAD + q);
@@ -514,11 +501,14 @@ __global__ __launch_bounds__(64) void hmm_draw_wide_kernel(const SampleArgsT<RAG
           double w = st ? cur[q] * colv : 0.0;
           double C = cumsum(w);
           double tot = smp_readlane(C, K - 1);
-          if (!last && tot < SMP_TINY) {
-            // the weights of this draw in log space (wave-uniform branch, rare); the matrix entry is read again
+          // (a chain whose record is log a_t has no positive weight here: its total is <= 0 or NaN at every step, the
+          //  last one included, where a scaled chain's total is 1 -- the one compare of the chain serves both)
+          if (!(tot >= SMP_TINY)) {
+            // the weights of this draw in log space (wave-uniform branch; every step of a chain whose record is log a_t,
+            // else rare); the matrix entry is read again
             const int zc = z < K ? z : K - 1;
-            const double la = cur[q] > 0.0 ? ::log(cur[q]) : NEG_INF;
-            const double x = st ? la + pp[cc * K + zc] : NEG_INF;
+            const double la = islog ? cur[q] : (cur[q] > 0.0 ? ::log(cur[q]) : NEG_INF);
+            const double x = st ? la + (last ? 0.0 : pp[cc * K + zc]) : NEG_INF;
             const double mx = smp_wave_max(x);
             w = (st && mx > NEG_INF) ? exp(x - mx) : 0.0;
             C = cumsum(w);

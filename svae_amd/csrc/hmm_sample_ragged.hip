@@ -10,17 +10,22 @@
 #include "dpp.hpp"
 #include "hmm_sample_kernel.hpp"
 
+// hmm_sample_log.hip: the log-space filter, at work on the sequences the scaled filter flagged
+extern "C" int svae_hmm_sample_log_ragged_launch(const svae::SampleRaggedArgs* a, void* stream);
+
 namespace svae {
 
 template <int K>
 static void launch_sample_row_ragged(const SampleRaggedArgs& a, hipStream_t s) {
   hipLaunchKernelGGL((hmm_filter_row_kernel<K, true>), dim3((a.B + 3) / 4), dim3(64), 0, s, a);
+  svae_hmm_sample_log_ragged_launch(&a, s);
   const long R = (long)a.B * a.S;
   hipLaunchKernelGGL((hmm_draw_row_kernel<K, true>), dim3((unsigned)((R + 3) / 4)), dim3(64), 0, s, a);
 }
 template <int KP>
 static void launch_sample_wide_ragged(const SampleRaggedArgs& a, hipStream_t s) {
   hipLaunchKernelGGL((hmm_filter_wide_kernel<KP, true>), dim3(a.B), dim3(64), 0, s, a);
+  svae_hmm_sample_log_ragged_launch(&a, s);
   hipLaunchKernelGGL((hmm_draw_wide_kernel<KP, true>), dim3((unsigned)((long)a.B * a.S)), dim3(64), 0, s, a);
 }
 

@@ -5,6 +5,7 @@
   redone_sequences(workspace, B, T, K) -> which sequences of that E-step took the log-space route
   hmm_viterbi(natparam) -> most probable state path (and its score)          (:54-63; csrc/hmm_viterbi.hip)
   hmm_sample(natparam, num_samples) -> state paths drawn from the posterior  (csrc/hmm_sample.hip)
+  sample_redone_sequences(workspace, B, T, K) -> which sequences of that call had their filter redone in log space
   hmm_estep_differentiable(natparam) -> hmm_estep's outputs, with gradients of all four to all three inputs
                                                                              (csrc/hmm_estep_vjp.hip)
 
@@ -198,7 +199,9 @@ def hmm_sample(natparam, num_samples=1, u=None, generator=None, workspace=None, 
     -inf), by forward filtering and backward sampling: labels torch.int32 (S,T), or (B,S,T) when node_params is (B,T,K),
     S = num_samples; labels[:, s] is a (B,T) label array of the form hmm_viterbi returns.  With return_logZ also the
     log-normaliser the filter computes (0-d, or (B)).  The arithmetic is defined in include/svae_hip.h
-    (svae_hmm_sample_f64): a state with a forbidden (-inf) transition or observation is never drawn.
+    (svae_hmm_sample_f64): a state with a forbidden (-inf) transition or observation is never drawn.  The filter keeps
+    the E-step's range contract: a sequence that leaves the range of the scaled recursion is filtered again, all of it,
+    in log space, and sample_redone_sequences(workspace, B, T, K) says which were.
     u: the uniforms, (B,S,T) ((S,T) for the unbatched call); None draws torch.rand fp64 on the device with `generator`.
     workspace: any contiguous device tensor of at least svae_hmm_sample_workspace_bytes(B,T,K) bytes.
     lengths: (B,) integers, see the module docstring -- labels from a sequence's length on are -1."""
@@ -258,6 +261,20 @@ def hmm_sample(natparam, num_samples=1, u=None, generator=None, workspace=None, 
         states = states[0]
         logZ = logZ[0] if return_logZ else None
     return (states, logZ) if return_logZ else states
+
+
+def sample_redone_sequences(workspace, B, T, K):
+    """Which sequences of the last hmm_sample call on `workspace` left the range of the scaled filter and were filtered
+    again in log space: a (B,) bool tensor read from the records themselves (csrc/hmm_sample_kernel.hpp: B T KP doubles,
+    KP = 16, 32 or 64; a scaled record a_t sums to 1 and so has a positive entry, a log-space record log a_t has none).
+    The counterpart of redone_sequences for the sampler; with lengths= every sequence has its step-0 record."""
+    if not (1 <= K <= HMM_MAX_K):
+        raise ValueError("number of states K=%d outside 1..%d" % (K, HMM_MAX_K))
+    kp = 16 if K <= 16 else (32 if K <= 32 else 64)
+    ws = workspace.reshape(-1)
+    if ws.dtype != torch.float64 or ws.numel() < B * T * kp:
+        raise ValueError("workspace is not the float64 workspace of a (B=%d, T=%d, K=%d) sampling call" % (B, T, K))
+    return ~(ws[:B * T * kp].view(B, T * kp)[:, :K] > 0).any(dim=1)
 
 
 class _HMMLogZ(torch.autograd.Function):

@@ -1,12 +1,15 @@
 """Posterior sampling against the E-step and Viterbi at the same shapes, in one process:
-python tools/bench_hmm_sample.py [--json FILE]
+python tools/bench_hmm_sample.py [--json FILE] [--all-flagged]
 
 Shapes: K = 8, T = 500, B = 2048 (the SLDS configuration) and K = 64, T = 500, B in {64, 512, 2048}; the sampler at
 S = 1 and S = 8 samples per sequence.  Every entry point is called through the C ABI on preallocated buffers (no
 allocation inside the timed window), timed with device events after warm-up, in 7 windows that alternate between the
-four; the median window and the spread are printed.  The sampler's two launches (filter, draw) are then split with the
+four; the median window and the spread are printed.  The sampler's three launches (filter, log-space filter, draw) are then split with the
 profiler's kernel times over a few calls: the filter launch is the forward half of the one-directional E-step, so
-filter / E-step well above 1/2 is a defect to explain (the E-step at K <= 16 is the two-ended kernel: its chain is T/2)."""
+filter / E-step well above 1/2 is a defect to explain (the E-step at K <= 16 is the two-ended kernel: its chain is T/2).
+--all-flagged forbids state 1 at t = 0 (init[1] = -1e4): every sequence leaves the range of the scaled recursions, so the
+sampler's filter (and the E-step) redo every sequence in log space -- the cost of the redone route against a run without
+the option.  The number of sequences the sampler redid is printed with every shape."""
 import json
 import os
 import sys
@@ -16,6 +19,7 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from svae_amd import _lib  # noqa: E402
+from svae_amd.hmm.hmm_inference import sample_redone_sequences  # noqa: E402
 
 SHAPES = [(8, 500, 2048), (64, 500, 64), (64, 500, 512), (64, 500, 2048)]
 SAMPLES = (1, 8)
@@ -23,7 +27,8 @@ WINDOWS, MIN_WINDOW_MS = 7, 60.0
 
 
 def _kernel_split(fn, calls=5):
-    """mean device time (ms) per call of the kernels whose names hold `hmm_filter` / `hmm_draw`, or None"""
+    """mean device time (ms) per call of the kernels whose names hold `hmm_filter` (the scaled filter, without
+    `hmm_filter_log`) / `hmm_filter_log` (the log-space filter launch) / `hmm_draw`, or None"""
     try:
         from torch.profiler import ProfilerActivity, profile
         with profile(activities=[ProfilerActivity.CUDA]) as prof:
@@ -31,14 +36,14 @@ def _kernel_split(fn, calls=5):
                 fn()
             torch.cuda.synchronize()
         out = {}
-        for key in ("hmm_filter", "hmm_draw"):
+        for key in ("hmm_filter", "hmm_filter_log", "hmm_draw"):
             us = sum(getattr(e, "device_time_total", getattr(e, "cuda_time_total", 0.0))
-                     for e in prof.key_averages() if key in e.key)
+                     for e in prof.key_averages() if key in e.key and (key != "hmm_filter" or "hmm_filter_log" not in e.key))
             out[key] = us / calls / 1e3 if us > 0 else None
         return out
     except Exception as e:                                  # the split is an extra: the windows above stand without it
         print("kernel split unavailable:", repr(e))
-        return {"hmm_filter": None, "hmm_draw": None}
+        return {"hmm_filter": None, "hmm_filter_log": None, "hmm_draw": None}
 
 
 def main(argv):
@@ -51,6 +56,8 @@ def main(argv):
     for K, T, B in SHAPES:
         f64 = dict(dtype=torch.float64, device=dev)
         init = torch.as_tensor(rng.standard_normal(K), device=dev)
+        if "--all-flagged" in argv:
+            init[1] = -1e4
         pair = torch.as_tensor(rng.standard_normal((K, K)), device=dev)
         node = torch.as_tensor(3.0 * rng.standard_normal((B, T, K)), device=dev)
         SM = max(SAMPLES)
@@ -110,7 +117,8 @@ def main(argv):
             w = sorted(res[name])
             row[name + "_ms"], row[name + "_min_ms"], row[name + "_max_ms"] = w[len(w) // 2], w[0], w[-1]
         split = _kernel_split(sampler(1))
-        row["filter_ms"], row["draw_S1_ms"] = split["hmm_filter"], split["hmm_draw"]
+        row["filter_ms"], row["draw_S1_ms"], row["filter_log_ms"] = split["hmm_filter"], split["hmm_draw"], split["hmm_filter_log"]
+        row["sample_redone"] = int(sample_redone_sequences(sws, B, T, K).sum())
         for S in SAMPLES:
             row["ratio_sample_S%d_over_viterbi" % S] = row["sample_S%d_ms" % S] / row["viterbi_ms"]
         row["ratio_filter_over_estep"] = None if row["filter_ms"] is None else row["filter_ms"] / row["estep_ms"]
@@ -120,11 +128,14 @@ def main(argv):
             row["estep_min_ms"], row["estep_max_ms"]))
         for S in SAMPLES:
             n = "sample_S%d" % S
-            print("    sampler S=%d %.4f ms [%.4f, %.4f]   sampler / viterbi %.3f" % (
-                S, row[n + "_ms"], row[n + "_min_ms"], row[n + "_max_ms"], row["ratio_%s_over_viterbi" % n]))
+            print("    sampler S=%d %.4f ms [%.4f, %.4f]   sampler / viterbi %.3f   (%d of %d sequences redone)" % (
+                S, row[n + "_ms"], row[n + "_min_ms"], row[n + "_max_ms"], row["ratio_%s_over_viterbi" % n],
+                row["sample_redone"], B))
         if row["filter_ms"] is not None:
-            print("    filter launch %.4f ms, draw launch (S=1) %s ms   filter / E-step %.3f   (logZ[0] %.6f vs %.6f)" % (
-                row["filter_ms"], "%.4f" % row["draw_S1_ms"] if row["draw_S1_ms"] else "?", row["ratio_filter_over_estep"],
+            print("    filter launch %.4f ms, log-space filter launch %s ms, draw launch (S=1) %s ms   filter / E-step %.3f   "
+                  "(logZ[0] %.6f vs %.6f)" % (
+                row["filter_ms"], "%.4f" % row["filter_log_ms"] if row["filter_log_ms"] else "?",
+                "%.4f" % row["draw_S1_ms"] if row["draw_S1_ms"] else "?", row["ratio_filter_over_estep"],
                 float(slogZ[0]), float(logZ[0])), flush=True)
     if "--json" in argv:
         path = argv[argv.index("--json") + 1]
