@@ -676,6 +676,41 @@ int svae_hmm_ragged_estep_vjp_f64(int B, int T, int K, int pair_batched,
                                   double* d_init, double* d_pair, double* d_node,
                                   int32_t* info, void* workspace, size_t ws_bytes, void* stream);
 
+/* Batched HMM E-step with PER-STEP transition potentials (time-inhomogeneous chains: input-driven and recurrent
+ * transitions, time-varying priors, per-step expected pair terms), K <= SVAE_HMM_MAX_K -- csrc/hmm_estep_perstep.hip,
+ * which states the arithmetic.  Additions to ABI 15 (no new number).  For sequence b of length L (= T without lengths):
+ *    log p(z) ∝ init[z_0] + sum_{t<L-1} pair[t][z_t][z_{t+1}] + sum_{t<L} node[b,t][z_t]
+ *  in : init_params (K); pair_params (T-1,K,K), [t][j][k] = z_t = j -> z_{t+1} = k, or (B,T-1,K,K) if pair_batched (T = 1
+ *       reads no pair parameters: the pointer may then be NULL); node_params (B,T,K); lengths (B) device int32 or NULL =
+ *       every sequence has length T
+ *  out: logZ (B); E_init (B,K) = the marginal at t = 0; E_states (B,T,K); E_trans (B,T-1,K,K) PER STEP: E_trans[b,t] is the
+ *       posterior pairwise marginal of (z_t, z_{t+1}), its rows sum to E_states[b,t] and its columns to E_states[b,t+1] --
+ *       or NULL = not wanted (log-normaliser / marginals only): the pass that forms it is skipped and the other three
+ *       outputs are bit for bit those of the call with E_trans.
+ *  Domain: potentials finite or -inf; one step's matrix may sit at any common offset (it only shifts logZ) and its entries
+ *       may lie hundreds of nats below its maximum.  ONE route, log space throughout (a scaled step would pay the same K^2
+ *       exponentials per step for exp(P_t - max)): every sequence with finite logZ has the log-space forward-backward's
+ *       result to rounding, and there is no fallback to report.  A sequence with logZ = -inf is outside the contract.
+ *  Lengths: the conventions of the svae_hmm_ragged_* entries -- L = lengths[b] clamped to [1, T] for addressing and trip
+ *       counts, a length outside 1..T ORs 1 into the device word `info` (an atomic; never cleared by the library, never read
+ *       on the host); results up to L are those of the sequence cut there; E_states[b, L:] and E_trans[b, L-1:] are exactly
+ *       0.0; nothing stored at node steps >= L or pair steps >= L-1 is read (it may be NaN); no sequence sees another's
+ *       length or data.
+ *  workspace: svae_hmm_perstep_workspace_bytes(B,T,K) = B T K doubles rounded up to 128 bytes (log alpha_t[k], one record of
+ *       K doubles per (sequence, step)); 0 for B <= 0, T <= 0 or K outside 1..SVAE_HMM_MAX_K.  16-byte aligned.
+ *  Returns 0, or (decided on the host before any HIP call, the first failing check)
+ *   -1 B < 0, -2 T < 1, -3 K outside 1..SVAE_HMM_MAX_K, -4 pair_batched not 0 or 1, -5 init_params NULL, -6 pair_params
+ *   NULL with T > 1, [B = 0 returns 0 here], -7 node_params NULL, -8 logZ NULL, -9 E_init NULL, -10 E_states NULL,
+ *   -11 info NULL with lengths given, -12 workspace NULL, -13 ws_bytes too small, -14 workspace not 16-byte aligned;
+ *  -1000 launch error.  One launch, asynchronous on `stream`, no internal allocation, no host synchronisation, safe under
+ *  graph capture. */
+size_t svae_hmm_perstep_workspace_bytes(int B, int T, int K);
+int svae_hmm_perstep_estep_f64(int B, int T, int K, int pair_batched,
+                               const double* init_params, const double* pair_params, const double* node_params,
+                               const int32_t* lengths /* or NULL */,
+                               double* logZ, double* E_init, double* E_trans /* or NULL */, double* E_states,
+                               int32_t* info /* NULL only if lengths is */, void* workspace, size_t ws_bytes, void* stream);
+
 /* HMM step of the SLDS coordinate ascent on the rows `seq_index` lists (B of `rows`; NULL: rows 0..B-1; negative
  * entries = unused slots, which must follow the live ones -- the list svae_slds_sweep_glue_f64 writes):
  *   hmm_meanfield + get_arhmm_local_nodeparams   /root/reference/svae/models/slds_svae.py:108-115, 131-147

@@ -95,6 +95,10 @@ SIGNATURES = {
                                + [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]),
     "svae_hmm_ragged_estep_vjp_f64": (ctypes.c_int, [ctypes.c_int] * 4 + [_c_double_p] * 3 + [_c_int_p] + [_c_double_p] * 7
                                       + [_c_int_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]),
+    # per-step transition potentials (1 <= K <= 64; lengths, E_trans and, without lengths, info may be NULL)
+    "svae_hmm_perstep_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int] * 3),
+    "svae_hmm_perstep_estep_f64": (ctypes.c_int, [ctypes.c_int] * 4 + [_c_double_p] * 3 + [_c_int_p] + [_c_double_p] * 4
+                                   + [_c_int_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]),
     "svae_slds_hmm_meanfield_f64": (ctypes.c_int, [ctypes.c_int] * 5 + [_c_double_p] * 9 + [_c_int_p] + [_c_double_p] * 5
                                     + [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]),
     "svae_slds_sweep_glue_f64": (ctypes.c_int, [ctypes.c_int] * 3 + [ctypes.c_double, _c_int_p] + [_c_double_p] * 7

@@ -8,6 +8,9 @@
   sample_redone_sequences(workspace, B, T, K) -> which sequences of that call had their filter redone in log space
   hmm_estep_differentiable(natparam) -> hmm_estep's outputs, with gradients of all four to all three inputs
                                                                              (csrc/hmm_estep_vjp.hip)
+  hmm_estep_perstep(natparam) -> hmm_estep for PER-STEP transition potentials, pair (T-1,K,K) or (B,T-1,K,K); E_trans is
+                                 then per step too, (…,T-1,K,K)                (csrc/hmm_estep_perstep.hip)
+  hmm_logZ_perstep(natparam), hmm_logZ_perstep_differentiable(natparam) -> its log-normaliser, with gradients to all three
 
 natparam = (init_params (K), pair_params (K,K), node_params (T,K)) are LOG potentials, as in the
 reference.  New: node_params may be (B,T,K) (and pair_params (B,K,K)); outputs then carry a leading
@@ -418,3 +421,122 @@ def hmm_estep_differentiable(natparam, lengths=None, check=False):
             raise TypeError("hmm_estep_differentiable takes torch tensors")
     logZ, E_init, E_trans, E_states = _HMMEStep.apply(init_params, pair_params, node_params, lengths, check)
     return logZ, (E_init, E_trans, E_states)
+
+
+# ---- per-step transition potentials (svae_hmm_perstep_estep_f64, csrc/hmm_estep_perstep.hip) --------------------------------
+def _shape_of(x):
+    return tuple(x.shape) if hasattr(x, "shape") else np.shape(x)
+
+
+def _perstep_shapes(natparam):
+    """(B, T, K, batched, pair_batched) of a per-step natparam, from shapes alone: every refusal is a ValueError raised
+    before anything is converted, copied or launched."""
+    init_s, pair_s, node_s = (_shape_of(x) for x in natparam)
+    if len(node_s) not in (2, 3):
+        raise ValueError("node_params must be (T,K) or (B,T,K)")
+    batched = len(node_s) == 3
+    B = node_s[0] if batched else 1
+    T, K = node_s[-2:]
+    if not (1 <= K <= HMM_MAX_K):
+        raise ValueError("number of states K=%d outside 1..%d" % (K, HMM_MAX_K))
+    if T < 1:
+        raise ValueError("node_params has no steps")
+    if init_s != (K,):
+        raise ValueError("init_params must have shape (K,) = (%d,), got %r" % (K, init_s))
+    if len(pair_s) not in (3, 4):
+        raise ValueError("per-step pair_params must be (T-1,K,K) or (B,T-1,K,K), got %r" % (pair_s,))
+    pair_batched = len(pair_s) == 4
+    if pair_batched and not batched:
+        raise ValueError("per-sequence pair_params (B,T-1,K,K) need batched node_params (B,T,K)")
+    if pair_s[-2:] != (K, K):
+        raise ValueError("pair_params must end in (K,K) = (%d,%d), got %r" % (K, K, pair_s))
+    if pair_s[-3] != T - 1:
+        raise ValueError("pair_params must hold T-1 = %d per-step matrices, got %d" % (T - 1, pair_s[-3]))
+    if pair_batched and pair_s[0] != B:
+        raise ValueError("pair_params has batch %d, node_params %d" % (pair_s[0], B))
+    return B, T, K, batched, pair_batched
+
+
+def hmm_estep_perstep(natparam, workspace=None, lengths=None, check=False, want_trans=True):
+    """The E-step of an HMM whose transition potentials change with time:
+        log p(z) ∝ init[z_0] + sum_t pair[t][z_t][z_{t+1}] + sum_t node[t][z_t]
+    natparam = (init (K), pair (T-1,K,K) or (B,T-1,K,K), node (T,K) or (B,T,K)), LOG potentials, finite or -inf.
+    Returns (logZ, (E_init, E_trans, E_states)) with E_trans PER STEP, (…,T-1,K,K): E_trans[…,t] is the posterior pairwise
+    marginal of (z_t, z_{t+1}) -- or None with want_trans=False (the other three do not change a bit).  Unbatched node
+    potentials return unbatched results.  One route, log space throughout (include/svae_hip.h): there is no fallback.
+    workspace: a contiguous float64 device tensor of at least svae_hmm_perstep_workspace_bytes(B,T,K) bytes.
+    lengths: (B,) integers, see the module docstring -- E_states[b, L:] and E_trans[b, L-1:] are exactly 0, and neither
+    node[b, L:] nor pair[b, L-1:] is read."""
+    B, T, K, batched, pair_batched = _perstep_shapes(natparam)
+    init_params, pair_params, node_params = natparam
+    lens = None if lengths is None else _lengths_arg(lengths, node_params)
+    dev = node_params.device if isinstance(node_params, torch.Tensor) and node_params.is_cuda \
+        else torch.device("cuda", torch.cuda.current_device())
+    init_params, pair_params, node = (_dev64(x, dev) for x in (init_params, pair_params, node_params))
+    lib = _lib.load()
+    f64 = dict(dtype=torch.float64, device=dev)
+    if workspace is None:
+        wsb = int(lib.svae_hmm_perstep_workspace_bytes(max(B, 1), T, K))
+        ws = torch.empty(wsb // 8, **f64)
+    else:
+        ws = workspace
+        wsb = ws.numel() * ws.element_size()
+    logZ = torch.empty(B, **f64)
+    E_init, E_states = torch.empty(B, K, **f64), torch.empty(B, T, K, **f64)
+    E_trans = torch.empty(B, T - 1, K, K, **f64) if want_trans else None
+    p = _lib.ptr
+    rc = lib.svae_hmm_perstep_estep_f64(B, T, K, int(pair_batched), p(init_params), p(pair_params), p(node), p(lens),
+                                        p(logZ), p(E_init), p(E_trans), p(E_states),
+                                        p(_status_word(dev)) if lens is not None else None, p(ws), wsb,
+                                        _lib.current_stream(dev))
+    _lib.check(rc, "svae_hmm_perstep_estep_f64")
+    if lens is not None and check:
+        check_lengths_status(dev)
+    if not batched:
+        return logZ[0], (E_init[0], None if E_trans is None else E_trans[0], E_states[0])
+    return logZ, (E_init, E_trans, E_states)
+
+
+def hmm_logZ_perstep(natparam, lengths=None):
+    """The log-normaliser of hmm_estep_perstep alone (the per-step pair marginals are not formed)."""
+    return hmm_estep_perstep(natparam, lengths=lengths, want_trans=False)[0]
+
+
+class _HMMLogZPerstep(torch.autograd.Function):
+    """log Z of HMMs with per-step transition potentials, differentiable w.r.t. all three natural parameters: the
+    gradients are the expected statistics of the same launch (E_init, the per-step E_trans, E_states), summed over the
+    batch where a parameter is shared."""
+
+    @staticmethod
+    def forward(ctx, init_params, pair_params, node_params, lengths):
+        logZ, (E_init, E_trans, E_states) = hmm_estep_perstep((init_params, pair_params, node_params), lengths=lengths)
+        ctx.save_for_backward(E_init, E_trans, E_states)
+        ctx.pair_batched = pair_params.dim() == 4
+        ctx.like = [(x.device, x.dtype) for x in (init_params, pair_params, node_params)]
+        return logZ
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g):
+        E_init, E_trans, E_states = ctx.saved_tensors
+        g = g.to(device=E_states.device, dtype=E_states.dtype)
+        d_init, d_pair, d_node = g[..., None] * E_init, g[..., None, None, None] * E_trans, g[..., None, None] * E_states
+        if E_states.dim() == 3:
+            d_init = d_init.sum(0)                    # shared parameters receive the batch sum
+            if not ctx.pair_batched:
+                d_pair = d_pair.sum(0)
+        need = ctx.needs_input_grad
+        out = [d.to(device=dv, dtype=dt) if n else None for d, (dv, dt), n in zip((d_init, d_pair, d_node), ctx.like, need)]
+        return out[0], out[1], out[2], None
+
+
+def hmm_logZ_perstep_differentiable(natparam, lengths=None):
+    """hmm_logZ_perstep with gradients flowing to init (K), pair (T-1,K,K) or (B,T-1,K,K) and node (T,K) or (B,T,K)
+    (torch tensors): E_init, the per-step E_trans and E_states of the same launch, times the incoming cotangent, summed
+    over the batch where the parameter is shared.  With lengths= they are exactly 0 from a sequence's length on (node
+    steps >= L, pair steps >= L-1).  The training path of time-varying transitions; once differentiable."""
+    init_params, pair_params, node_params = natparam
+    for x in (init_params, pair_params, node_params):
+        if not isinstance(x, torch.Tensor):
+            raise TypeError("hmm_logZ_perstep_differentiable takes torch tensors")
+    return _HMMLogZPerstep.apply(init_params, pair_params, node_params, lengths)
