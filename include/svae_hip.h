@@ -711,6 +711,57 @@ int svae_hmm_perstep_estep_f64(int B, int T, int K, int pair_batched,
                                double* logZ, double* E_init, double* E_trans /* or NULL */, double* E_states,
                                int32_t* info /* NULL only if lengths is */, void* workspace, size_t ws_bytes, void* stream);
 
+/* Viterbi decoding with PER-STEP transition potentials, K <= SVAE_HMM_MAX_K -- csrc/hmm_viterbi_perstep.hip.  Addition to
+ * ABI 15 (no new number).  Inputs, lengths and the status word as svae_hmm_perstep_estep_f64; the arithmetic is that of
+ * svae_hmm_viterbi_f64 with the step's own matrix, for sequence b of length L (= T without lengths):
+ *    delta_0[k] = init[k] + node[0][k]
+ *    delta_t[k] = (max_j (delta_{t-1}[j] + pair[t-1][j][k])) + node[t][k]      fp64, the additions in that order
+ *    psi_t[k]   = the LOWEST j attaining the maximum
+ *    z_{L-1}    = the lowest k attaining max_k delta_{L-1}[k];   z_t = psi_{t+1}[z_{t+1}];   score = delta_{L-1}[z_{L-1}]
+ *  Labels and score are reproducible bit for bit (where the reduction over j is split over wavefronts the shares are
+ *  combined in ascending j with a strict `>`, which keeps exactly this rule).  A step whose potentials are all -inf gives
+ *  score -inf and the labels the lowest-index rule gives; NaN inputs give unspecified labels in 0..K-1 and no fault.
+ *  out: states (B,T) int32, states[b, L:] = -1; score (B) or NULL.
+ *  Lengths: L clamped to [1,T], a value outside ORs 1 into `info` (a vector atomic); results up to L are those of the
+ *       sequence cut there; nothing at node steps >= L or pair steps >= L-1 is loaded; no sequence sees another's length or data.
+ *  workspace: at least svae_hmm_viterbi_workspace_bytes(B,T,K) (one back-pointer byte per step and padded state), 16-byte
+ *       aligned.
+ *  Returns 0, or (decided on the host before any HIP call, the first failing check) -1 B < 0, -2 T < 1, -3 K outside
+ *   1..SVAE_HMM_MAX_K, -4 pair_batched not 0 or 1, -5 init_params NULL, -6 pair_params NULL with T > 1, [B = 0 returns 0
+ *   here], -7 node_params NULL, -8 states NULL, -9 info NULL with lengths given, -10 workspace NULL, -11 ws_bytes too small,
+ *   -12 workspace not 16-byte aligned; -1000 launch error.  One launch, asynchronous on `stream`, no internal allocation,
+ *  safe under graph capture. */
+int svae_hmm_perstep_viterbi_f64(int B, int T, int K, int pair_batched,
+                                 const double* init_params, const double* pair_params, const double* node_params,
+                                 const int32_t* lengths /* or NULL */, int32_t* states, double* score /* or NULL */,
+                                 int32_t* info /* NULL only if lengths is */, void* workspace, size_t ws_bytes, void* stream);
+
+/* Posterior sampling (forward filter, backward draw) with PER-STEP transition potentials, K <= SVAE_HMM_MAX_K, S >= 1
+ * samples per sequence -- csrc/hmm_sample_perstep.hip.  Addition to ABI 15 (no new number).  Inputs, lengths and the status
+ * word as svae_hmm_perstep_estep_f64; u (B,S,T) uniforms; out: states (B,S,T) int32, states[b, :, L:] = -1; logZ (B) or NULL.
+ * ONE route, log space throughout, as the per-step E-step: no range flags, no second filter launch, nothing redone.
+ *    filter: la_0 = init + node_0;  la_{t+1}[k] = node_{t+1}[k] + logsumexp_j(la_t[j] + pair[t][j][k]) -- the forward sweep
+ *            of svae_hmm_perstep_estep_f64 itself; its unnormalised records la_t stay in the workspace;
+ *            logZ = logsumexp_k la_{L-1}[k], bit for bit the E-step's.
+ *    draw:   t = L-1: lw[k] = la_{L-1}[k];   t < L-1: lw[k] = la_t[k] + pair[t][k][z_{t+1}]
+ *            m = max_k lw[k], taken as 0 if that is -inf;  w[k] = exp(lw[k] - m)
+ *            and from there the selection rule of svae_hmm_sample_f64: C[k] = w[0] + .. + w[k] in index order,
+ *            thr = clamp(u,0,1) C[K-1] (a NaN u counts as 0),  z_t = #{k : C[k] <= thr and C[k] < C[K-1]}.
+ *  A state with a forbidden (-inf) transition or observation is never drawn; u = 0 draws the lowest allowed state, u = 1 the
+ *  highest.  A chain with logZ = -inf or NaN potentials gives unspecified labels in 0..K-1 and affects no other sequence;
+ *  every data-dependent index is masked into range before it addresses memory.
+ *  Lengths: as above; nothing at node steps >= L, pair steps >= L-1 or u steps >= L is loaded.
+ *  workspace: at least svae_hmm_perstep_workspace_bytes(B,T,K) (the E-step's la_t records), 16-byte aligned.
+ *  Returns 0, or (decided on the host before any HIP call, the first failing check) -1 .. -7 as svae_hmm_perstep_viterbi_f64,
+ *   -8 S < 1, -9 u NULL, -10 states NULL, -11 info NULL with lengths given, -12 workspace NULL, -13 ws_bytes too small,
+ *   -14 workspace not 16-byte aligned; -1000 launch error.  Two launches (filter, draw), asynchronous on `stream`, no
+ *  internal allocation, safe under graph capture. */
+int svae_hmm_perstep_sample_f64(int B, int T, int K, int S, int pair_batched,
+                                const double* init_params, const double* pair_params, const double* node_params,
+                                const int32_t* lengths /* or NULL */, const double* u,
+                                int32_t* states, double* logZ /* or NULL */,
+                                int32_t* info /* NULL only if lengths is */, void* workspace, size_t ws_bytes, void* stream);
+
 /* HMM step of the SLDS coordinate ascent on the rows `seq_index` lists (B of `rows`; NULL: rows 0..B-1; negative
  * entries = unused slots, which must follow the live ones -- the list svae_slds_sweep_glue_f64 writes):
  *   hmm_meanfield + get_arhmm_local_nodeparams   /root/reference/svae/models/slds_svae.py:108-115, 131-147

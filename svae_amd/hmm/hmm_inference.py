@@ -11,6 +11,8 @@
   hmm_estep_perstep(natparam) -> hmm_estep for PER-STEP transition potentials, pair (T-1,K,K) or (B,T-1,K,K); E_trans is
                                  then per step too, (…,T-1,K,K)                (csrc/hmm_estep_perstep.hip)
   hmm_logZ_perstep(natparam), hmm_logZ_perstep_differentiable(natparam) -> its log-normaliser, with gradients to all three
+  hmm_viterbi_perstep(natparam), hmm_sample_perstep(natparam, num_samples) -> hmm_viterbi / hmm_sample for per-step
+                                 transition potentials                        (csrc/hmm_viterbi_perstep.hip, hmm_sample_perstep.hip)
 
 natparam = (init_params (K), pair_params (K,K), node_params (T,K)) are LOG potentials, as in the
 reference.  New: node_params may be (B,T,K) (and pair_params (B,K,K)); outputs then carry a leading
@@ -540,3 +542,92 @@ def hmm_logZ_perstep_differentiable(natparam, lengths=None):
         if not isinstance(x, torch.Tensor):
             raise TypeError("hmm_logZ_perstep_differentiable takes torch tensors")
     return _HMMLogZPerstep.apply(init_params, pair_params, node_params, lengths)
+
+
+def _perstep_device(natparam, lengths):
+    """(lens, dev) of a per-step call whose shapes have been accepted: the validated (B,) int32 lengths or None, the device"""
+    node_params = natparam[2]
+    lens = None if lengths is None else _lengths_arg(lengths, node_params)
+    dev = node_params.device if isinstance(node_params, torch.Tensor) and node_params.is_cuda \
+        else torch.device("cuda", torch.cuda.current_device())
+    return lens, dev
+
+
+def hmm_viterbi_perstep(natparam, workspace=None, return_score=False, lengths=None, check=False):
+    """hmm_viterbi for the natparam hmm_estep_perstep takes -- init (K), pair (T-1,K,K) or (B,T-1,K,K), node (T,K) or
+    (B,T,K), LOG potentials, finite or -inf: labels torch.int32 (T,) or (B,T); with return_score also the path's score
+    (0-d, or (B)).  The arithmetic is hmm_viterbi's with the step's own matrix (include/svae_hip.h,
+    svae_hmm_perstep_viterbi_f64): labels and score are reproducible bit for bit, ties to the lowest index.
+    workspace: any contiguous device tensor of at least svae_hmm_viterbi_workspace_bytes(B,T,K) bytes.
+    lengths: (B,) integers, see the module docstring -- labels from a sequence's length on are -1, and neither node[b, L:]
+    nor pair[b, L-1:] is read."""
+    B, T, K, batched, pair_batched = _perstep_shapes(natparam)
+    lens, dev = _perstep_device(natparam, lengths)
+    init_params, pair_params, node = (_dev64(x, dev) for x in natparam)
+    lib = _lib.load()
+    if workspace is None:
+        wsb = int(lib.svae_hmm_viterbi_workspace_bytes(max(B, 1), T, K))
+        ws = torch.empty(wsb, dtype=torch.uint8, device=dev)
+    else:
+        ws = workspace
+        wsb = ws.numel() * ws.element_size()
+    states = torch.empty(B, T, dtype=torch.int32, device=dev)
+    score = torch.empty(B, dtype=torch.float64, device=dev) if return_score else None
+    p = _lib.ptr
+    rc = lib.svae_hmm_perstep_viterbi_f64(B, T, K, int(pair_batched), p(init_params), p(pair_params), p(node), p(lens),
+                                          p(states), p(score), p(_status_word(dev)) if lens is not None else None,
+                                          p(ws), wsb, _lib.current_stream(dev))
+    _lib.check(rc, "svae_hmm_perstep_viterbi_f64")
+    if lens is not None and check:
+        check_lengths_status(dev)
+    if not batched:
+        states = states[0]
+        score = score[0] if return_score else None
+    return (states, score) if return_score else states
+
+
+def hmm_sample_perstep(natparam, num_samples=1, u=None, generator=None, workspace=None, return_logZ=False, lengths=None,
+                       check=False):
+    """hmm_sample for the natparam hmm_estep_perstep takes: state paths drawn from the posterior by forward filtering and
+    backward sampling, labels torch.int32 (S,T) or (B,S,T), S = num_samples; with return_logZ also the log-normaliser the
+    filter computes (0-d, or (B)) -- bit for bit hmm_logZ_perstep's: the filter is the E-step's forward sweep.  One route,
+    log space throughout (include/svae_hip.h, svae_hmm_perstep_sample_f64): nothing is flagged or redone; a state with a
+    forbidden (-inf) transition or observation is never drawn.
+    u: the uniforms, (B,S,T) ((S,T) for the unbatched call); None draws torch.rand fp64 on the device with `generator`.
+    workspace: a contiguous device tensor of at least svae_hmm_perstep_workspace_bytes(B,T,K) bytes.
+    lengths: (B,) integers, see the module docstring -- labels from a sequence's length on are -1, and none of node[b, L:],
+    pair[b, L-1:] and u[b, :, L:] is read."""
+    B, T, K, batched, pair_batched = _perstep_shapes(natparam)
+    S = int(num_samples)
+    if S != num_samples or S < 1:
+        raise ValueError("num_samples must be an integer >= 1, got %r" % (num_samples,))
+    if B * S * T >= 2 ** 31:
+        raise ValueError("B * num_samples * T = %d is not below 2^31" % (B * S * T))
+    if u is not None and _shape_of(u) != ((B, S, T) if batched else (S, T)):
+        raise ValueError("u must have shape %r, got %r" % ((B, S, T) if batched else (S, T), _shape_of(u)))
+    lens, dev = _perstep_device(natparam, lengths)
+    init_params, pair_params, node = (_dev64(x, dev) for x in natparam)
+    if u is None:
+        u = torch.rand(B, S, T, dtype=torch.float64, device=dev, generator=generator)
+    else:
+        u = _dev64(u, dev).reshape(B, S, T)
+    lib = _lib.load()
+    if workspace is None:
+        wsb = int(lib.svae_hmm_perstep_workspace_bytes(max(B, 1), T, K))
+        ws = torch.empty(wsb // 8, dtype=torch.float64, device=dev)
+    else:
+        ws = workspace
+        wsb = ws.numel() * ws.element_size()
+    states = torch.empty(B, S, T, dtype=torch.int32, device=dev)
+    logZ = torch.empty(B, dtype=torch.float64, device=dev) if return_logZ else None
+    p = _lib.ptr
+    rc = lib.svae_hmm_perstep_sample_f64(B, T, K, S, int(pair_batched), p(init_params), p(pair_params), p(node), p(lens),
+                                         p(u), p(states), p(logZ), p(_status_word(dev)) if lens is not None else None,
+                                         p(ws), wsb, _lib.current_stream(dev))
+    _lib.check(rc, "svae_hmm_perstep_sample_f64")
+    if lens is not None and check:
+        check_lengths_status(dev)
+    if not batched:
+        states = states[0]
+        logZ = logZ[0] if return_logZ else None
+    return (states, logZ) if return_logZ else states
