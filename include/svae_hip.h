@@ -247,7 +247,8 @@ int svae_lds_tile_noise_f64(int mode, int B, int T, int n, int S, int t_begin, i
  *  out: init_J (n,n) = -1/2 E[J], init_h (n) = E[h], init_logZ (1) = -1/2 E[h'J^-1 h] + 1/2 E[log|J|];
  *       J11, J12, J22 (n,n), logZ_pair (1) = the MNIW expected statistics;
  *       niw_expectedstats (n+2,n+2) dense-packed or NULL; global_kl (1) or NULL;
- *       info: 1 if an inversion met a non-positive pivot (natural parameters outside the domain).   n <= 64. */
+ *       info: 1 if an inversion met a non-positive pivot, kappa <= 0 or nu <= n - 1 of either factor (natural parameters
+ *       outside the domain; the prior's likewise).   n <= 64. */
 int svae_lds_global_step_f64(int n, const double* niw, const double* mniw_A, const double* mniw_B,
                              const double* mniw_C, const double* mniw_d,
                              const double* prior_niw, const double* prior_A, const double* prior_B,
@@ -904,7 +905,8 @@ int svae_gmm_mw_fixed_point_f64(int T, int N, int K,
  *                           given, the prior KL of gmm.py:54-58: kl[0] as the code spells it (full contraction;
  *                           dirichlet.logZ, niw.logZ), kl[1] as the reference AS SHIPPED evaluates it (util.py:39 `flat`
  *                           after util.py:166 rebinds `flatten`: the contraction keeps its first term only).  *info is
- *                           raised to 1 on a non-positive-definite NIW scale matrix. */
+ *                           raised to 1 on invalid parameters of the global factor or the prior: a non-positive-definite
+ *                           NIW scale matrix, kappa <= 0, nu <= N - 1, a Dirichlet alpha <= 0. */
 int svae_gmm_global_step_f64(int K, int N, const double* dirichlet_natparam, const double* niw_natparam,
                              const double* prior_dirichlet, const double* prior_niw,
                              double* label_global, double* gaussian_globals, double* kl, int32_t* info, void* stream);

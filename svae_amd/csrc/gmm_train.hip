@@ -21,6 +21,7 @@
 #include <stdint.h>
 
 #include "../../include/svae_hip.h"
+#include "special_fn.hpp"
 
 namespace svae {
 
@@ -280,15 +281,6 @@ __global__ __launch_bounds__(256) void gmm_local_vjp_kernel(
 // -> the potentials the fixed-point kernels take, and the prior KL of gmm.py:54-58 (with dirichlet.logZ dirichlet.py:9-11,
 // niw.logZ niw.py:27-31).  One lane per component (K <= 64, N <= 8: a component's matrices live in registers); the sums
 // over components are wavefront butterflies.  In torch the same maps are ~60 small launches (1.4 ms of a 2.2 ms step).
-__device__ inline double gmm_digamma_pos(double x) {
-  double acc = 0.0;
-  while (x < 10.0) { acc -= 1.0 / x; x += 1.0; }
-  const double r = 1.0 / x, r2 = r * r;
-  const double s = -1.0 / 12.0 + r2 * (1.0 / 120.0 + r2 * (-1.0 / 252.0 + r2 * (1.0 / 240.0 + r2 * (-1.0 / 132.0
-                   + r2 * (691.0 / 32760.0 + r2 * (-1.0 / 12.0))))));
-  return acc + log(x) - 0.5 * r + r2 * s;
-}
-
 __device__ __forceinline__ double gmm_wave_sum(double v) {
 #pragma unroll
   for (int m = 1; m < 64; m <<= 1) v += __shfl_xor(v, m, 64);
@@ -296,7 +288,8 @@ __device__ __forceinline__ double gmm_wave_sum(double v) {
 }
 
 // NIW natural parameter (dense (N+2)x(N+2)) -> standard (S, m, kappa, nu); S^-1 and log|S| by Gauss-Jordan without
-// pivoting (S is SPD for a valid parameter; a non-positive pivot clears *ok)
+// pivoting (S is SPD for a valid parameter; a non-positive pivot clears ok, and so do kappa <= 0 and nu <= N - 1, for
+// which the maps are NaN or meaningless with every pivot positive)
 template <int N>
 struct NiwStd { double Sinv[N][N], m[N], kappa, nu, logdet; bool ok; };
 
@@ -305,15 +298,19 @@ __device__ __forceinline__ void niw_standard(const double* nat, NiwStd<N>& q, bo
   constexpr int D = N + 2;
   q.kappa = nat[N * D + N];
   q.nu = nat[(N + 1) * D + N + 1];
-  double S[N][N], b[N];
+  double S[N][N], b[N], mr[N];
 #pragma unroll
-  for (int i = 0; i < N; ++i) { b[i] = nat[i * D + N]; q.m[i] = b[i] / q.kappa; }
+  for (int i = 0; i < N; ++i) {
+    b[i] = nat[i * D + N];
+    q.m[i] = b[i] / q.kappa;
+    mr[i] = niw_mean_residual(b[i], q.m[i], q.kappa);
+  }
 #pragma unroll
   for (int i = 0; i < N; ++i)
 #pragma unroll
-    for (int j = 0; j < N; ++j) S[i][j] = nat[i * D + j] - b[i] * q.m[j];
+    for (int j = 0; j < N; ++j) S[i][j] = niw_scale_entry(nat[i * D + j], b[i], q.m[j], mr[j]);
   // in-place Gauss-Jordan: S -> S^-1, pivots -> log det
-  q.ok = true;
+  q.ok = (q.kappa > 0.0) && (q.nu > (double)(N - 1));
   double ld = 0.0;
 #pragma unroll
   for (int k = 0; k < N; ++k) {
@@ -372,7 +369,7 @@ __global__ __launch_bounds__(64) void gmm_global_step_kernel(int K, const double
   // ---- Dirichlet factor ----
   const double alpha = dir_nat[kk] + 1.0;
   const double asum = gmm_wave_sum(on ? alpha : 0.0);
-  const double es_dir = gmm_digamma_pos(alpha) - gmm_digamma_pos(asum);
+  const double es_dir = digamma_pos(alpha) - digamma_pos(asum);
   if (on) label_global[k] = es_dir;
   // ---- NIW factors ----
   NiwStd<N> q;
@@ -394,7 +391,7 @@ __global__ __launch_bounds__(64) void gmm_global_step_kernel(int K, const double
   const double E_hJh = (double)N / q.kappa + mEh;
   double dg = 0.0;
 #pragma unroll
-  for (int i = 0; i < N; ++i) dg += gmm_digamma_pos(0.5 * (q.nu - i));
+  for (int i = 0; i < N; ++i) dg += digamma_pos(0.5 * (q.nu - i));
   const double E_logdet = dg + N * 0.6931471805599453094 - q.logdet;
   if (on) {
     double* G = gaussian_globals + (long)k * D * D;
@@ -410,7 +407,7 @@ __global__ __launch_bounds__(64) void gmm_global_step_kernel(int K, const double
         G[i * D + j] = v;
       }
   }
-  const bool bad = __ballot(on && !q.ok) != 0;
+  const bool bad = __ballot(on && !(q.ok && alpha > 0.0)) != 0;        // (every alpha > 0: their sum too)
   if (bad && k == 0) atomicMax(info, 1);
   if (!kl) return;
   // ---- prior KL (gmm.py:54-58): <eta_q - eta_p, E_q t> - (logZ(q) - logZ(p)) ----
@@ -431,8 +428,12 @@ __global__ __launch_bounds__(64) void gmm_global_step_kernel(int K, const double
   }
   const double palpha = prior_dir[kk] + 1.0;
   const double psum = gmm_wave_sum(on ? palpha : 0.0);
-  const double lz = (lgamma(alpha) - lgamma(palpha)) + (niw_logZ_one<N>(q) - niw_logZ_one<N>(pq));
-  const double mlz = gmm_wave_sum(on ? -lz : 0.0) + (lgamma(asum) - lgamma(psum));   // -(logZ(q) - logZ(p))
+  // -(logZ(q) - logZ(p)).  The Dirichlet part on its own: sum_k lgamma(alpha_k) and lgamma(sum_k alpha_k) cancel (exactly
+  // for K = 1, to ~alpha_min psi for one dominant alpha = 1e8), and an NIW term added to lgamma(1e8) = 1.7e9 first would
+  // lose its digits below 2e-7
+  const double lz_dir = lgamma(alpha) - lgamma(palpha);
+  const double lz_niw = niw_logZ_one<N>(q) - niw_logZ_one<N>(pq);
+  const double mlz = ((lgamma(asum) - lgamma(psum)) - gmm_wave_sum(on ? lz_dir : 0.0)) - gmm_wave_sum(on ? lz_niw : 0.0);
   const double total = gmm_wave_sum(on ? contr : 0.0) + mlz;
   if (k == 0) {
     kl[0] = total;
@@ -440,7 +441,7 @@ __global__ __launch_bounds__(64) void gmm_global_step_kernel(int K, const double
     // (util.py:166 rebinds `flatten`) keeps the FIRST scalar of the nested structure: the contraction is its first term
     kl[1] = (dir_nat[0] - prior_dir[0]) * es_dir + mlz;
   }
-  const bool pbad = __ballot(on && !pq.ok) != 0;
+  const bool pbad = __ballot(on && !(pq.ok && palpha > 0.0)) != 0;
   if (pbad && k == 0) atomicMax(info, 1);
 }
 

@@ -20,6 +20,7 @@
 
 #include "../../include/svae_hip.h"
 #include "dpp.hpp"
+#include "special_fn.hpp"
 
 namespace svae {
 namespace gwide {
@@ -594,15 +595,6 @@ __global__ __launch_bounds__(WBLOCK) void wide_chol_vjp_kernel(int T, int S, con
 }
 
 // ---- global step: one row per NIW component ---------------------------------------------------------------------------
-__device__ inline double digamma_pos(double x) {
-  double acc = 0.0;
-  while (x < 10.0) { acc -= 1.0 / x; x += 1.0; }
-  const double r = 1.0 / x, r2 = r * r;
-  const double s = -1.0 / 12.0 + r2 * (1.0 / 120.0 + r2 * (-1.0 / 252.0 + r2 * (1.0 / 240.0 + r2 * (-1.0 / 132.0
-                   + r2 * (691.0 / 32760.0 + r2 * (-1.0 / 12.0))))));
-  return acc + log(x) - 0.5 * r + r2 * s;
-}
-
 // NIW natural parameter (dense (N+2)x(N+2)) -> row i of S^-1 (X), m_i, kappa, nu, log|S|, ok
 template <int N>
 __device__ __forceinline__ void niw_row_standard(const double* nat, int i, double (&X)[N], double& m, double& kappa,
@@ -615,9 +607,12 @@ __device__ __forceinline__ void niw_row_standard(const double* nat, int i, doubl
   m = bi / kappa;
   double W[N], d[N], Lr[N], Lc[N];
 #pragma unroll
-  for (int c = 0; c < N; ++c) W[c] = act ? nat[i * D + c] - bi * (nat[c * D + N] / kappa) : 0.0;
+  for (int c = 0; c < N; ++c) {
+    const double bc = nat[c * D + N], mc = bc / kappa;
+    W[c] = act ? niw_scale_entry(nat[i * D + c], bi, mc, niw_mean_residual(bc, mc, kappa)) : 0.0;
+  }
   row_factor<N, false>(i, W, X, d, Lr, Lc);
-  ok = true;
+  ok = (kappa > 0.0) && (nu > (double)(N - 1));      // (NaN / meaningless maps with every pivot positive otherwise)
   logdet = 0.0;
 #pragma unroll
   for (int j = 0; j < N; ++j) { ok = ok && (d[j] > 0.0); logdet += log(d[j]); }
@@ -631,7 +626,8 @@ __device__ __forceinline__ double niw_logZ_row(double nu, double kappa, double l
   return 0.5 * N * nu * 0.6931471805599453094 + mg - 0.5 * nu * logdet - 0.5 * N * log(kappa);
 }
 
-// one component on the caller's row -> its contraction term and logZ difference (prior KL) in *contr / *lz
+// one component on the caller's row -> its contraction term and its logZ differences (prior KL: the Dirichlet log-gamma
+// term and the NIW log-normalisers apart) in contr / lz_dir / lz
 template <int N>
 __device__ __forceinline__ void wide_global_one(const int k, const int i, const double asum,
                                                 const double* __restrict__ dir_nat, const double* __restrict__ niw_nat,
@@ -639,7 +635,7 @@ __device__ __forceinline__ void wide_global_one(const int k, const int i, const 
                                                 const double* __restrict__ prior_niw,
                                                 double* __restrict__ label_global,
                                                 double* __restrict__ gaussian_globals, const bool want_kl,
-                                                double& es_dir, double& contr, double& lz, bool& bad) {
+                                                double& es_dir, double& contr, double& lz_dir, double& lz, bool& bad) {
   constexpr int D = N + 2;
   const bool act = i < N;
   // ---- Dirichlet factor (dirichlet.py:5-7) ----
@@ -686,7 +682,7 @@ __device__ __forceinline__ void wide_global_one(const int k, const int i, const 
       G[row * D + c] = v;
     }
   }
-  bad = !ok;
+  bad = !(ok && alpha > 0.0);
   if (!want_kl) return;
   // ---- prior KL terms (gmm.py:54-58): <eta_q - eta_p, E_q t>, logZ(q) - logZ(p) ----
   const double* pn = prior_niw + (long)k * D * D;
@@ -707,9 +703,9 @@ __device__ __forceinline__ void wide_global_one(const int k, const int i, const 
   contr = __builtin_fma(nat[N * D + N] - pn[N * D + N], -0.5 * E_hJh, contr);
   contr = __builtin_fma(nat[(N + 1) * D + N + 1] - pn[(N + 1) * D + N + 1], 0.5 * E_logdet, contr);
   const double palpha = prior_dir[k] + 1.0;
-  lz = (lgamma(alpha) - lgamma(palpha)) +
-       (niw_logZ_row<N>(nu, kappa, logdet) - niw_logZ_row<N>(pnu, pkappa, plogdet));
-  bad = bad || !pok;
+  lz_dir = lgamma(alpha) - lgamma(palpha);
+  lz = niw_logZ_row<N>(nu, kappa, logdet) - niw_logZ_row<N>(pnu, pkappa, plogdet);
+  bad = bad || !(pok && palpha > 0.0);
 }
 
 // One workgroup of 16 rows; row r takes the components r, r + 16, .. < K.  The sums over components run in index
@@ -722,7 +718,7 @@ __global__ __launch_bounds__(WBLOCK) void wide_global_step_kernel(int K, const d
                                                                   double* __restrict__ label_global,
                                                                   double* __restrict__ gaussian_globals,
                                                                   double* __restrict__ kl, int32_t* __restrict__ info) {
-  __shared__ double sh_contr[WMAX_K], sh_lz[WMAX_K], sh_es0;
+  __shared__ double sh_contr[WMAX_K], sh_lz[WMAX_K], sh_lzd[WMAX_K], sh_es0;
   __shared__ int sh_bad;
   const int i = threadIdx.x & 15, r = threadIdx.x >> 4;
   if (threadIdx.x == 0) sh_bad = 0;
@@ -730,13 +726,14 @@ __global__ __launch_bounds__(WBLOCK) void wide_global_step_kernel(int K, const d
   double asum = 0.0;
   for (int j = 0; j < K; ++j) asum += dir_nat[j] + 1.0;
   for (int k = r; k < K; k += WROWS) {
-    double es = 0.0, contr = 0.0, lz = 0.0;
+    double es = 0.0, contr = 0.0, lzd = 0.0, lz = 0.0;
     bool bad = false;
     wide_global_one<N>(k, i, asum, dir_nat, niw_nat, prior_dir, prior_niw, label_global, gaussian_globals,
-                       kl != nullptr, es, contr, lz, bad);
+                       kl != nullptr, es, contr, lzd, lz, bad);
     if (i == 0) {
       sh_contr[k] = contr;
       sh_lz[k] = lz;
+      sh_lzd[k] = lzd;
       if (k == 0) sh_es0 = es;
       if (bad) atomicOr(&sh_bad, 1);
     }
@@ -747,9 +744,11 @@ __global__ __launch_bounds__(WBLOCK) void wide_global_step_kernel(int K, const d
   if (!kl) return;
   double psum = 0.0;
   for (int j = 0; j < K; ++j) psum += prior_dir[j] + 1.0;
-  double c = 0.0, mlz = 0.0;
-  for (int j = 0; j < K; ++j) { c += sh_contr[j]; mlz -= sh_lz[j]; }
-  mlz += lgamma(asum) - lgamma(psum);                 // -(logZ(q) - logZ(p))
+  // -(logZ(q) - logZ(p)), the Dirichlet part on its own: sum_k lgamma(alpha_k) and lgamma(sum_k alpha_k) cancel, and an NIW
+  // term added to lgamma(1e8) = 1.7e9 first would lose its digits below 2e-7 (svae_gmm_global_step_f64 does the same)
+  double c = 0.0, lzd = 0.0, lzn = 0.0;
+  for (int j = 0; j < K; ++j) { c += sh_contr[j]; lzd += sh_lzd[j]; lzn += sh_lz[j]; }
+  const double mlz = ((lgamma(asum) - lgamma(psum)) - lzd) - lzn;
   kl[0] = c + mlz;
   // kl[1]: the value the reference AS SHIPPED returns (svae_gmm_global_step_f64): the contraction's first term only
   kl[1] = (dir_nat[0] - prior_dir[0]) * sh_es0 + mlz;

@@ -8,29 +8,21 @@
 //   * the natural-gradient expression of svae/svae.py:33-34 on the packed statistics buffer the E-step's batch
 //     reduction (svae_lds_reduce_stats_f64, after the all-reduce) leaves: one launch.
 // n <= 64; everything float64.  Inversions are in-LDS Gauss-Jordan eliminations without pivoting (the matrices
-// are SPD whenever the natural parameters are valid; a non-positive pivot is reported through `info`).
+// are SPD whenever the natural parameters are valid; a non-positive pivot is reported through `info`, and so are
+// kappa <= 0 and nu <= n - 1 of either factor).
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
 
 #include "../../include/svae_hip.h"
 #include "per_device.hpp"
+#include "special_fn.hpp"
 
 namespace svae {
 
 constexpr int GL_BLOCK = 256;
 constexpr int GL_MAX_N = 64;
 constexpr double GL_FUDGE = 1e-8;      // niw.py:18, mniw.py:43-44
-
-// psi(x), x > 0: recurrence up to x >= 10, then the asymptotic series (error < 1e-16 there)
-__device__ inline double digamma_pos(double x) {
-  double acc = 0.0;
-  while (x < 10.0) { acc -= 1.0 / x; x += 1.0; }
-  const double r = 1.0 / x, r2 = r * r;
-  double s = -1.0 / 12.0 + r2 * (1.0 / 120.0 + r2 * (-1.0 / 252.0 + r2 * (1.0 / 240.0 + r2 * (-1.0 / 132.0
-             + r2 * (691.0 / 32760.0 + r2 * (-1.0 / 12.0))))));
-  return acc + log(x) - 0.5 * r + r2 * s;
-}
 
 // sum_{i<n} psi((nu - i)/2)  and  multigammaln(nu/2, n)  (scipy.special.multigammaln): every thread returns both
 __device__ inline void wishart_terms(double nu, int n, double* red, double& psi_sum, double& mgl) {
@@ -162,7 +154,6 @@ __device__ __forceinline__ void lds_global_body(const GlobalArgs& a, const int p
   if (tid == 0) bad = 0;
   __syncthreads();
 
-  double kl = 0.0;                  // accumulated by thread 0 only where noted
   // two passes, one WORKGROUP each (they are independent): q = 0 the global factors (outputs written), q = 1 the
   // prior (log-normalisers only).  Each adds its share of the KL to *global_kl (zeroed by the launcher): two terms,
   // so the sum does not depend on the order of the two atomic additions.
@@ -177,13 +168,20 @@ __device__ __forceinline__ void lds_global_body(const GlobalArgs& a, const int p
     const double nu2 = q ? a.p_md[0] : a.md[0];
     // ---- NIW: S = A - b m', m = b / kappa -----------------------------------------------------------
     const double kappa = niw[n * D + n], nu = niw[(n + 1) * D + n + 1];
-    for (int j = tid; j < n; j += blockDim.x) v0[j] = niw[j * D + n] / kappa;          // m
+    // (kappa <= 0, nu <= n - 1: NaN or meaningless maps with every pivot positive -- reported like a non-positive pivot)
+    if (tid == 0 && !(kappa > 0.0 && nu > (double)(n - 1) && nu2 > (double)(n - 1))) bad = 1;
+    for (int j = tid; j < n; j += blockDim.x) {
+      v0[j] = niw[j * D + n] / kappa;                                                   // m
+      v1[j] = niw_mean_residual(niw[j * D + n], v0[j], kappa);                          // (what m_j dropped of b_j / kappa)
+    }
     __syncthreads();
     for (int e = tid; e < n * n; e += blockDim.x) {
       const int i = e / n, j = e % n;
-      W0[e] = niw[i * D + j] - niw[i * D + n] * v0[j];
+      W0[e] = niw_scale_entry(niw[i * D + j], niw[i * D + n], v0[j], v1[j]);
     }
     __syncthreads();
+    double trS = 0.0;                                                                   // (thread 0, for the contraction below)
+    if (tid == 0 && q == 0 && a.p_niw) for (int j = 0; j < n; ++j) trS += W0[j * n + j];
     const double logdetS = spd_inverse(W0, n, n, rowk, colk, &bad, alt);
     symmetrize(W0, n, n);
     double psi, mgl;
@@ -207,17 +205,25 @@ __device__ __forceinline__ void lds_global_body(const GlobalArgs& a, const int p
         const double val = -0.5 * W0[e];
         a.init_J[e] = val;
         if (a.niw_es) a.niw_es[(e / n) * D + (e % n)] = val;
-        if (a.p_niw) es_dot = __builtin_fma(a.p_niw[(e / n) * D + (e % n)] - a.niw[(e / n) * D + (e % n)], val, es_dot);
+        if (a.p_niw) {
+          // <prior - global, E t> of the NIW, not term by term: for a mean far off the spread the products with A, b and
+          // kappa are |m|^2 kappa nu / |S| each and cancel to ~n nu.  With Q(A*, b*, kappa*) = A* - b* m' - m b*' + kappa* m m'
+          // the three terms of a parameter are -1/2 tr(E_J Q), and Q(global) = S exactly: tr(E_J S) = n nu + fudge tr S.
+          const int i = e / n, j = e % n;
+          const double pbi = a.p_niw[i * D + n], pbj = a.p_niw[j * D + n];
+          const double Qp = a.p_niw[i * D + j] - pbi * v0[j] - v0[i] * pbj + a.p_niw[n * D + n] * v0[i] * v0[j];
+          es_dot = __builtin_fma(val, Qp, es_dot);
+        }
       }
       for (int j = tid; j < n; j += blockDim.x) {
         a.init_h[j] = v1[j];
         if (a.niw_es) a.niw_es[j * D + n] = v1[j];
-        if (a.p_niw) es_dot = __builtin_fma(a.p_niw[j * D + n] - a.niw[j * D + n], v1[j], es_dot);
       }
       if (tid == 0) {
         a.init_logZ[0] = es_c + es_d;
         if (a.niw_es) { a.niw_es[n * D + n] = es_c; a.niw_es[(n + 1) * D + n + 1] = es_d; }
-        if (a.p_niw) es_dot += (a.p_niw[n * D + n] - kappa) * es_c + (a.p_niw[(n + 1) * D + n + 1] - nu) * es_d;
+        if (a.p_niw) es_dot += 0.5 * (nu * n + GL_FUDGE * trS) - 0.5 * n * ((a.p_niw[n * D + n] - kappa) / kappa)
+                               + (a.p_niw[(n + 1) * D + n + 1] - nu) * es_d;
       }
       if (a.niw_es) {   // the structurally zero entries of the dense packing
         for (int e = tid; e < D * D; e += blockDim.x) {
@@ -273,16 +279,37 @@ __device__ __forceinline__ void lds_global_body(const GlobalArgs& a, const int p
         const double j12 = nu2 * W0[j * n + i];                                        // (nu SinvM)'
         const double j22 = -0.5 * (nu2 * W3[e] + ((i == j) ? GL_FUDGE : 0.0));
         a.J11[e] = j11; a.J12[e] = j12; a.J22[e] = j22;
-        if (a.p_niw) {
-          es_dot = __builtin_fma(a.p_mA[e] - a.mA[e], j11, es_dot);
-          es_dot = __builtin_fma(a.p_mB[e] - a.mB[e], j12, es_dot);
-          es_dot = __builtin_fma(a.p_mC[e] - a.mC[e], j22, es_dot);
-        }
       }
       const double lz = 0.5 * (psi2 + n * 0.69314718055994530942 - logdetS2);
+      if (a.p_niw) {
+        // <prior - global, E t> of the MNIW likewise: with Q(A*, B*, C*) = C* - M B* - B*' M' + M A* M' the three terms of a
+        // parameter are -1/2 nu tr(S^-1 Q) - 1/2 n tr(K A*) - 1/2 fudge (tr A* + tr C*), and Q(global) = S, K A = I exactly.
+        // Term by term the products are |M|^2 |A| nu / |S| each, and the error of S = C - M B entered the KL times nu / 2;
+        // this way the KL holds log|S| only as (nu_prior / 2) log|S|.
+        __syncthreads();                                                               // (W0 = SinvM has been read)
+        for (int e = tid; e < n * n; e += blockDim.x) {                                 // W0 = A_prior M'
+          const int i = e / n, j = e % n;
+          double s = 0.0;
+          for (int k = 0; k < n; ++k) s = __builtin_fma(a.p_mA[i * n + k], W2[k * n + j], s);
+          W0[e] = s;
+        }
+        __syncthreads();
+        for (int e = tid; e < n * n; e += blockDim.x) {
+          const int i = e / n, j = e % n;
+          double qp = a.p_mC[e];
+          for (int k = 0; k < n; ++k) {
+            qp = __builtin_fma(-W2[k * n + i], a.p_mB[k * n + j], qp);
+            qp = __builtin_fma(-a.p_mB[k * n + i], W2[k * n + j], qp);
+            qp = __builtin_fma(W2[k * n + i], W0[k * n + j], qp);
+          }
+          es_dot = __builtin_fma(-0.5 * nu2 * W3[e], qp, es_dot);
+          es_dot = __builtin_fma(-0.5 * n * W1[e], a.p_mA[e], es_dot);
+          if (i == j) es_dot -= 0.5 * GL_FUDGE * ((a.p_mA[e] - a.mA[e]) + (a.p_mC[e] - a.mC[e]));
+        }
+      }
       if (tid == 0) {
         a.logZ_pair[0] = lz;
-        if (a.p_niw) es_dot += (a.p_md[0] - a.md[0]) * lz;
+        if (a.p_niw) es_dot += 0.5 * n * (nu2 + n) + (a.p_md[0] - a.md[0]) * lz;
       }
       __syncthreads();
     } else {
@@ -296,7 +323,7 @@ __device__ __forceinline__ void lds_global_body(const GlobalArgs& a, const int p
       if (tid < s) red[tid] += red[tid + s];
       __syncthreads();
     }
-    if (tid == 0) atomicAdd(a.global_kl, pass == 0 ? -red[0] - logZ_g + kl : logZ_p);   // lds.py:16-20
+    if (tid == 0) atomicAdd(a.global_kl, pass == 0 ? -red[0] - logZ_g : logZ_p);   // lds.py:16-20
   }
   if (tid == 0 && bad) atomicMax(a.info, 1);
 }

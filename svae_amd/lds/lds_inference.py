@@ -594,7 +594,8 @@ class LDSEStepPlan(object):
             self.info.zero_()
             raise FloatingPointError("LDS E-step: sequence %d hit a non-positive pivot "
                                      "(potentials not positive definite; through models.lds.run_inference also: the "
-                                     "global natural parameters are not valid; with lengths= also: a length outside 1..T)"
+                                     "global natural parameters are not valid -- a scale matrix that is not positive "
+                                     "definite, kappa <= 0 or nu <= n - 1; with lengths= also: a length outside 1..T)"
                                      % (v - 1))
 
 

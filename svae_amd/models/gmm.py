@@ -218,7 +218,10 @@ def global_step(global_natparam, prior_natparam=None, info=None, reference_compa
     of gmm.py:54-58 -- `reference_compat=True` (default): the value the reference AS SHIPPED returns (its `flat`,
     util.py:39 after util.py:166, keeps the first scalar: the contraction is its first term); False: the full
     contraction the code spells.  The kernel writes both.  -> (label_global, gaussian_globals, kl | None).  `info`:
-    (1,) int32 status word, raised to 1 on an invalid NIW scale matrix (kept as global_step.last_info, never read here)."""
+    (1,) int32 status word, raised to 1 on invalid global parameters -- of the global factor or of the prior: an NIW scale
+    matrix that is not positive definite (a non-positive pivot), kappa <= 0, nu <= N - 1, or a Dirichlet alpha <= 0 (natural
+    parameter <= -1); the potentials of such a component are NaN or meaningless, those of the valid components are not
+    touched (kept as global_step.last_info, never read here)."""
     dev = torch.device("cuda", torch.cuda.current_device())
     for x in global_natparam:
         if isinstance(x, torch.Tensor) and x.is_cuda:

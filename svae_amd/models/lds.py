@@ -74,8 +74,9 @@ def global_step(global_natparam, prior_natparam=None, info=None):
     (NIW dense (n+2,n+2), (A, B, C, d)).  Returns ((init_params, pair_params), global_kl | None, niw_expectedstats)
     with init_params = (-1/2 E[J], E[h], logZ) and pair_params = (J11, J12, J22, logZ) as the E-step takes them.
     Same values as local_natparam_from_global / lds_prior_kl (the torch path, ~150 small launches).
-    `info`: (1,) int32 device status word; the kernel raises it to 1 on a non-positive Gauss-Jordan pivot, i.e. global
-    natural parameters that are not valid (the reference asserts is_posdef in mniw.expectedstats, mniw.py:49-50).
+    `info`: (1,) int32 device status word; the kernel raises it to 1 on global natural parameters (or prior ones) that are
+    not valid: a non-positive Gauss-Jordan pivot (an NIW / MNIW scale matrix or K^-1 that is not positive definite; the
+    reference asserts is_posdef in mniw.expectedstats, mniw.py:49-50), kappa <= 0, or nu <= n - 1 of either factor.
     Without one a fresh word is allocated and kept as `global_step.last_info` -- never read here: checking costs a
     host synchronisation; run_inference passes the plan's word, so that plan.check_info() reports it."""
     niw, (A, B, C, d) = global_natparam

@@ -65,7 +65,8 @@ def _status_word(name, device):
 
 def check_info():
     """Synchronising check of the status words the SLDS device paths leave on the device -- the global -> local maps
-    (a non-positive-definite NIW / MNIW scale), the diagonal initial sample path (a non-positive precision) and the
+    (a non-positive-definite NIW / MNIW scale or K^-1, kappa <= 0, nu <= n - 1 of either factor of any state), the diagonal
+    initial sample path (a non-positive precision) and the
     fused LDS mean-field kernel (a non-positive pivot) -- like gmm.check_info(): the ascent itself never reads them
     (no host synchronisation on the hot path; the reference ignores LAPACK `info` altogether,
     cython_gaussian_grads.pxd:54-76).  Raises FloatingPointError naming the path."""
@@ -76,7 +77,8 @@ def check_info():
             word.zero_()                       # (every word is read and cleared before anything is raised)
             bad.append("%s on %s: status word %d" % (name, device, v))
     if bad:
-        raise FloatingPointError("SLDS " + "; ".join(bad) + " (parameters / potentials not positive definite; "
+        raise FloatingPointError("SLDS " + "; ".join(bad) + " (parameters / potentials not positive definite, or "
+                                 "kappa <= 0 / nu <= n - 1 in the global parameters; "
                                  "with lengths=: a length outside 2..T)")
 
 
