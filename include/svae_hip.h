@@ -834,6 +834,8 @@ int svae_slds_pair_contract_f64(int B, int T, int K, int n, const double* pair_s
  *       dirichlet_stats (K), niw_stats (K,N+2,N+2)      (sums over points, :80-81)
  *       kl (1) = label_kl + gaussian_kl (:86),  iters (1) number of fixed-point iterations run
  *       assign (T) int32 argmax_k label_stats
+ *       info (1) int32 status word, untouched on valid input: t + 1 of the LOWEST point t whose Gaussian factor met a
+ *         non-positive pivot or whose KL term is not finite (a NaN or infinite potential passes every pivot test)
  *  Limits: N <= 8, K <= 64.  Single workgroup (the minibatch total KL is a block reduction).
  */
 int svae_gmm_meanfield_f64(int T, int N, int K,

@@ -34,7 +34,8 @@ def label_meanfield(label_global, gaussian_globals, gaussian_stats):
 
 
 def meanfield_fixed_point(label_global, gaussian_globals, node_potentials, label_init,
-                          tol=1e-3, max_iter=100, return_iters=False):
+                          tol=1e-3, max_iter=100, return_iters=False, kl_hist=None):
+    """`kl_hist`: a list that receives the batch-total KL of every sweep (what the stopping rule compares)"""
     kl = np.inf
     label_stats = label_init
     it = 0
@@ -49,18 +50,24 @@ def meanfield_fixed_point(label_global, gaussian_globals, node_potentials, label
         linear_difference = gaussian_natparam - gaussian_global_potentials - node_potentials
         gaussian_kl = gaussian_kl + np.tensordot(linear_difference, gaussian_stats, 3)
         kl, prev_kl = label_kl + gaussian_kl, kl
+        if kl_hist is not None:
+            kl_hist.append(kl)
         if abs(kl - prev_kl) < tol:
             break
     return (label_stats, it) if return_iters else label_stats
 
 
 def local_meanfield(label_global, gaussian_globals, node_potentials, label_init,
-                    tol=1e-3, max_iter=100):
+                    tol=1e-3, max_iter=100, trace=None):
     """gmm.py:62-88 with the two global->local maps (dirichlet/niw expectedstats, :67-68) already
-    applied by the caller, and node_potentials = (J diag (T,N), h (T,N))."""
+    applied by the caller, and node_potentials = (J diag (T,N), h (T,N)).  `trace`: a dict that receives
+    `label_fixed` (the responsibilities entering the final pass) and `kl_hist` (the KL of every sweep)."""
     node_potentials = ef.pack_dense(*node_potentials)
+    hist = []
     label_stats, iters = meanfield_fixed_point(label_global, gaussian_globals, node_potentials,
-                                               label_init, tol, max_iter, return_iters=True)
+                                               label_init, tol, max_iter, return_iters=True, kl_hist=hist)
+    if trace is not None:
+        trace["label_fixed"], trace["kl_hist"] = label_stats, np.array(hist, float)
     gaussian_natparam, gaussian_stats, gaussian_kl = \
         gaussian_meanfield(gaussian_globals, node_potentials, label_stats)
     label_natparam, label_stats, label_kl = \

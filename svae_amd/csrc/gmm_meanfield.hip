@@ -125,8 +125,9 @@ __device__ __forceinline__ double gmm_exp_nonpos(double x) {
 
 // log(x), x > 0 normal: x = 2^e m, m in [sqrt(1/2), sqrt(2)); log m = 2 atanh(s), s = (m - 1) / (m + 1), |s| <= 0.1716,
 // odd series to s^23 (remainder < 1e-19).
-__device__ __forceinline__ double gmm_log(double x) {
-  int e = __builtin_amdgcn_frexp_exp(x);
+// gmm_log2e(x, eadd) = log(x 2^eadd): the exponent of a product kept apart from its mantissa (gauss_update's determinant).
+__device__ __forceinline__ double gmm_log2e(double x, int eadd) {
+  int e = __builtin_amdgcn_frexp_exp(x) + eadd;
   double m = __builtin_amdgcn_frexp_mant(x);                           // [0.5, 1)
   const bool lo = m < 0.70710678118654752440;
   m = lo ? 2.0 * m : m;
@@ -151,6 +152,7 @@ __device__ __forceinline__ double gmm_log(double x) {
   return __builtin_fma(de, 6.93147180369123816490e-01,
                        __builtin_fma(2.0, s, __builtin_fma(2.0, t, de * 1.90821492927058770002e-10)));
 }
+__device__ __forceinline__ double gmm_log(double x) { return gmm_log2e(x, 0); }
 
 template <int N>
 __device__ __forceinline__ void gauss_update(PointGauss<N>& g) {
@@ -158,7 +160,11 @@ __device__ __forceinline__ void gauss_update(PointGauss<N>& g) {
   // sum_j log chol(J)_jj = 1/2 log prod_j d_j   [gaussian.py:11-25].  No square root, one reciprocal per pivot.
   double L[N][N], d[N], dinv[N];
   g.ok = true;
-  double det = 1.0;       // prod_j d_j (N <= 8 factors of O(1e-3 .. 1e3): no overflow)
+  // prod_j d_j = detm 2^dete: the product of the pivots' mantissas (each in [1/2, 1): N <= 8 factors stay normal) and
+  // the sum of their exponents -- pivots of 1e+-40 at N = 8 leave the fp64 range as a plain product.  Scaling by powers
+  // of two is exact, so wherever the plain product is a normal number this is the same logZ bit for bit.
+  double detm = 1.0;
+  int dete = 0;
 #pragma unroll
   for (int j = 0; j < N; ++j) {
     double v[N];          // v_m = L_jm d_m
@@ -171,7 +177,8 @@ __device__ __forceinline__ void gauss_update(PointGauss<N>& g) {
     g.ok = g.ok && (dj > 0.0);
     d[j] = dj;
     dinv[j] = gmm_rcp(dj);
-    det *= dj;
+    detm *= __builtin_amdgcn_frexp_mant(dj);
+    dete += __builtin_amdgcn_frexp_exp(dj);
 #pragma unroll
     for (int i = j + 1; i < N; ++i) {
       double s = -2.0 * g.A[i][j];
@@ -220,7 +227,7 @@ __device__ __forceinline__ void gauss_update(PointGauss<N>& g) {
       g.ExxT[i][j] = s;
       g.ExxT[j][i] = s;
     }
-  g.logZ = 0.5 * vv - 0.5 * gmm_log(det) + g.ab;
+  g.logZ = 0.5 * vv - 0.5 * gmm_log2e(detm, dete) + g.ab;
 }
 
 // The K global potentials as a table in LDS, staged once per launch: per state k the entries the (N+2) x (N+2)
@@ -308,14 +315,6 @@ __device__ __forceinline__ double gmm_point(const GmmArgs& a, const double* tab,
   }
   gauss_update<N>(g);
   mid();
-  if (!g.ok) {
-    int old = *(volatile int32_t*)a.info;
-    while (old == 0 || old > t + 1) {
-      const int seen = atomicCAS(a.info, old, t + 1);
-      if (seen == old) break;
-      old = seen;
-    }
-  }
   // gaussian_kl_t = <node, stats> - logZ(eta)        [gmm.py:116]
   double nodedot = 0.0;
 #pragma unroll
@@ -387,6 +386,17 @@ __device__ __forceinline__ double gmm_point(const GmmArgs& a, const double* tab,
       a.label_stats[(long)t * K + k] = rnew;
     }
     klt += lab - lse;
+  }
+  // status word: the lowest point + 1 whose factor has a non-positive pivot, or whose KL term is not finite (a NaN or
+  // infinite node potential passes every pivot test; it reaches klt through logZ or the label natural parameters,
+  // which gmm_exp_nonpos's clamp would otherwise turn into responsibilities of 0).
+  if (!g.ok || !(fabs(klt) < 1.0 / 0.0)) {
+    int old = *(volatile int32_t*)a.info;
+    while (old == 0 || old > t + 1) {
+      const int seen = atomicCAS(a.info, old, t + 1);
+      if (seen == old) break;
+      old = seen;
+    }
   }
   if (!final_pass) klt += lin;
 

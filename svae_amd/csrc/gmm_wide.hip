@@ -29,8 +29,9 @@ constexpr int WBLOCK = 256;                 // 16 points (rows) per workgroup
 constexpr int WROWS = WBLOCK / 16;
 constexpr int WMAX_K = 64;
 
-__device__ __forceinline__ double wide_log(double x) {   // log(x), x > 0 normal (the arithmetic of gmm_meanfield.hip)
-  int e = __builtin_amdgcn_frexp_exp(x);
+// log(x 2^eadd), x > 0 normal (the arithmetic of gmm_meanfield.hip's gmm_log2e)
+__device__ __forceinline__ double wide_log2e(double x, int eadd) {
+  int e = __builtin_amdgcn_frexp_exp(x) + eadd;
   double m = __builtin_amdgcn_frexp_mant(x);
   const bool lo = m < 0.70710678118654752440;
   m = lo ? 2.0 * m : m;
@@ -54,6 +55,7 @@ __device__ __forceinline__ double wide_log(double x) {   // log(x), x > 0 normal
   return __builtin_fma(de, 6.93147180369123816490e-01,
                        __builtin_fma(2.0, s, __builtin_fma(2.0, t, de * 1.90821492927058770002e-10)));
 }
+__device__ __forceinline__ double wide_log(double x) { return wide_log2e(x, 0); }
 
 // a[i] for a lane-dependent i (a select chain: the array stays in registers)
 template <int M>
@@ -215,24 +217,23 @@ __device__ __forceinline__ double wide_point(const WideArgs& a, const int t, con
   for (int c = 0; c < N; ++c) W[c] = -2.0 * A[c];
   row_factor<N, false>(i, W, X, d, Lr, Lc);
   bool ok = true;
-  double det = 1.0;
+  // prod_j d_j = detm 2^dete (mantissas in [1/2, 1), exponents summed: pivots of 1e+-20 at N = 16 leave the fp64 range
+  // as a plain product; the same bits as the plain product wherever that is a normal number)
+  double detm = 1.0;
+  int dete = 0;
 #pragma unroll
-  for (int j = 0; j < N; ++j) { ok = ok && (d[j] > 0.0); det *= d[j]; }
+  for (int j = 0; j < N; ++j) {
+    ok = ok && (d[j] > 0.0);
+    detm *= __builtin_amdgcn_frexp_mant(d[j]);
+    dete += __builtin_amdgcn_frexp_exp(d[j]);
+  }
   const double mu = row_matvec<N>(X, h);
   double E[N];                                   // row i of E[x x'] = Sigma + mu mu'
   static_for<0, N>([&](auto C_) {
     constexpr int c = decltype(C_)::value;
     E[c] = __builtin_fma(mu, bcast<c>(mu), X[c]);
   });
-  const double logZ = 0.5 * row_sum16(h * mu) - 0.5 * wide_log(det) + (cN + dN);
-  if (!ok && i == 0) {
-    int old = *(volatile int32_t*)a.info;
-    while (old == 0 || old > t + 1) {
-      const int seen = atomicCAS(a.info, old, t + 1);
-      if (seen == old) break;
-      old = seen;
-    }
-  }
+  const double logZ = 0.5 * row_sum16(h * mu) - 0.5 * wide_log2e(detm, dete) + (cN + dN);
   double klt = row_sum16(act ? __builtin_fma(nJ, pick(E, i), nh * mu) : 0.0) - logZ;   // <node, s> - logZ [gmm.py:116]
   // ---- label update [gmm.py:119-124]: lane (k mod 16) keeps l_k in slot k / 16
   double lsl[4] = {0.0, 0.0, 0.0, 0.0};
@@ -295,6 +296,15 @@ __device__ __forceinline__ double wide_point(const WideArgs& a, const int t, con
     if (ov > bestv || (ov == bestv && ob < best)) { bestv = ov; best = ob; }
   }
   klt += row_sum16(labp) - lse;
+  // status word, as gmm_point's: a non-positive pivot, or a KL term that is not finite (NaN / infinite node potentials)
+  if ((!ok || !(fabs(klt) < 1.0 / 0.0)) && i == 0) {
+    int old = *(volatile int32_t*)a.info;
+    while (old == 0 || old > t + 1) {
+      const int seen = atomicCAS(a.info, old, t + 1);
+      if (seen == old) break;
+      old = seen;
+    }
+  }
   if (!final_pass) klt += row_sum16(linp);
   if (final_pass) {
     if (i == 0) a.assign[t] = best;

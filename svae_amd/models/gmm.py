@@ -209,7 +209,7 @@ def check_info(info=None):
                            "the grid of the persistent kernel was not co-resident" % v)
     if v != 0:
         raise FloatingPointError("GMM mean field: point %d has a non positive definite "
-                                 "Gaussian factor" % (v - 1))
+                                 "Gaussian factor or non-finite potentials" % (v - 1))
 
 
 def global_step(global_natparam, prior_natparam=None, info=None, reference_compat=True):
