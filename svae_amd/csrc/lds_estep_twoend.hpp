@@ -55,6 +55,8 @@ __device__ __forceinline__ double asm_max(double a, double b) {        // fmax a
   return r;
 }
 
+__device__ __forceinline__ void pin(double& x) { asm volatile("" : "+v"(x)); }   // x is computed BEFORE the volatile statements that follow
+
 // ---- in-place Gauss-Jordan on one register per row --------------------------------------------------
 // M[i]: lanes < N = row i of P (SPD), other lanes = right-hand-side columns.  On exit lanes < N hold
 // the inverse in "unscaled column" form (true inverse = M[i][c] * v[c], v[c] = -1/p_c accumulated in
@@ -124,6 +126,13 @@ __device__ __forceinline__ void te_gauss_jordan(double (&M)[N], const double (&E
 #endif
 }
 
+// The elimination step as ONE generated statement per stage (gj1r_gen.hpp: te_condition_asm, gauss_jordan_1r_asm_from,
+// te_schur_asm): same operations in the same order per element as the statement-by-statement form, which stays for MIX
+// (its stages are interleaved with the table mixing) and for the A/B builds without the fused DPP forms.
+#ifndef SVAE_TE_STAGE_ASM
+#define SVAE_TE_STAGE_ASM (SVAE_GJ_GENERATED && SVAE_FUSED_DPP && !SVAE_DPP_ALWAYS_FENCED)
+#endif
+
 #ifdef SVAE_PHASE_TIMING
 #define TE_TICK(i) { const long long now_ = __builtin_readcyclecounter(); tm[i] += now_ - tlast_; tlast_ = now_; }
 #else
@@ -185,6 +194,7 @@ __device__ __forceinline__ void lds_estep_twoend_body(const LdsArgs& a, const in
   constexpr int J1 = (N + 2) / 2;         // slots holding rows 0..N
   constexpr int HL = 15;                  // lane of the h column
   constexpr int RSL = (N + 3) & ~1;       // LDS row stride of the transposition tile (even, >= N + 1)
+  constexpr bool TE_STAGE_ASM = !MIX && (SVAE_TE_STAGE_ASM);   // the elimination step's stages as one statement each
   __shared__ double tab_static[MIX ? 2 : (S4 ? 4 : 2) * 16 * 16];   // [chain][row 0..15][RSL]: G~ rows for the transposed read (S4: + the gather tiles)
   __shared__ double xch_static[S4 ? 2 * ((N + 3) / 4) * 64 + 256 : 2];   // S4: chain B's sums on their way to chain A
   extern __shared__ double2 te_dyn[];     // MIX: the parameter tables (te_mix_lds_bytes)
@@ -424,8 +434,6 @@ __device__ __forceinline__ void lds_estep_twoend_body(const LdsArgs& a, const in
   }
 
   // node potentials of local step s: global node t = s (A) / T-1-s (B); lanes >= N read element 0
-  const double* nJb = a.node_J + ((long)b * T) * N + cc;
-  const double* nhb = a.node_h + ((long)b * T) * N + cc;
   auto node_off = [&](int s) -> long { return (long)(dir ? T - 1 - s : s) * N; };
 
   // chain workspace: constant page [e_N (N+2) | zeros (N+2) | trash (2)], then the records
@@ -471,11 +479,19 @@ __device__ __forceinline__ void lds_estep_twoend_body(const LdsArgs& a, const in
   // stores; loading by inline asm with a hand-placed s_waitcnt vmcnt(N) was tried and is NOT safe: the
   // compiler may copy the destination register before the wait.)
   // (walking per-lane pointers: recomputing node_off(s + 1) per step was two 64-bit multiply-adds and three selects)
-  const double* pJn = nJb + node_off(0);
-  const double* phn = nhb + node_off(0);
-  const long nstep = dir ? -(long)N : (long)N;
-  double Jo_n = *pJn;
-  double ho_n = *phn;
+  // (... and the pointers five 64-bit adds per step: the sequence's base is uniform, so the walk is ONE 32-bit add of
+  //  the lane's byte offset -- kept out of hipcc's sight by an empty asm like the hand-off's, see hand_off below)
+  const char* const nJu = reinterpret_cast<const char*>(a.node_J + (long)b * T * N);
+  const char* const nhu = reinterpret_cast<const char*>(a.node_h + (long)b * T * N);
+  unsigned noff = 8u * (unsigned)(node_off(0) + cc);
+  const unsigned nstep = dir ? 0u - 8u * N : 8u * N;
+  auto node_load = [&](double& Jo, double& ho) {
+    asm volatile("" : "+v"(noff));
+    Jo = *reinterpret_cast<const double*>(nJu + noff);
+    ho = *reinterpret_cast<const double*>(nhu + noff);
+  };
+  double Jo_n, ho_n;
+  node_load(Jo_n, ho_n);
   const double jm2 = col ? -2.0 : 0.0, jadd = col ? 0.0 : 1.0;      // JoX = col ? -2 Jo : 1 as ONE multiply-add
   double Mp[N];             // partner chain's An at the hand-over point
   static_for<0, N>([&](auto i) { Mp[i] = 0.0; });
@@ -488,22 +504,28 @@ __device__ __forceinline__ void lds_estep_twoend_body(const LdsArgs& a, const in
     qacc_s = qacc; ldM_s = ldM; ldE_s = ldE;
   };
   const int s0 = e + 1 - keep;              // S4: records of local steps >= s0 go to LDS
-  auto hand_off = [&](int s, const double (&M)[N], double vfull, auto to_lds) {
+  // (R[i] = M[i] * vfull, the record's rows with their columns scaled)
+  auto hand_off_rows = [&](int s, const double (&R)[N], auto to_lds) {
     if constexpr (S4 && decltype(to_lds)::value) {
       char* w = reinterpret_cast<char*>(lrecs + (long)(s - s0) * WS);
-      static_for<0, N>([&](auto i) { *reinterpret_cast<double*>(w + lloff[i]) = M[i] * vfull; });
+      static_for<0, N>([&](auto i) { *reinterpret_cast<double*>(w + lloff[i]) = R[i]; });
     } else if constexpr (LEAN) {
       char* w = reinterpret_cast<char*>(wsb + (long)s * WS);     // uniform base + 32-bit lane offset
       // (the offset passes through an empty asm: hipcc otherwise hoists its zero-extension out of the loop and pays
       //  a 64-bit add per store instead of the SGPR-base + 32-bit-offset addressing mode)
       static_for<0, N>([&](auto i) {
         asm volatile("" : "+v"(loff[i]));
-        *reinterpret_cast<double*>(w + loff[i]) = M[i] * vfull;
+        *reinterpret_cast<double*>(w + loff[i]) = R[i];
       });
     } else {
       double* w = rec0 + (long)s * WS + stoff;
-      static_for<0, N>([&](auto i) { w[i * RW] = M[i] * vfull; });
+      static_for<0, N>([&](auto i) { w[i * RW] = R[i]; });
     }
+  };
+  auto hand_off = [&](int s, const double (&M)[N], double vfull, auto to_lds) {
+    double R[N];
+    static_for<0, N>([&](auto i) { R[i] = M[i] * vfull; });
+    hand_off_rows(s, R, to_lds);
   };
 
   // hipcc merges the memory-counter state of the loop entry with the back edge's and waits for the more
@@ -521,9 +543,8 @@ __device__ __forceinline__ void lds_estep_twoend_body(const LdsArgs& a, const in
     if (s == jx) take_partner();
     const double JoX = __builtin_fma(Jo_n, jm2, jadd);
     double ho = ho_n;
-    pJn += nstep; phn += nstep;            // node s + 1 <= e: the meeting node's potentials included
-    Jo_n = *pJn;
-    ho_n = *phn;
+    noff += nstep;                         // node s + 1 <= e: the meeting node's potentials included
+    node_load(Jo_n, ho_n);
     if constexpr (RING) ring_pair(s & 1, true);
     else if (INHOMOG && !MIX) load_pair(s, true);
     double wq[2] = {wr0 * wmask, wr1 * wmask};     // MIX: lane k = weight of state k (pair s, pair s + 1)
@@ -535,13 +556,18 @@ __device__ __forceinline__ void lds_estep_twoend_body(const LdsArgs& a, const in
 
     // condition on the node potential; right-hand sides ride in the upper lanes
     double M[N], Bt[N];
+    // (An arrives from the split tile: ONE wait for the batch of reads -- they return in order -- instead of one per
+    //  read in front of its first use)
+    if constexpr (TE_LDS_SPLIT<MIX, CROSS>()) touch(An[N - 1]);
     if constexpr (MIX) {
       static_for<0, N>([&](auto i) { M[i] = __builtin_fma(JoX, E[i], An[i]); });
     } else {
       static_for<0, N>([&](auto i) { M[i] = __builtin_fma(JoX, EX[i], An[i]); });
     }
     dpp_fence(ho);
-    static_for<0, N>([&](auto i) { mac_bc<i>(M[i], ho, EH); });      // lane 15: h_filt = h_pred + h_node
+    [[maybe_unused]] double p0 = 0.0, rinv0 = 0.0;                   // first pivot and its reciprocal
+    if constexpr (TE_STAGE_ASM) te_condition_asm<N>(M, ho, EH, p0, rinv0);
+    else static_for<0, N>([&](auto i) { mac_bc<i>(M[i], ho, EH); });      // lane 15: h_filt = h_pred + h_node
     // B operand of the Schur stage: lanes < N: -J12'[k][c]; lane 15: -h_filt,k
     if constexpr (MIX) {
       // mixed J12' of this pair, once, for both of its uses (disjoint lanes; zero in lane 15: h_filt is left alone)
@@ -560,11 +586,12 @@ __device__ __forceinline__ void lds_estep_twoend_body(const LdsArgs& a, const in
     } else {
       static_for<0, N>([&](auto k) { Bt[k] = __builtin_fma(-EH, M[k], NJ12c[k]); });
     }
-    dpp_fence(M);
+    if constexpr (!TE_STAGE_ASM) dpp_fence(M);       // (the statement above wrote M: its first DPP read is pivots away)
     TE_TICK(0)
 
     double vfull = col ? 0.0 : 1.0;
-    te_gauss_jordan<N>(M, E, qacc, vfull);
+    if constexpr (TE_STAGE_ASM) gauss_jordan_1r_asm_from<N>(M, E, qacc, vfull, p0, rinv0);
+    else te_gauss_jordan<N>(M, E, qacc, vfull);
     TE_TICK(1)
 
     // next pivot block, slot layout:  AnD[j] = Cc[j] + sum_k X[k][i] * Bt[k]   (row i = 2j + gl;
@@ -577,10 +604,14 @@ __device__ __forceinline__ void lds_estep_twoend_body(const LdsArgs& a, const in
     } else {
       static_for<0, J>([&](auto j) { AnD[j] = Cc[j]; });
     }
-    asm volatile("s_nop 1");
-    static_for<0, N>([&](auto k) {
-      static_for<0, J>([&](auto j) { mac_bc<N + j>(AnD[j], M[k], Bt[k]); });
-    });
+    if constexpr (TE_STAGE_ASM) {
+      te_schur_asm<N>(AnD, M, Bt);
+    } else {
+      asm volatile("s_nop 1");
+      static_for<0, N>([&](auto k) {
+        static_for<0, J>([&](auto j) { mac_bc<N + j>(AnD[j], M[k], Bt[k]); });
+      });
+    }
     TE_TICK(2)
 
     // The next pivot block leaves the Schur stage in slot layout (row 2j + gl in DPP row gl of the chain's pair) and
@@ -605,13 +636,22 @@ __device__ __forceinline__ void lds_estep_twoend_body(const LdsArgs& a, const in
       ldE += __builtin_amdgcn_frexp_exp(ldM);
       ldM = __builtin_amdgcn_frexp_mant(ldM);
     }
-    hand_off(s, M, vfull, to_lds);
-
     if constexpr (TE_LDS_SPLIT<MIX, CROSS>()) {
+      // The record's rows are scaled FIRST (M is dead from here: the reads below land in its registers), the split
+      // tile is read back NEXT, and only then do the stores go out: the reads' round trip runs under the stores, the
+      // loop's bookkeeping and the head of the next step instead of standing, exposed, in front of its first
+      // multiply-add.  (The empty statements pin that order: a load may not cross a "memory" clobber.)
+      double R[N];
+      static_for<0, N>([&](auto i) { R[i] = M[i] * vfull; });
+      static_for<0, N>([&](auto i) { pin(R[i]); });
+      asm volatile("" : : : "memory");
       const double* sp = split_tile + dir * (N + 1) * 16 + c;
       static_for<0, N>([&](auto i) { An[i] = sp[i * 16]; });
+      asm volatile("" : : : "memory");
+      hand_off_rows(s, R, to_lds);
       __builtin_amdgcn_wave_barrier();
     } else {
+      hand_off(s, M, vfull, to_lds);
       dpp_fence(AnD);
       static_for<0, J>([&](auto j) {
         if constexpr (2 * j + 1 < N) pair_split(AnD[j], An[2 * j], An[2 * j + 1]);

@@ -154,6 +154,150 @@ def emit2(N):
     return "\n".join(out)
 
 
+# ---- the elimination step of the two-ended kernel as three blocks (lds_estep_twoend.hpp: elim_step) ----------------
+# hipcc pads between separate inline-asm statements that share a register (an s_nop after every second multiply-add
+# of a product stage, one between two pivot blocks) and cannot start the first pivot's reciprocal before the
+# statements in front of it are through.  One statement per stage leaves it nothing to pad; the wait states a
+# DPP / trans hazard does need are counted here (tools/audit_dpp_hazards.py checks the result).
+
+def condition_block(N):
+    """Adds the node's potential vector to lane 15 of every row (M[i] += bcast_i(ho) * EH, as mac_bc<i>) and starts the
+    Gauss-Jordan's FIRST pivot on the way: p = M[0][0] is final after the first of these multiply-adds, so its
+    broadcast and the reciprocal chain (the arithmetic of rcp_nr, dpp.hpp) ride between the others instead of standing
+    alone, serial, in front of the first pivot block."""
+    mac = lambda i: "v_fmac_f64_dpp %[m{i}], %[ho], %[eh] row_newbcast:{i} {d}".format(i=i, d=DPP)
+    fill = [mac(i) for i in range(1, N)]
+    L = [mac(0)]
+
+    def wait(states):            # `states` wait states from other work, s_nop for what is missing
+        got = 0
+        while got < states and fill:
+            L.append(fill.pop(0))
+            got += 1
+        if got < states:
+            L.append("s_nop %d" % (states - got - 1))
+
+    wait(2)                                                                 # VALU write of m0 -> DPP read
+    L.append("v_mov_b64_dpp %[p], %[m0] row_newbcast:0 {d}".format(d=DPP))
+    L.append("v_rcp_f64 %[t0], %[p]")
+    wait(1)                                                                 # trans result -> VALU use
+    for _ in range(2):                                                      # (its latency is about two FMAs')
+        if fill:
+            L.append(fill.pop(0))
+    L.append("v_fma_f64 %[e0], -%[p], %[t0], 1.0")
+    if fill:
+        L.append(fill.pop(0))
+    L.append("v_fma_f64 %[e0], %[e0], %[e0], %[e0]")
+    if fill:
+        L.append(fill.pop(0))
+    L.append("v_fma_f64 %[ri], %[t0], %[e0], %[t0]")
+    return L + fill
+
+
+def emit_condition(N):
+    out = ["template <>",
+           "__device__ __forceinline__ void te_condition_asm<%d>(double (&M)[%d], double ho, double EH, double& p, "
+           "double& rinv) {" % (N, N),
+           "  double t0, e0;"]
+    body = "\\n\\t\"\n      \"".join(condition_block(N))
+    outs = ", ".join('[m%d] "+v"(M[%d])' % (i, i) for i in range(N))
+    outs += ', [p] "=&v"(p), [ri] "=&v"(rinv), [t0] "=&v"(t0), [e0] "=&v"(e0)'
+    out.append("  asm volatile(\n      \"%s\"\n      : %s\n      : [ho] \"v\"(ho), [eh] \"v\"(EH));" % (body, outs))
+    out.append("}")
+    return "\n".join(out)
+
+
+def emit_from_pivot(N):
+    """gauss_jordan_1r_asm with the first pivot and its reciprocal handed in, every pivot in ONE statement.  The
+    arithmetic per element is pivot_block()'s; with the blocks in one statement their instructions can be placed for
+    latency across the block boundary:
+      * the head of block k + 1 -- its scaled pivot row ru = (M[k+1] - p e) * (1/p), two dependent instructions every
+        row update of that block waits for -- is issued inside block k (row k + 1 is final after the block's first
+        update, p after the broadcast, 1/p after the chain); the pivot row alternates between two registers, like
+        the (pivot, reciprocal) pair;
+      * v_rcp_f64 has about twice the latency of an FMA: three instructions stand between it and its first use, one
+        between the dependent FMAs behind it."""
+    sets = [("%[p]", "%[ri]"), ("%[pa]", "%[ra]"), ("%[pb]", "%[rb]")]
+    rus = ["%[ru]", "%[rv]"]
+    lines = []
+    for k in range(N):
+        p, ri = sets[0] if k == 0 else sets[1 + (k - 1) % 2]
+        pn, rn = sets[1 + k % 2]
+        ru, run = rus[k % 2], rus[(k + 1) % 2]
+        e, en, mk = "%%[u%d]" % k, "%%[u%d]" % (k + 1), "%%[m%d]" % k
+        upd = lambda i: "v_fmac_f64_dpp %[m{i}], %[m{i}], -{ru} row_newbcast:{k} {d}".format(i=i, ru=ru, k=k, d=DPP)
+        L = []
+        if k == 0:
+            L.append("v_fma_f64 %s, -%s, %s, %s" % (ru, p, e, mk))         # lane k -> exactly 0
+            L.append("v_mul_f64 %s, %s, %s" % (ru, ru, ri))                 # scaled pivot row
+        L.append("v_fma_f64 %[q], {m}, {ru}, %[q]".format(m=mk, ru=ru))
+        L.append("v_fma_f64 %[vf], -{ri}, {e}, %[vf]".format(ri=ri, e=e))
+        if k + 1 < N:
+            others = [upd(i) for i in list(range(k + 2, N)) + list(range(0, k))]
+            take = lambda n: [others.pop(0) for _ in range(min(n, len(others)))]
+            L.append(upd(k + 1))
+            pre = take(2)
+            L += pre
+            if len(pre) < 2:
+                L.append("s_nop %d" % (1 - len(pre)))                       # VALU write -> DPP read: 2 wait states
+            L.append("v_mov_b64_dpp {pn}, %[m{i}] row_newbcast:{i} {d}".format(pn=pn, i=k + 1, d=DPP))
+            L.append("v_rcp_f64 %[t0], " + pn)
+            L += take(2)
+            L.append("v_fma_f64 %s, -%s, %s, %%[m%d]" % (run, pn, en, k + 1))   # next block's head (also the trans wait state)
+            L.append("v_fma_f64 %[e0], -" + pn + ", %[t0], 1.0")
+            L += take(1)
+            L.append("v_fma_f64 %[e0], %[e0], %[e0], %[e0]")
+            L += take(1)
+            L.append("v_fma_f64 " + rn + ", %[t0], %[e0], %[t0]")
+            L += take(1)
+            L.append("v_mul_f64 %s, %s, %s" % (run, run, rn))
+            L += others
+        else:
+            L += [upd(i) for i in range(0, N - 1)]
+        L.append("v_add_f64 %s, %s, -%s" % (mk, ru, e))                     # pivot row as kept: lane k = -1
+        lines += L
+    out = ["template <>",
+           "__device__ __forceinline__ void gauss_jordan_1r_asm_from<%d>(double (&M)[%d], const double (&E)[%d], "
+           "double& qacc, double& vfull, double p, double rinv) {" % (N, N, N),
+           "  double ru, rv, t0, e0, pa, ra, pb, rb;",
+           "  (void)rv; (void)t0; (void)e0; (void)pa; (void)ra; (void)pb; (void)rb;"]
+    body = "\\n\\t\"\n      \"".join(lines)
+    outs = ", ".join('[m%d] "+v"(M[%d])' % (i, i) for i in range(N))
+    outs += ', [q] "+v"(qacc), [vf] "+v"(vfull), [ru] "=&v"(ru)'
+    if N > 1:
+        outs += ', [rv] "=&v"(rv), [t0] "=&v"(t0), [e0] "=&v"(e0), [pa] "=&v"(pa), [ra] "=&v"(ra)'
+    if N > 2:
+        outs += ', [pb] "=&v"(pb), [rb] "=&v"(rb)'
+    ins = ", ".join('[u%d] "v"(E[%d])' % (k, k) for k in range(N)) + ', [p] "v"(p), [ri] "v"(rinv)'
+    out.append("  asm volatile(\n      \"%s\"\n      : %s\n      : %s);" % (body, outs, ins))
+    out.append("}")
+    return "\n".join(out)
+
+
+def emit_schur(N):
+    """The Schur stage  AnD[j] += bcast_{N+j}(M[k]) * Bt[k]  (k outer, j inner: the order of the mac_bc statements it
+    replaces) as one statement.  M[k] is the DPP operand: the Gauss-Jordan's last block writes M[0] .. M[N-2] in this
+    order and M[N-1] last of all, so only N <= 2 needs wait states in front (an instruction between the two
+    statements only adds to them)."""
+    J = (N + 1) // 2
+    L = []
+    if N <= 2:
+        L.append("s_nop %d" % (2 - N))
+    for k in range(N):
+        for j in range(J):
+            L.append("v_fmac_f64_dpp %[a{j}], %[m{k}], %[b{k}] row_newbcast:{l} {d}".format(j=j, k=k, l=N + j, d=DPP))
+    out = ["template <>",
+           "__device__ __forceinline__ void te_schur_asm<%d>(double (&AnD)[%d], const double (&M)[%d], "
+           "const double (&Bt)[%d]) {" % (N, J, N, N)]
+    body = "\\n\\t\"\n      \"".join(L)
+    outs = ", ".join('[a%d] "+v"(AnD[%d])' % (j, j) for j in range(J))
+    ins = ", ".join('[m%d] "v"(M[%d])' % (k, k) for k in range(N)) + ", " + \
+        ", ".join('[b%d] "v"(Bt[%d])' % (k, k) for k in range(N))
+    out.append("  asm volatile(\n      \"%s\"\n      : %s\n      : %s);" % (body, outs, ins))
+    out.append("}")
+    return "\n".join(out)
+
+
 HEADER = '''// gj1r_gen.hpp -- GENERATED by tools/gen_gj_asm.py; do not edit.
 // In-place Gauss-Jordan on one register per row (see gauss_jordan_1r in lds_estep_twoend.hpp for the
 // algorithm and the meaning of the operands), one hand-scheduled inline-asm block per pivot.
@@ -173,6 +317,15 @@ __device__ __forceinline__ void gauss_jordan_1r_asm_rows(double (&M)[N], const d
 template <int N>
 __device__ __forceinline__ void gauss_jordan_2r_asm(double (&A)[N], double (&B)[N], const double (&E)[N], double& qacc,
                                                     double& vfull);
+// the elimination step of the two-ended kernel, one statement per stage: the node potential's conditioning with the
+// first pivot's reciprocal started inside it, the Gauss-Jordan from that pivot on, the Schur stage
+template <int N>
+__device__ __forceinline__ void te_condition_asm(double (&M)[N], double ho, double EH, double& p, double& rinv);
+template <int N>
+__device__ __forceinline__ void gauss_jordan_1r_asm_from(double (&M)[N], const double (&E)[N], double& qacc,
+                                                         double& vfull, double p, double rinv);
+template <int N>
+__device__ __forceinline__ void te_schur_asm(double (&AnD)[(N + 1) / 2], const double (&M)[N], const double (&Bt)[N]);
 
 '''
 
@@ -183,6 +336,9 @@ def generate():
         parts.append(emit(N) + "\n\n")
         parts.append(emit(N, rows=True) + "\n\n")
         parts.append(emit2(N) + "\n\n")
+        parts.append(emit_condition(N) + "\n\n")
+        parts.append(emit_from_pivot(N) + "\n\n")
+        parts.append(emit_schur(N) + "\n\n")
     parts.append("}  // namespace svae\n")
     return "".join(parts)
 
