@@ -186,6 +186,9 @@ __device__ __forceinline__ void lds_estep_twoend_body(const LdsArgs& a, const in
   // (CROSS runs next to the one-directional filter: one wavefront per SIMD, see lds_estep_split.hpp)
   // (S4: 2 B wavefronts on 1024 SIMDs -- without the marker two of them may share a SIMD: 180 us instead of 152)
   if constexpr (CROSS || S4) asm volatile("v_accvgpr_write_b32 a63, 0" ::: "a63");
+#ifdef SVAE_PHASE_TIMING
+  const long long tbegin_ = __builtin_readcyclecounter();
+#endif
   constexpr int RW = te_row_doubles(N), ZP = te_page_doubles(N);
   constexpr int WS = LEAN ? te_lean_step_doubles(N) : te_step_doubles(N);
   constexpr int TRI = N * (N + 1) / 2;    // LEAN record: [lower triangle | c (N) | 0.0 | trash | pad]
@@ -226,10 +229,25 @@ __device__ __forceinline__ void lds_estep_twoend_body(const LdsArgs& a, const in
     const int e_ = te_elims(a.T);
     keep = a.lds_keep < e_ + 1 ? a.lds_keep : e_ + 1;
     if (keep < 3) keep = 0;
-    if (wv == 1) {                        // chain B's smoother wavefront: sleeps until the records are complete
-      __syncthreads();
-      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-      te_smooth4<N>(a, b, 1, lane, tab_static + 256, tab_static + 768, xch_static, lrecs, keep);
+    if (wv == 1) {
+      // chain B's smoother wavefront: sets up everything that reads no record, then sleeps until the records are complete
+#ifdef SVAE_PHASE_TIMING
+      long long tm1[16] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+      long long tl1 = __builtin_readcyclecounter();
+      [[maybe_unused]] long long* const ptm = tm1;         // (S4_TICK's names)
+      [[maybe_unused]] long long* const ptlast = &tl1;
+#endif
+      te_smooth4<N>(a, b, 1, lane, tab_static + 256, tab_static + 768, xch_static, lrecs, keep,
+                    [&]() {
+                      __syncthreads();
+                      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+                      S4_TICK(10)
+                    },
+                    []() {}
+#ifdef SVAE_PHASE_TIMING
+                    , tm1, &tl1
+#endif
+      );
       return;
     }
   }
@@ -508,7 +526,10 @@ __device__ __forceinline__ void lds_estep_twoend_body(const LdsArgs& a, const in
   auto hand_off_rows = [&](int s, const double (&R)[N], auto to_lds) {
     if constexpr (S4 && decltype(to_lds)::value) {
       char* w = reinterpret_cast<char*>(lrecs + (long)(s - s0) * WS);
-      static_for<0, N>([&](auto i) { *reinterpret_cast<double*>(w + lloff[i]) = R[i]; });
+      // (a pointer QUALIFIED as LDS: hipcc merges the meeting record's two hand-off branches into one flat store otherwise,
+      //  and a pending flat access makes it wait for vmcnt(0) at the head of the smoother loop on every trip)
+      typedef __attribute__((address_space(3))) double ldouble;
+      static_for<0, N>([&](auto i) { *(ldouble*)(w + lloff[i]) = R[i]; });
     } else if constexpr (LEAN) {
       char* w = reinterpret_cast<char*>(wsb + (long)s * WS);     // uniform base + 32-bit lane offset
       // (the offset passes through an empty asm: hipcc otherwise hoists its zero-extension out of the loop and pays
@@ -534,8 +555,11 @@ __device__ __forceinline__ void lds_estep_twoend_body(const LdsArgs& a, const in
   // potentials -- instead of a wait for the previous step's hand-off stores.
   hand_off(e, An, 1.0, std::false_type{});
 #ifdef SVAE_PHASE_TIMING
-  long long tm[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+  long long tm[16] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
   long long tlast_ = __builtin_readcyclecounter();
+  tm[11] = tlast_ - tbegin_;               // the kernel's prologue
+  [[maybe_unused]] long long* const ptm = tm;
+  [[maybe_unused]] long long* const ptlast = &tlast_;
 #endif
   // MIX: weights of local pairs s and s + 1 (raw, fetched one step ahead like the node potentials)
   double wr0 = MIX ? wrow[(long)wnode(0) * K] : 0.0, wr1 = MIX ? wrow[(long)wnode(1) * K] : 0.0;
@@ -679,7 +703,7 @@ __device__ __forceinline__ void lds_estep_twoend_body(const LdsArgs& a, const in
   // P_m = An_own + An_partner - (J22' + J11') + node.  No pair potential ahead: the right-hand sides are
   // h alone (G = 0), and the record is the smoother's starting point (c = mu_m, P^-1 = Sigma_m).
   double qacc_m = 0.0, vfull_m = col ? 0.0 : 1.0;
-  {
+  auto meeting_node = [&]() {
     const long o = pair_off(e - 1), o1 = pair_off(e);
     const double JoX = col ? -2.0 * Jo_n : 1.0;
     double ho = ho_n;
@@ -720,20 +744,26 @@ __device__ __forceinline__ void lds_estep_twoend_body(const LdsArgs& a, const in
     te_gauss_jordan<N>(M, E, qacc_m, vfull_m);
     if (S4 && keep > 0) hand_off(e, M, vfull_m, std::true_type{});
     else hand_off(e, M, vfull_m, std::false_type{});
-  }
+  };
 
   // ---- log-normaliser --------------------------------------------------------------------------------
-  {
+  auto log_normaliser = [&]() {
     // per chain: 1/2 sum h'P^-1h - 1/2 sum log p = 1/2 [ q + sum_c log|prod_t (-1/p_c)| ]
+    // (q enters the row sum in lane N, where the row-per-chain kernels keep their h column, not in lane HL = 15: the
+    //  sum is a butterfly, and with q in lane 15 it groups the terms differently at N = 3, 5, 6, 7 -- at N = 5,
+    //  ((l0 + l1) + (l2 + l3) + l4) + q against ((l0 + l1) + (l2 + l3)) + (l4 + q) -- which left the two kernels' log-normalisers apart in their last bits there)
+    auto h_to_lane_n = [&](double q) { return bcast_fenced<HL>(q); };
     auto chain_part = [&](double q, double m, int ee) {
       const int ex = __builtin_amdgcn_frexp_exp(m);
       const double mant = __builtin_amdgcn_frexp_mant(m);
       double part = col ? (::log(fabs(mant)) + (double)(ee + ex) * 0.6931471805599453094) : 0.0;
-      if (c == HL) part = q;
+      const double qh = h_to_lane_n(q);
+      if (c == N) part = qh;
       return 0.5 * row_sum16(part);
     };
     double pm = col ? ::log(fabs(vfull_m)) : 0.0;
-    if (c == HL) pm = qacc_m;
+    const double qm = h_to_lane_n(qacc_m);
+    if (c == N) pm = qm;
     const double meet_total = 0.5 * row_sum16(pm);
     // all of this chain's eliminations + the partner's up to its hand-over + this chain's meeting node
     const double chain_total = chain_part(qacc, ldM, ldE) + __shfl_xor(chain_part(qacc_s, ldM_s, ldE_s), 32);
@@ -748,25 +778,50 @@ __device__ __forceinline__ void lds_estep_twoend_body(const LdsArgs& a, const in
     // (MIX: the mixed log-normaliser constants sum_k w_k logZ_k are the caller's, a (B,T,K) x (K) product)
     double total = row_sum16(z) + chain_total + meet_total + ((MIX || RING) ? 0.0 : a.init_logZ[0]);
     if (!INHOMOG) total += (double)(T - 1) * a.logZ_pair[0];
-    if (lane == 0) a.lognorm[b] = total;
+    // (both through pointers QUALIFIED as global memory: as flat accesses -- what hipcc makes of them here -- they leave
+    //  its wait-count bookkeeping with "may return out of order" until the next full wait, and S4's smoother loop, which
+    //  now follows with its ring loads in flight, would wait for vmcnt(0) at its head on every trip)
+    typedef __attribute__((address_space(1))) double gdouble;
+    typedef __attribute__((address_space(1))) volatile int32_t gvint32;
+    if (lane == 0) ((gdouble*)a.lognorm)[b] = total;
     const bool lane_bad = col && (!(vworst < 0.0) || !(vfull_m < 0.0));
     const bool bad = __ballot(lane_bad) != 0 || !(total == total);
     if (bad && lane == 0) {   // rare path: keep the smallest failing index (+1); 0 = ok
-      int old = *(volatile int32_t*)a.info;
+      int old = *(gvint32*)a.info;
       while (old == 0 || old > b + 1) {
         const int seen = atomicCAS(a.info, old, b + 1);
         if (seen == old) break;
         old = seen;
       }
     }
-  }
-  TE_TICK(4)
+  };
   if constexpr (S4) {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-    __syncthreads();
-    te_smooth4<N>(a, b, 0, lane, tab_static, tab_static + 512, xch_static, lrecs, keep);
+    // The smoother's set-up that reads no record (its constants, the loads of J12' in its orientation) runs BEFORE the
+    // meeting node; the barrier that wakes chain B's wavefront stands right behind the meeting record's hand-off, and the
+    // log-normaliser -- which nobody else waits for -- follows it, behind this wavefront's first record loads.
+    TE_TICK(12)                                  // (phase indices of the S4 timing build: tools/te_phase_timing.py)
+    te_smooth4<N>(a, b, 0, lane, tab_static, tab_static + 512, xch_static, lrecs, keep,
+                  [&]() {
+                    meeting_node();
+                    TE_TICK(13)
+                    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+                    __syncthreads();
+                    TE_TICK(10)
+                  },
+                  [&]() {
+                    TE_TICK(4)
+                    log_normaliser();
+                    TE_TICK(14)
+                  }
+#ifdef SVAE_PHASE_TIMING
+                  , tm, &tlast_
+#endif
+    );
     return;
   }
+  meeting_node();
+  log_normaliser();
+  TE_TICK(4)
 
   if constexpr (TE_LDS_SPLIT<MIX, CROSS>() && !S4) {   // the transposition tiles served as the elimination phase's split tile
     __builtin_amdgcn_wave_barrier();

@@ -14,6 +14,20 @@
 // Homogeneous parameters, lean records, statistics summed over time (the headline configuration).
 #pragma once
 #include "lds_estep_kernel.hpp"
+#include "gj1r_gen.hpp"
+
+// 1: the three product stages of a step as ONE generated statement each (gj1r_gen.hpp: te_smooth_w_asm,
+// te_smooth_prep_asm, te_smooth_s_asm; tools/gen_gj_asm.py) -- same operations in the same order per element as the
+// statement-by-statement form, which stays for the A/B builds without the fused DPP forms.
+#ifndef SVAE_S4_STAGE_ASM
+#define SVAE_S4_STAGE_ASM (SVAE_FUSED_DPP && !SVAE_DPP_ALWAYS_FENCED)
+#endif
+
+#ifdef SVAE_PHASE_TIMING
+#define S4_TICK(i) { const long long now_ = __builtin_readcyclecounter(); ptm[i] += now_ - *ptlast; *ptlast = now_; }
+#else
+#define S4_TICK(i)
+#endif
 
 namespace svae {
 
@@ -61,12 +75,21 @@ __device__ __forceinline__ double reg_copy(double x) {       // a copy the compi
 // dir = the chain (0: A, forward in time; 1: B, reversed) = the wavefront's index in the workgroup.
 // tabw: 16 x RSL doubles of LDS of this wavefront, zero-initialised;  wtw: 16 x RSL more (the gather tile of the
 // software-pipelined steps, any contents);  xch: exchange buffer of the workgroup.
-// Both wavefronts of the workgroup call this function; it contains ONE __syncthreads().
+// Both wavefronts of the workgroup call this function; it contains ONE __syncthreads() of its own (at the statistics'
+// exchange) and calls `hand_over` once, which contains the workgroup's other one: everything in front of that call reads
+// no record, so chain B's wavefront has it behind it when the barrier releases, and chain A's issues its loads before
+// the meeting node.  `after_loads` runs once, behind the first record loads (in flight for an L2 round trip): chain A's
+// wavefront computes the log-normaliser there.
+// ptm / ptlast: cycle counts per phase (-DSVAE_PHASE_TIMING builds only, tools/te_phase_timing.py).
 // lrecs / keep: the last `keep` records of each chain (local steps e+1-keep .. e, the ones read first) live in LDS
 // ([chain][slot][WS] doubles, written by the elimination phase) instead of the HBM workspace; keep = 0 or >= 3.
-template <int N>
+template <int N, class HandOver, class AfterLoads>
 __device__ __forceinline__ void te_smooth4(const LdsArgs& a, const int b, const int dir, const int lane,
-                                           double* tabw, double* wtw, double* xch, const double* lrecs, const int keep) {
+                                           double* tabw, double* wtw, double* xch, const double* lrecs, const int keep,
+                                           HandOver&& hand_over, AfterLoads&& after_loads,
+                                           [[maybe_unused]] long long* ptm = nullptr,
+                                           [[maybe_unused]] long long* ptlast = nullptr) {
+  constexpr bool STAGE_ASM = SVAE_S4_STAGE_ASM;
   constexpr int ZP = te_page_doubles(N), WS = te_lean_step_doubles(N);
   constexpr int TRI = N * (N + 1) / 2, LZERO = TRI + N;
   constexpr int J = (N + 3) / 4;          // slots holding rows 0..N-1 (row i = 4j + r)
@@ -108,6 +131,8 @@ __device__ __forceinline__ void te_smooth4(const LdsArgs& a, const int b, const 
   const bool own_e = oddT && !dir;        // who reports the meeting node
 
   // node statistics: unconditional stores through per-lane walking pointers (idle lanes -> trash)
+  // (per-lane 64-bit pointers, two 64-bit adds per step: a uniform base with a 32-bit lane offset cannot reach the trash
+  //  page of the idle lanes, which lies in another allocation, and masking them off costs three scalar instructions)
   const bool dlane = col && (c & 3) == r, xlane = col && own_N;
   const long nstride = dir ? N : -N;      // towards smaller s
   double* pdg = trash;
@@ -166,12 +191,17 @@ __device__ __forceinline__ void te_smooth4(const LdsArgs& a, const int b, const 
   auto prep_products = [&](auto first, const Ops& pi, Prep& p) {          // VALU part + the tile stores
     static_for<0, J1>([&](auto j) { p.Gc[j] = (j == NS) ? __builtin_fma(EN, pi.Pi[j], CN) : EN * pi.Pi[j]; });
     if constexpr (!decltype(first)::value) {
-      double piv[J1];
-      static_for<0, J1>([&](auto j) { piv[j] = pi.Pi[j]; });
-      dpp_fence(piv);
-      static_for<0, N>([&](auto k) {
-        static_for<0, J>([&](auto j) { mac_bc<k, true>(p.Gc[j], piv[j], NJ12c[k]); });
-      });
+      if constexpr (STAGE_ASM) {
+        // (the record's registers are read in place: they were written a whole product stage ago)
+        te_smooth_prep_asm<N>(p.Gc, pi.Pi, NJ12c);
+      } else {
+        double piv[J1];
+        static_for<0, J1>([&](auto j) { piv[j] = pi.Pi[j]; });
+        dpp_fence(piv);
+        static_for<0, N>([&](auto k) {
+          static_for<0, J>([&](auto j) { mac_bc<k, true>(p.Gc[j], piv[j], NJ12c[k]); });
+        });
+      }
     }
     static_for<0, J1>([&](auto j) { p.PiZ[j] = __builtin_fma(-EN, pi.Pi[j], pi.Pi[j]); });
     __builtin_amdgcn_wave_barrier();
@@ -198,10 +228,14 @@ __device__ __forceinline__ void te_smooth4(const LdsArgs& a, const int b, const 
     // (the LAST register the operand's LDS reads fill is "used" here: one wait for the batch -- issued a whole product
     //  ago -- instead of one per 16-byte read in front of its first multiply-add: 5 issue slots per product)
     touch(p.H[N]);
-    asm volatile("s_nop 1");
-    static_for<0, N + 1>([&](auto k) {
-      static_for<0, J1>([&](auto j) { mac_bc<k, (k < N)>(W[j], S[j], p.H[k]); });
-    });
+    if constexpr (STAGE_ASM) {
+      te_smooth_w_asm<N>(W, S, p.H);       // (S~ was written by the previous step's last statement: the wait states are the generator's)
+    } else {
+      asm volatile("s_nop 1");
+      static_for<0, N + 1>([&](auto k) {
+        static_for<0, J1>([&](auto j) { mac_bc<k, (k < N)>(W[j], S[j], p.H[k]); });
+      });
+    }
     // all-gather through LDS: store [c][i], read back [c][0..N]
     __builtin_amdgcn_wave_barrier();
     static_for<0, J1>([&](auto j) { wtw[c * RSW + 4 * j + r] = W[j]; });
@@ -225,10 +259,14 @@ __device__ __forceinline__ void te_smooth4(const LdsArgs& a, const int b, const 
     prep_read(p);
     // S~_t[i] = P^-1[i] + G~[i] W~
     touch(WR[2 * ((N + 2) / 2) - 1]);
-    dpp_fence(Gc);
-    static_for<0, N + 1>([&](auto k) {
-      static_for<0, J1>([&](auto j) { mac_bc<k, (k < N)>(Sn[j], Gc[j], WR[k]); });
-    });
+    if constexpr (STAGE_ASM) {
+      te_smooth_s_asm<N>(Sn, Gc, WR);      // (G~ of this step was prepared during the previous one)
+    } else {
+      dpp_fence(Gc);
+      static_for<0, N + 1>([&](auto k) {
+        static_for<0, J1>([&](auto j) { mac_bc<k, (k < N)>(Sn[j], Gc[j], WR[k]); });
+      });
+    }
     if constexpr (KIND == 1) {
       static_for<0, J>([&](auto j) { Stop[j] = Sn[j]; });
     } else if constexpr (KIND == 2) {
@@ -251,6 +289,7 @@ __device__ __forceinline__ void te_smooth4(const LdsArgs& a, const int b, const 
   // a step whose NEXT record sits in `stage` of the HBM ring (copied out, then the stage is refilled four records on)
   auto rstep = [&](auto kind, int s, Prep& p, Ops& stage) {
     Ops nxt;
+    touch(stage.Pi[J1 - 1]);               // the stage's loads return in order: ONE wait for the three of them
     static_for<0, J1>([&](auto j) { nxt.Pi[j] = reg_copy(stage.Pi[j]); });
     load_ops(stage);
     pstep(kind, s, p, nxt);
@@ -258,17 +297,22 @@ __device__ __forceinline__ void te_smooth4(const LdsArgs& a, const int b, const 
   constexpr std::integral_constant<int, 0> GEN{};
   constexpr std::integral_constant<int, 1> FIRST{};
   constexpr std::integral_constant<int, 2> SECOND{};
+  // ---- everything above reads no record: the workgroup's barrier (records complete) goes here ---------------------
+  S4_TICK(9)
+  hand_over();
   Ops R0, R1, R2, R3;
   Prep P;
   int s;
   if (keep > 0) {
     // records e .. s0 in LDS (keep >= 3: the first two steps find their next record there), s0-1 .. 0 in the HBM ring
     if (s0 > 0) { load_ops(R0); load_ops(R1); load_ops(R2); load_ops(R3); }   // HBM records s0-1 .. s0-4: long on their way
+    after_loads();
     Ops nx;
     lds_ops(nx, e);
     prep_products(std::true_type{}, nx, P);                        // the meeting record: G = 0
     prep_read(P);
     lds_ops(nx, e - 1);
+    S4_TICK(4)
     pstep(FIRST, e, P, nx);
     lds_ops(nx, e - 2);
     pstep(SECOND, e - 1, P, nx);
@@ -284,6 +328,7 @@ __device__ __forceinline__ void te_smooth4(const LdsArgs& a, const int b, const 
     }
   } else {
     load_ops(R0); load_ops(R1); load_ops(R2); load_ops(R3);       // records e, e-1, e-2, e-3
+    after_loads();
     {
       Ops first;
       static_for<0, J1>([&](auto j) { first.Pi[j] = reg_copy(R0.Pi[j]); });
@@ -291,20 +336,24 @@ __device__ __forceinline__ void te_smooth4(const LdsArgs& a, const int b, const 
       prep_products(std::true_type{}, first, P);                   // the meeting record: G = 0
       prep_read(P);
     }
+    S4_TICK(4)
     rstep(FIRST, e, P, R1);                                        // next: record e-1
     rstep(SECOND, e - 1, P, R2);                                   // (e >= 2: T >= TE_MIN_T)
     s = e - 2;
     if (s >= 0) { rstep(GEN, s, P, R3); --s; }                     // next: e-3 (s = 0: the clamped ring re-reads record 0, unused)
   }
+  S4_TICK(5)
   for (; s >= 3; s -= 4) {             // four steps per trip, no branch inside (hipcc's wait counts stay exact)
     rstep(GEN, s, P, R0);
     rstep(GEN, s - 1, P, R1);
     rstep(GEN, s - 2, P, R2);
     rstep(GEN, s - 3, P, R3);
   }
+  S4_TICK(6)
   if (s >= 0) rstep(GEN, s, P, R0);
   if (s >= 1) rstep(GEN, s - 1, P, R1);
   if (s >= 2) rstep(GEN, s - 2, P, R2);
+  S4_TICK(7)
 
   // ---- global statistics: chain B's sums travel to chain A's wavefront through LDS ---------------------------
   // S = S~ at the chain's end node (x_0 for A, x_{T-1} for B).  sumS = sum S~(s) over the chain's counted steps,
@@ -340,6 +389,20 @@ __device__ __forceinline__ void te_smooth4(const LdsArgs& a, const int b, const 
     });
     if (col && own_N) ei[N * N + c] = S[NS];
   }
+#ifdef SVAE_PHASE_TIMING
+  // the timing build reports instead of computing: both wavefronts' phase counters overwrite the head of E_init
+  // ([wavefront][16]; chain B's travel through its transposition tile, which lies 256 doubles behind chain A's)
+  S4_TICK(8)
+  if constexpr (N * N + N >= 32) {
+    if (dir && lane == 0) { for (int q = 0; q < 16; ++q) tabw[q] = (double)ptm[q]; }
+    __syncthreads();
+    if (!dir && lane == 0) {
+      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
+      double* ei = a.E_init + (long)b * (N * N + N);
+      for (int q = 0; q < 16; ++q) { ei[q] = (double)ptm[q]; ei[16 + q] = tabw[256 + q]; }
+    }
+  }
+#endif
 }
 
 }  // namespace svae

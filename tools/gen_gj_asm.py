@@ -298,6 +298,50 @@ def emit_schur(N):
     return "\n".join(out)
 
 
+# ---- the product stages of the one-chain-per-wavefront smoother step (lds_estep_twoend_s4.hpp: pstep) ----------------
+# Four-row slot layout: row i of a tile lives in DPP row i & 3, slot i >> 2; J = (N + 3) / 4 slots hold rows 0 .. N-1,
+# J1 = (N + 4) / 4 rows 0 .. N.  As separate mac_bc statements hipcc padded one of the four unrolled steps of the
+# loop with an s_nop behind every `k` group (22 per trip at N = 10), although the DPP operand of a stage is never
+# written inside it.  Order: k outer, j inner -- the order of the statements they replace.
+
+def smoother_stage(N, kind):
+    """-> (lines, number of accumulators, number of b operands).  acc[j] += bcast_k(d[j]) * (+/-) b[k]:
+      "w":    W~ = S~ G~'        acc = W (J1),  d = S~ (J1),   b = H[0..N]  (the transposed G~; - for k < N, + for row N)
+      "prep": G~ = P^-1 NJ12c    acc = Gc (J),  d = Pi (J),    b = NJ12c[0..N-1]  (-)
+      "s":    S~ = PiZ + G~ W~   acc = PiZ (J1), d = Gc (J1),  b = WR[0..N]  (- for k < N, + for row N)
+    Wait states (VALU write of a VGPR -> DPP read of it: 2).  "prep" and "s" read registers written a whole step
+    earlier (the record; the preparation of this step, issued during the previous one).  "w" reads S~, which the "s"
+    statement of the previous step wrote LAST: slot j in the last J1 - j instructions of that statement, read here by
+    instruction j of the first group -- J1 - 1 instructions lie between the write of a slot and its read even when the
+    two statements are adjacent, so only J1 < 3 needs s_nop in front (anything between the statements adds to it)."""
+    J, J1 = (N + 3) // 4, (N + 4) // 4
+    nacc, nb = (J, N) if kind == "prep" else (J1, N + 1)
+    L = []
+    if kind == "w" and J1 < 3:
+        L.append("s_nop %d" % (2 - J1))
+    for k in range(nb):
+        sign = "-" if (kind == "prep" or k < N) else ""
+        for j in range(nacc):
+            L.append("v_fmac_f64_dpp %[a{j}], %[d{j}], {s}%[b{k}] row_newbcast:{k} {d}".format(j=j, k=k, s=sign, d=DPP))
+    return L, nacc, nb
+
+
+def emit_smoother_stage(N, kind):
+    J1 = (N + 4) // 4
+    L, nacc, nb = smoother_stage(N, kind)
+    nbdecl = {"w": N + 1, "prep": N, "s": N + 2}[kind]       # ("s": the gathered tile is read in pairs, N + 2 registers)
+    out = ["template <>",
+           "__device__ __forceinline__ void te_smooth_%s_asm<%d>(double (&A)[%d], const double (&D)[%d], "
+           "const double (&Bk)[%d]) {" % (kind, N, J1, J1, nbdecl)]
+    body = "\\n\\t\"\n      \"".join(L)
+    outs = ", ".join('[a%d] "+v"(A[%d])' % (j, j) for j in range(nacc))
+    ins = ", ".join('[d%d] "v"(D[%d])' % (j, j) for j in range(nacc)) + ", " + \
+        ", ".join('[b%d] "v"(Bk[%d])' % (k, k) for k in range(nb))
+    out.append("  asm volatile(\n      \"%s\"\n      : %s\n      : %s);" % (body, outs, ins))
+    out.append("}")
+    return "\n".join(out)
+
+
 HEADER = '''// gj1r_gen.hpp -- GENERATED by tools/gen_gj_asm.py; do not edit.
 // In-place Gauss-Jordan on one register per row (see gauss_jordan_1r in lds_estep_twoend.hpp for the
 // algorithm and the meaning of the operands), one hand-scheduled inline-asm block per pivot.
@@ -326,6 +370,20 @@ __device__ __forceinline__ void gauss_jordan_1r_asm_from(double (&M)[N], const d
                                                          double& vfull, double p, double rinv);
 template <int N>
 __device__ __forceinline__ void te_schur_asm(double (&AnD)[(N + 1) / 2], const double (&M)[N], const double (&Bt)[N]);
+// the product stages of the one-chain-per-wavefront smoother step (lds_estep_twoend_s4.hpp), four-row slot layout,
+// one statement each:  A[j] += bcast_k(D[j]) * (+/-) Bk[k],  k outer, j inner
+//   w:    W~ = S~ G~'        A = W,       D = S~,    Bk = H (G~ transposed, replicated)
+//   prep: G~ = P^-1 NJ12c    A = G~ rows, D = P^-1,  Bk = NJ12c        (rows 0 .. N-1 only)
+//   s:    S~ = PiZ + G~ W~   A = PiZ,     D = G~,    Bk = the gathered W~
+template <int N>
+__device__ __forceinline__ void te_smooth_w_asm(double (&A)[(N + 4) / 4], const double (&D)[(N + 4) / 4],
+                                                const double (&Bk)[N + 1]);
+template <int N>
+__device__ __forceinline__ void te_smooth_prep_asm(double (&A)[(N + 4) / 4], const double (&D)[(N + 4) / 4],
+                                                   const double (&Bk)[N]);
+template <int N>
+__device__ __forceinline__ void te_smooth_s_asm(double (&A)[(N + 4) / 4], const double (&D)[(N + 4) / 4],
+                                                const double (&Bk)[N + 2]);
 
 '''
 
@@ -339,6 +397,8 @@ def generate():
         parts.append(emit_condition(N) + "\n\n")
         parts.append(emit_from_pivot(N) + "\n\n")
         parts.append(emit_schur(N) + "\n\n")
+        for kind in ("w", "prep", "s"):
+            parts.append(emit_smoother_stage(N, kind) + "\n\n")
     parts.append("}  // namespace svae\n")
     return "".join(parts)
 
