@@ -712,6 +712,50 @@ int svae_hmm_perstep_estep_f64(int B, int T, int K, int pair_batched,
                                double* logZ, double* E_init, double* E_trans /* or NULL */, double* E_states,
                                int32_t* info /* NULL only if lengths is */, void* workspace, size_t ws_bytes, void* stream);
 
+/* Reverse-mode derivative of svae_hmm_perstep_estep_f64: the VJP of all four outputs (logZ, E_init, the per-step E_trans,
+ * E_states) w.r.t. all three inputs, K <= SVAE_HMM_MAX_K -- csrc/hmm_estep_perstep_vjp.hip.  Additions to ABI 15 (no new
+ * number).  Inputs, lengths and the status word as svae_hmm_perstep_estep_f64.
+ *  in : cotangents g_logZ (B), g_init (B,K), g_trans (B,T-1,K,K) PER STEP, g_states (B,T,K); each may be NULL = zero
+ *  out: PER-SEQUENCE gradients d_init (B,K), d_pair (B,T-1,K,K), d_node (B,T,K), as svae_hmm_estep_vjp_f64: a shared
+ *       parameter's gradient is their sum over b, formed by the caller.  d_pair may be NULL = not wanted (the pair
+ *       parameters need no gradient): the pass that forms it is skipped and d_init, d_node are bit for bit those of the call
+ *       with d_pair.  With g_trans == NULL no V_t is loaded.
+ *  Arithmetic, for one sequence of length L, potentials init, P_t = pair[t], node and cotangents g, u0 = g_init,
+ *  V_t = g_trans[t], W = g_states; phi(z) = u0[z_0] + sum_t V_t[z_t, z_{t+1}] + sum_t W[t, z_t]; log space throughout:
+ *    forward   la_0 = init + node_0                         r_0 = u0 + W[0]
+ *              w_t[j,k] = softmax_j(la_t[j] + P_t[j,k])     (0 where the column is all -inf)
+ *              la_{t+1}[k] = node_{t+1}[k] + lse_j(la_t[j] + P_t[j,k])
+ *              r_{t+1}[k]  = sum_j w_t[j,k] (r_t[j] + V_t[j,k]) + W[t+1,k]
+ *    end       logZ = lse_k la_{L-1};  gamma_{L-1} = exp(la_{L-1} - logZ);  E[phi] = sum_k gamma_{L-1}[k] r_{L-1}[k];
+ *              c = g - E[phi]
+ *    backward  lb_{L-1} = 0, s_{L-1} = 0;   y_{t+1} = W[t+1] + s_{t+1}
+ *              q_t[j,k] = softmax_k(P_t[j,k] + node_{t+1}[k] + lb_{t+1}[k])              (0 where the row is all -inf)
+ *              lb_t[j] = lse_k(...),   s_t[j] = sum_k q_t[j,k] (V_t[j,k] + y_{t+1}[k]),   gamma_t = exp(la_t + lb_t - logZ)
+ *              d_pair[t,j,k] = gamma_t[j] q_t[j,k] (c + r_t[j] + V_t[j,k] + y_{t+1}[k])
+ *              d_node[t,k]   = gamma_t[k] (c + r_t[k] + s_t[k]),      d_init = d_node[0]
+ *  The softmax weights are the two sweeps' own exponentials (2 K^2 exp per step, as in the E-step); r and s are bounded by
+ *  L max|cotangent| and are not scaled; a -inf potential gives exactly 0 in d_pair (the 0-weight convention keeps r and s
+ *  finite); the shift of an empty maximum is 0.  ONE route: no flags, nothing redone.  Domain: that of
+ *  svae_hmm_perstep_estep_f64; cotangents finite.
+ *  Lengths: L = lengths[b] clamped to [1, T], a length outside 1..T ORs 1 into `info` (a vector atomic); the gradients are
+ *       those of the sequence cut to L; d_node[b, L:] and d_pair[b, L-1:] are exactly +0.0; nothing at node / g_states steps
+ *       >= L or pair / g_trans steps >= L-1 is loaded (it may be NaN); no sequence sees another's length or data.
+ *  workspace: svae_hmm_perstep_estep_vjp_workspace_bytes(B,T,K) = B T 2 K doubles rounded up to 128 bytes (the records
+ *       [la_t | r_t], 2 K doubles per (sequence, step)); 0 for B <= 0, T <= 0 or K outside 1..SVAE_HMM_MAX_K.  16-byte aligned.
+ *  Returns 0, or (decided on the host before any HIP call, the first failing check)
+ *   -1 B < 0, -2 T < 1, -3 K outside 1..SVAE_HMM_MAX_K, -4 pair_batched not 0 or 1, -5 init_params NULL, -6 pair_params
+ *   NULL with T > 1, [B = 0 returns 0 here], -7 node_params NULL, -8 d_init NULL, -9 d_node NULL, -10 info NULL with
+ *   lengths given, -11 workspace NULL, -12 ws_bytes too small, -13 workspace not 16-byte aligned; -1000 launch error.
+ *  One launch, asynchronous on `stream`, no internal allocation, no host synchronisation, safe under graph capture. */
+size_t svae_hmm_perstep_estep_vjp_workspace_bytes(int B, int T, int K);
+int svae_hmm_perstep_estep_vjp_f64(int B, int T, int K, int pair_batched,
+                                   const double* init_params, const double* pair_params, const double* node_params,
+                                   const int32_t* lengths /* or NULL */,
+                                   const double* g_logZ /* (B) or NULL */, const double* g_init /* (B,K) or NULL */,
+                                   const double* g_trans /* (B,T-1,K,K) or NULL */, const double* g_states /* (B,T,K) or NULL */,
+                                   double* d_init /* (B,K) */, double* d_pair /* (B,T-1,K,K) or NULL */, double* d_node /* (B,T,K) */,
+                                   int32_t* info /* NULL only if lengths is */, void* workspace, size_t ws_bytes, void* stream);
+
 /* Viterbi decoding with PER-STEP transition potentials, K <= SVAE_HMM_MAX_K -- csrc/hmm_viterbi_perstep.hip.  Addition to
  * ABI 15 (no new number).  Inputs, lengths and the status word as svae_hmm_perstep_estep_f64; the arithmetic is that of
  * svae_hmm_viterbi_f64 with the step's own matrix, for sequence b of length L (= T without lengths):

@@ -99,6 +99,10 @@ SIGNATURES = {
     "svae_hmm_perstep_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int] * 3),
     "svae_hmm_perstep_estep_f64": (ctypes.c_int, [ctypes.c_int] * 4 + [_c_double_p] * 3 + [_c_int_p] + [_c_double_p] * 4
                                    + [_c_int_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]),
+    # ... its reverse-mode derivative (the four cotangents, lengths and d_pair may be NULL)
+    "svae_hmm_perstep_estep_vjp_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int] * 3),
+    "svae_hmm_perstep_estep_vjp_f64": (ctypes.c_int, [ctypes.c_int] * 4 + [_c_double_p] * 3 + [_c_int_p] + [_c_double_p] * 7
+                                       + [_c_int_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]),
     # ... its Viterbi decoding and posterior sampling (lengths nullable; one entry each)
     "svae_hmm_perstep_viterbi_f64": (ctypes.c_int, [ctypes.c_int] * 4 + [_c_double_p] * 3 + [_c_int_p]
                                      + [_c_int_p, _c_double_p]

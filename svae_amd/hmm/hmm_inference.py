@@ -11,6 +11,8 @@
   hmm_estep_perstep(natparam) -> hmm_estep for PER-STEP transition potentials, pair (T-1,K,K) or (B,T-1,K,K); E_trans is
                                  then per step too, (…,T-1,K,K)                (csrc/hmm_estep_perstep.hip)
   hmm_logZ_perstep(natparam), hmm_logZ_perstep_differentiable(natparam) -> its log-normaliser, with gradients to all three
+  hmm_estep_perstep_differentiable(natparam) -> hmm_estep_perstep's outputs, with gradients of all four to all three
+                                 inputs; hmm_estep_perstep_vjp is its backward pass (csrc/hmm_estep_perstep_vjp.hip)
   hmm_viterbi_perstep(natparam), hmm_sample_perstep(natparam, num_samples) -> hmm_viterbi / hmm_sample for per-step
                                  transition potentials                        (csrc/hmm_viterbi_perstep.hip, hmm_sample_perstep.hip)
 
@@ -542,6 +544,94 @@ def hmm_logZ_perstep_differentiable(natparam, lengths=None):
         if not isinstance(x, torch.Tensor):
             raise TypeError("hmm_logZ_perstep_differentiable takes torch tensors")
     return _HMMLogZPerstep.apply(init_params, pair_params, node_params, lengths)
+
+
+def hmm_estep_perstep_vjp(natparam, cotangents, workspace=None, lengths=None, check=False, want_pair=True):
+    """The reverse-mode derivative of hmm_estep_perstep (svae_hmm_perstep_estep_vjp_f64, include/svae_hip.h): natparam as
+    there; cotangents = (g_logZ, (g_init, g_trans, g_states)) in the shapes hmm_estep_perstep returns -- g_trans PER STEP,
+    (…,T-1,K,K) --, each may be None (zero).  Returns the PER-SEQUENCE gradients (d_init (B,K), d_pair (B,T-1,K,K),
+    d_node (B,T,K)) -- without the leading axis for unbatched (T,K) node potentials --; a shared init or pair parameter's
+    gradient is their sum over the batch.  want_pair=False returns d_pair = None and skips the pass that forms it (the pair
+    parameters need no gradient); d_init and d_node do not change a bit.  One route, log space throughout: nothing is
+    flagged or redone.
+    workspace: a contiguous float64 device tensor of at least svae_hmm_perstep_estep_vjp_workspace_bytes(B,T,K) bytes.
+    lengths: (B,) integers -- the gradient of every sequence cut to its length; d_node[b, L:] and d_pair[b, L-1:] are
+    exactly 0, and nothing of the potentials or cotangents from there on is read."""
+    B, T, K, batched, pair_batched = _perstep_shapes(natparam)
+    g_logZ, (g_init, g_trans, g_states) = cotangents
+    for name, x, shape in (("g_logZ", g_logZ, (B,)), ("g_init", g_init, (B, K)), ("g_trans", g_trans, (B, T - 1, K, K)),
+                           ("g_states", g_states, (B, T, K))):
+        want = shape if batched else shape[1:]
+        if x is not None and _shape_of(x) != want:
+            raise ValueError("%s must have shape %r, got %r" % (name, want, _shape_of(x)))
+    lens, dev = _perstep_device(natparam, lengths)
+    init_params, pair_params, node = (_dev64(x, dev) for x in natparam)
+    cots = [None if x is None else _dev64(x, dev) for x in (g_logZ, g_init, g_trans, g_states)]
+    lib = _lib.load()
+    f64 = dict(dtype=torch.float64, device=dev)
+    if workspace is None:
+        wsb = int(lib.svae_hmm_perstep_estep_vjp_workspace_bytes(max(B, 1), T, K))
+        ws = torch.empty(wsb // 8, **f64)
+    else:
+        ws = workspace
+        wsb = ws.numel() * ws.element_size()
+    d_init, d_node = torch.empty(B, K, **f64), torch.empty(B, T, K, **f64)
+    d_pair = torch.empty(B, T - 1, K, K, **f64) if want_pair else None
+    p = _lib.ptr
+    rc = lib.svae_hmm_perstep_estep_vjp_f64(B, T, K, int(pair_batched), p(init_params), p(pair_params), p(node), p(lens),
+                                            p(cots[0]), p(cots[1]), p(cots[2]), p(cots[3]), p(d_init), p(d_pair), p(d_node),
+                                            p(_status_word(dev)) if lens is not None else None, p(ws), wsb,
+                                            _lib.current_stream(dev))
+    _lib.check(rc, "svae_hmm_perstep_estep_vjp_f64")
+    if lens is not None and check:
+        check_lengths_status(dev)
+    if not batched:
+        return d_init[0], None if d_pair is None else d_pair[0], d_node[0]
+    return d_init, d_pair, d_node
+
+
+class _HMMEStepPerstep(torch.autograd.Function):
+    """hmm_estep_perstep with its reverse-mode derivative: forward is hmm_estep_perstep unchanged, backward one call of
+    svae_hmm_perstep_estep_vjp_f64 on the saved potentials (without d_pair when the pair parameters need no gradient)."""
+
+    @staticmethod
+    def forward(ctx, init_params, pair_params, node_params, lengths, check):
+        logZ, (E_init, E_trans, E_states) = hmm_estep_perstep((init_params, pair_params, node_params), lengths=lengths,
+                                                              check=check)
+        ctx.save_for_backward(init_params, pair_params, node_params)
+        ctx.lengths = lengths
+        return logZ, E_init, E_trans, E_states
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g_logZ, g_init, g_trans, g_states):
+        init_params, pair_params, node_params = ctx.saved_tensors
+        need = ctx.needs_input_grad
+        d_init, d_pair, d_node = hmm_estep_perstep_vjp((init_params, pair_params, node_params),
+                                                       (g_logZ, (g_init, g_trans, g_states)), lengths=ctx.lengths,
+                                                       want_pair=need[1])
+        if node_params.dim() == 3:
+            d_init = d_init.sum(0)                    # shared parameters receive the batch sum
+            if need[1] and pair_params.dim() == 3:
+                d_pair = d_pair.sum(0)
+        like = lambda d, x: d.to(device=x.device, dtype=x.dtype)          # noqa: E731
+        return (like(d_init, init_params) if need[0] else None, like(d_pair, pair_params) if need[1] else None,
+                like(d_node, node_params) if need[2] else None, None, None)
+
+
+def hmm_estep_perstep_differentiable(natparam, lengths=None, check=False):
+    """hmm_estep_perstep -> (logZ, (E_init, E_trans, E_states)) with gradients of all four outputs flowing to whichever of
+    init (K), pair (T-1,K,K) or (B,T-1,K,K) and node (T,K) or (B,T,K) require them (torch tensors on the device).  The
+    outputs are those of hmm_estep_perstep, bit for bit; the backward pass is one call of svae_hmm_perstep_estep_vjp_f64
+    (once differentiable): a shared init or pair parameter receives the sum over the batch, a per-sequence pair parameter
+    its own block; pair parameters that need no gradient (a recognition network that emits node potentials only) skip the
+    pass that forms it.  With lengths= the gradient is that of every sequence cut to its length: exactly 0 from there on."""
+    init_params, pair_params, node_params = natparam
+    for x in (init_params, pair_params, node_params):
+        if not isinstance(x, torch.Tensor):
+            raise TypeError("hmm_estep_perstep_differentiable takes torch tensors")
+    logZ, E_init, E_trans, E_states = _HMMEStepPerstep.apply(init_params, pair_params, node_params, lengths, check)
+    return logZ, (E_init, E_trans, E_states)
 
 
 def _perstep_device(natparam, lengths):
