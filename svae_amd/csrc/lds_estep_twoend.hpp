@@ -139,6 +139,92 @@ __device__ __forceinline__ void te_gauss_jordan(double (&M)[N], const double (&E
 #define TE_TICK(i)
 #endif
 
+// S4's hand-over block of the log-normaliser's operands: [7 doubles | 2 ints][64 lanes], lane for lane.  Through pointers
+// QUALIFIED as LDS: as flat stores they would leave hipcc's wait-count bookkeeping with a pending flat access, and the
+// smoother loop that follows would wait for vmcnt(0) at its head on every trip (see hand_off_rows).
+struct TeLnzBlock {
+  static constexpr int ND = 7, NI = 2;                 // operands that are doubles (slots 0 .. ND-1) / ints (slots 0 .. NI-1)
+  static constexpr int DOUBLES = ND * 64 + (NI * 64 + 1) / 2;   // the block's size: what the buffer behind `base` must hold
+  typedef __attribute__((address_space(3))) double ldouble;
+  typedef __attribute__((address_space(3))) int lint;
+  double* base; int lane;
+  __device__ __forceinline__ int* ints() const { return reinterpret_cast<int*>(base + ND * 64); }
+  __device__ __forceinline__ void put(int k, double v) const { *(ldouble*)(base + k * 64 + lane) = v; }
+  __device__ __forceinline__ void puti(int k, int v) const { *(lint*)(ints() + k * 64 + lane) = v; }
+  __device__ __forceinline__ double get(int k) const { return *(const ldouble*)(base + k * 64 + lane); }
+  __device__ __forceinline__ int geti(int k) const { return *(const lint*)(ints() + k * 64 + lane); }
+};
+constexpr int TE_LNZ_DOUBLES = TeLnzBlock::DOUBLES;
+static_assert(TeLnzBlock::ND == 7 && TeLnzBlock::NI == 2,
+              "the slots used in lds_estep_twoend_body: qacc, ldM, qacc_s, ldM_s, vworst, qacc_m, vfull_m | ldE, ldE_s");
+
+// ---- log-normaliser and status word ----------------------------------------------------------------
+// A function of the nine accumulators a wavefront leaves behind (per lane; c = lane & 15 of DPP row lane >> 4, rows 0, 1 =
+// chain A, rows 2, 3 = chain B): qacc / ldM / ldE of all of the chain's eliminations, their snapshots at the partner's
+// hand-over point (take_partner), the largest -1/p of the chain, and the meeting node's qacc_m / vfull_m.  S4 runs it on
+// ANOTHER wavefront than the one that eliminated: the operands travel through LDS, lane for lane.
+// EARLY (S4 only; the other variants keep their instruction order): the two constants of the final sum are fetched first.
+template <int N, bool INHOMOG, bool MIX, bool RING, bool EARLY = false>
+__device__ __forceinline__ void te_log_normaliser(const LdsArgs& a, const int b, const int lane, const double qacc,
+                                                  const double ldM, const int ldE, const double qacc_s, const double ldM_s,
+                                                  const int ldE_s, const double vworst, const double qacc_m,
+                                                  const double vfull_m) {
+  constexpr int HL = 15;
+  const int c = lane & 15, T = a.T;
+  const bool col = c < N;
+  // (EARLY: nothing has touched the two constants on this CU yet, and the three logarithms below cover the round trip
+  //  that otherwise stands, exposed, in front of the final sum)
+  [[maybe_unused]] double init_early = 0.0, pair_early = 0.0;
+  if constexpr (EARLY && !(MIX || RING)) init_early = a.init_logZ[0];
+  if constexpr (EARLY && !INHOMOG) pair_early = a.logZ_pair[0];
+  // per chain: 1/2 sum h'P^-1h - 1/2 sum log p = 1/2 [ q + sum_c log|prod_t (-1/p_c)| ]
+  // (q enters the row sum in lane N, where the row-per-chain kernels keep their h column, not in lane HL = 15: the
+  //  sum is a butterfly, and with q in lane 15 it groups the terms differently at N = 3, 5, 6, 7 -- at N = 5,
+  //  ((l0 + l1) + (l2 + l3) + l4) + q against ((l0 + l1) + (l2 + l3)) + (l4 + q) -- which left the two kernels' log-normalisers apart in their last bits there)
+  auto h_to_lane_n = [&](double q) { return bcast_fenced<HL>(q); };
+  auto chain_part = [&](double q, double m, int ee) {
+    const int ex = __builtin_amdgcn_frexp_exp(m);
+    const double mant = __builtin_amdgcn_frexp_mant(m);
+    double part = col ? (::log(fabs(mant)) + (double)(ee + ex) * 0.6931471805599453094) : 0.0;
+    const double qh = h_to_lane_n(q);
+    if (c == N) part = qh;
+    return 0.5 * row_sum16(part);
+  };
+  double pm = col ? ::log(fabs(vfull_m)) : 0.0;
+  const double qm = h_to_lane_n(qacc_m);
+  if (c == N) pm = qm;
+  const double meet_total = 0.5 * row_sum16(pm);
+  // all of this chain's eliminations + the partner's up to its hand-over + this chain's meeting node
+  const double chain_total = chain_part(qacc, ldM, ldE) + __shfl_xor(chain_part(qacc_s, ldM_s, ldE_s), 32);
+  double z = 0.0;
+  if (a.node_logZ) {
+    for (int t = c; t < T; t += 16) z += a.node_logZ[(long)b * T + t];
+  }
+  if (INHOMOG && !MIX && !RING) {
+    const double* lz = a.logZ_pair + (a.pair_seq_stride ? (long)b * (T - 1) : 0);
+    for (int t = c; t < T - 1; t += 16) z += lz[t];
+  }
+  // (MIX: the mixed log-normaliser constants sum_k w_k logZ_k are the caller's, a (B,T,K) x (K) product)
+  double total = row_sum16(z) + chain_total + meet_total + ((MIX || RING) ? 0.0 : (EARLY ? init_early : a.init_logZ[0]));
+  if (!INHOMOG) total += (double)(T - 1) * (EARLY ? pair_early : a.logZ_pair[0]);
+  // (both through pointers QUALIFIED as global memory: as flat accesses -- what hipcc makes of them here -- they leave
+  //  its wait-count bookkeeping with "may return out of order" until the next full wait, and S4's smoother loop, which
+  //  now follows with its ring loads in flight, would wait for vmcnt(0) at its head on every trip)
+  typedef __attribute__((address_space(1))) double gdouble;
+  typedef __attribute__((address_space(1))) volatile int32_t gvint32;
+  if (lane == 0) ((gdouble*)a.lognorm)[b] = total;
+  const bool lane_bad = col && (!(vworst < 0.0) || !(vfull_m < 0.0));
+  const bool bad = __ballot(lane_bad) != 0 || !(total == total);
+  if (bad && lane == 0) {   // rare path: keep the smallest failing index (+1); 0 = ok
+    int old = *(gvint32*)a.info;
+    while (old == 0 || old > b + 1) {
+      const int seen = atomicCAS(a.info, old, b + 1);
+      if (seen == old) break;
+      old = seen;
+    }
+  }
+}
+
 // LEAN hand-off (the default): per (chain, step) only the lower triangle of P^-1 and c = P^-1 h_filt
 // (te_lean_step_doubles: 68 doubles at n = 10 instead of 220); the smoother rebuilds G = -P^-1 J12 with one
 // split product per step and transposes it through 3 KB of LDS.  Algorithmic HBM bytes x ~4 instead of x 11.
@@ -199,7 +285,11 @@ __device__ __forceinline__ void lds_estep_twoend_body(const LdsArgs& a, const in
   constexpr int RSL = (N + 3) & ~1;       // LDS row stride of the transposition tile (even, >= N + 1)
   constexpr bool TE_STAGE_ASM = !MIX && (SVAE_TE_STAGE_ASM);   // the elimination step's stages as one statement each
   __shared__ double tab_static[MIX ? 2 : (S4 ? 4 : 2) * 16 * 16];   // [chain][row 0..15][RSL]: G~ rows for the transposed read (S4: + the gather tiles)
-  __shared__ double xch_static[S4 ? 2 * ((N + 3) / 4) * 64 + 256 : 2];   // S4: chain B's sums on their way to chain A
+  // S4: the elimination phase's split tile, then the log-normaliser's operands on their way to chain B's wavefront
+  // (TE_LNZ_DOUBLES), then chain B's sums on their way to chain A: three uses one after the other, see te_smooth4
+  constexpr int XCH = S4 ? (2 * ((N + 3) / 4) * 64 + 256 > TE_LNZ_DOUBLES ? 2 * ((N + 3) / 4) * 64 + 256 : TE_LNZ_DOUBLES) : 2;
+  __shared__ double xch_static[XCH];
+  static_assert(!S4 || XCH >= TE_LNZ_DOUBLES, "the hand-over block of the log-normaliser's operands fits the exchange buffer");
   extern __shared__ double2 te_dyn[];     // MIX: the parameter tables (te_mix_lds_bytes)
 
   const int lane = threadIdx.x & 63;
@@ -220,7 +310,7 @@ __device__ __forceinline__ void lds_estep_twoend_body(const LdsArgs& a, const in
   // re-replication tile of the elimination phase, [chain][row 0..N][16]: S4 borrows the exchange buffer (used at the very
   // end), the other variants the transposition tiles (used by the smoother phase only, zeroed again in between)
   double* const split_tile = S4 ? xch_static : tab_static;
-  static_assert(MIX || 2 * (N + 1) * 16 <= (S4 ? 2 * ((N + 3) / 4) * 64 + 256 : 2 * 16 * 16), "split tile fits");
+  static_assert(MIX || 2 * (N + 1) * 16 <= (S4 ? XCH : 2 * 16 * 16), "split tile fits");
   // S4: the last `keep` records of each chain stay in (dynamic) LDS -- the smoother reads them first -- instead of
   // travelling through HBM: [chain][slot][WS] doubles, slot = local step - (e + 1 - keep)
   double* const lrecs = reinterpret_cast<double*>(te_dyn);
@@ -243,7 +333,14 @@ __device__ __forceinline__ void lds_estep_twoend_body(const LdsArgs& a, const in
                       __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
                       S4_TICK(10)
                     },
-                    []() {}
+                    [&]() {
+                      // the log-normaliser and the status word, which no other result waits for: chain A's wavefront -- the
+                      // critical one -- left their operands in the exchange buffer on its way to the barrier above
+                      const TeLnzBlock h{xch_static, lane};
+                      te_log_normaliser<N, INHOMOG, MIX, false, true>(a, b, lane, h.get(0), h.get(1), h.geti(0), h.get(2), h.get(3),
+                                                                h.geti(1), h.get(4), h.get(5), h.get(6));
+                      S4_TICK(14)
+                    }
 #ifdef SVAE_PHASE_TIMING
                     , tm1, &tl1
 #endif
@@ -335,6 +432,30 @@ __device__ __forceinline__ void lds_estep_twoend_body(const LdsArgs& a, const in
   const int xq = 2 * (c - N) + gl;                    // right-hand-side column of this lane (c >= N)
   const bool xok = c >= N && c < HL && xq < N;
   const int xx = xok ? xq : 0;
+  // S4: the parameters of the prologue -- J12' for the right-hand-side lanes and for lanes < N, J22' + J11' of pair 0, the
+  // init potential and J11' of the first pivot block -- are fetched as ONE batch and pinned before anything uses them.
+  // Their only uses are arms of selects on the lane (EX, NJ12c, Cc, An below), and hipcc sinks such a load into a branch
+  // on that condition with a full wait behind it: 30 dependent round trips of memory nobody has touched yet, one after
+  // the other, were most of this wavefront's prologue.  Every index is valid in every lane.
+  struct Pre { double x[N], c[N], c22[J], c11[J], ij[N], ih[N], j11[N]; };
+  [[maybe_unused]] Pre pre;
+  if constexpr (S4) {
+    static_for<0, N>([&](auto i) {
+      pre.x[i] = q12[i * si + xx * sc];
+      pre.c[i] = q12[i * si + cc * sc];
+      pre.ij[i] = a.init_J[i * N + cc];
+      pre.ih[i] = a.init_h[i];
+      pre.j11[i] = q11[i * N + cc];
+    });
+    static_for<0, (N + 1) / 2>([&](auto j) {
+      const int i = 2 * j + gl;
+      const int ii = i < N ? i : 0;
+      pre.c22[j] = q22[ii * N + cc];
+      pre.c11[j] = q11[ii * N + cc];
+    });
+    static_for<0, N>([&](auto i) { pin(pre.x[i]); pin(pre.c[i]); pin(pre.ij[i]); pin(pre.ih[i]); pin(pre.j11[i]); });
+    static_for<0, (N + 1) / 2>([&](auto j) { pin(pre.c22[j]); pin(pre.c11[j]); });
+  }
   // MIX: this lane's table entries (registers and state pairs are immediate offsets from these)
   const double2* tj_l = t_j + (xok ? (dir * 2 + gl) * NXL + (c - N) : (col ? 4 * NXL + dir * N + c : 4 * NXL + 2 * N));
   const double rmask = xok ? 1.0 : 0.0, jcmask = col ? 1.0 : 0.0;
@@ -383,14 +504,18 @@ __device__ __forceinline__ void lds_estep_twoend_body(const LdsArgs& a, const in
   auto load_pair = [&](int l, bool with_cc) {
     const long o = pair_off(l), o1 = pair_off(l + 1);
     static_for<0, N>([&](auto i) {
-      const double rx = q12[o + i * si + xx * sc], rc = q12[o + i * si + cc * sc];
+      double rx, rc;
+      if constexpr (S4) { rx = pre.x[i]; rc = pre.c[i]; }                    // (homogeneous: l = 0, fetched above)
+      else { rx = q12[o + i * si + xx * sc]; rc = q12[o + i * si + cc * sc]; }
       EX[i] = xok ? -rx : E[i];
       NJ12c[i] = col ? rc : 0.0;
     });
     if (with_cc) static_for<0, J>([&](auto j) {
       const int i = 2 * j + gl;
       const int ii = i < N ? i : 0;
-      const double r22 = q22[o + ii * N + cc], r11 = q11[o1 + ii * N + cc];
+      double r22, r11;
+      if constexpr (S4) { r22 = pre.c22[j]; r11 = pre.c11[j]; }
+      else { r22 = q22[o + ii * N + cc]; r11 = q11[o1 + ii * N + cc]; }
       Cc[j] = (col && i < N) ? -2.0 * (r22 + r11) : 0.0;
     });
   };
@@ -446,7 +571,9 @@ __device__ __forceinline__ void lds_estep_twoend_body(const LdsArgs& a, const in
   } else {
     const long o0 = pair_off(0);
     static_for<0, N>([&](auto i) {
-      const double ij = a.init_J[i * N + cc], ih = a.init_h[i], j11 = q11[o0 + i * N + cc];
+      double ij, ih, j11;
+      if constexpr (S4) { ij = pre.ij[i]; ih = pre.ih[i]; j11 = pre.j11[i]; }
+      else { ij = a.init_J[i * N + cc]; ih = a.init_h[i]; j11 = q11[o0 + i * N + cc]; }
       An[i] = col ? -2.0 * ((dir ? 0.0 : ij) + j11) : ((c == HL && !dir) ? ih : 0.0);
     });
   }
@@ -697,6 +824,14 @@ __device__ __forceinline__ void lds_estep_twoend_body(const LdsArgs& a, const in
     if constexpr (S4) for (; s < e; ++s) elim_step(s, std::true_type{});
   }
   if (jx == e) take_partner();
+  if constexpr (S4) {
+    // final from here on: the log-normaliser's operands of the elimination phase go to chain B's wavefront (the split tile
+    // that shared the buffer was read for the last time by the step above)
+    const TeLnzBlock h{xch_static, lane};
+    h.put(0, qacc); h.put(1, ldM); h.puti(0, ldE);
+    h.put(2, qacc_s); h.put(3, ldM_s); h.puti(1, ldE_s);
+    h.put(4, vworst);
+  }
 
   // ---- meeting node ---------------------------------------------------------------------------------
   // Both chains' An count J22'(pair e-1) + J11'(pair e) (the same two blocks in either orientation):
@@ -748,71 +883,26 @@ __device__ __forceinline__ void lds_estep_twoend_body(const LdsArgs& a, const in
 
   // ---- log-normaliser --------------------------------------------------------------------------------
   auto log_normaliser = [&]() {
-    // per chain: 1/2 sum h'P^-1h - 1/2 sum log p = 1/2 [ q + sum_c log|prod_t (-1/p_c)| ]
-    // (q enters the row sum in lane N, where the row-per-chain kernels keep their h column, not in lane HL = 15: the
-    //  sum is a butterfly, and with q in lane 15 it groups the terms differently at N = 3, 5, 6, 7 -- at N = 5,
-    //  ((l0 + l1) + (l2 + l3) + l4) + q against ((l0 + l1) + (l2 + l3)) + (l4 + q) -- which left the two kernels' log-normalisers apart in their last bits there)
-    auto h_to_lane_n = [&](double q) { return bcast_fenced<HL>(q); };
-    auto chain_part = [&](double q, double m, int ee) {
-      const int ex = __builtin_amdgcn_frexp_exp(m);
-      const double mant = __builtin_amdgcn_frexp_mant(m);
-      double part = col ? (::log(fabs(mant)) + (double)(ee + ex) * 0.6931471805599453094) : 0.0;
-      const double qh = h_to_lane_n(q);
-      if (c == N) part = qh;
-      return 0.5 * row_sum16(part);
-    };
-    double pm = col ? ::log(fabs(vfull_m)) : 0.0;
-    const double qm = h_to_lane_n(qacc_m);
-    if (c == N) pm = qm;
-    const double meet_total = 0.5 * row_sum16(pm);
-    // all of this chain's eliminations + the partner's up to its hand-over + this chain's meeting node
-    const double chain_total = chain_part(qacc, ldM, ldE) + __shfl_xor(chain_part(qacc_s, ldM_s, ldE_s), 32);
-    double z = 0.0;
-    if (a.node_logZ) {
-      for (int t = c; t < T; t += 16) z += a.node_logZ[(long)b * T + t];
-    }
-    if (INHOMOG && !MIX && !RING) {
-      const double* lz = a.logZ_pair + (a.pair_seq_stride ? (long)b * (T - 1) : 0);
-      for (int t = c; t < T - 1; t += 16) z += lz[t];
-    }
-    // (MIX: the mixed log-normaliser constants sum_k w_k logZ_k are the caller's, a (B,T,K) x (K) product)
-    double total = row_sum16(z) + chain_total + meet_total + ((MIX || RING) ? 0.0 : a.init_logZ[0]);
-    if (!INHOMOG) total += (double)(T - 1) * a.logZ_pair[0];
-    // (both through pointers QUALIFIED as global memory: as flat accesses -- what hipcc makes of them here -- they leave
-    //  its wait-count bookkeeping with "may return out of order" until the next full wait, and S4's smoother loop, which
-    //  now follows with its ring loads in flight, would wait for vmcnt(0) at its head on every trip)
-    typedef __attribute__((address_space(1))) double gdouble;
-    typedef __attribute__((address_space(1))) volatile int32_t gvint32;
-    if (lane == 0) ((gdouble*)a.lognorm)[b] = total;
-    const bool lane_bad = col && (!(vworst < 0.0) || !(vfull_m < 0.0));
-    const bool bad = __ballot(lane_bad) != 0 || !(total == total);
-    if (bad && lane == 0) {   // rare path: keep the smallest failing index (+1); 0 = ok
-      int old = *(gvint32*)a.info;
-      while (old == 0 || old > b + 1) {
-        const int seen = atomicCAS(a.info, old, b + 1);
-        if (seen == old) break;
-        old = seen;
-      }
-    }
+    te_log_normaliser<N, INHOMOG, MIX, RING>(a, b, lane, qacc, ldM, ldE, qacc_s, ldM_s, ldE_s, vworst, qacc_m, vfull_m);
   };
   if constexpr (S4) {
     // The smoother's set-up that reads no record (its constants, the loads of J12' in its orientation) runs BEFORE the
-    // meeting node; the barrier that wakes chain B's wavefront stands right behind the meeting record's hand-off, and the
-    // log-normaliser -- which nobody else waits for -- follows it, behind this wavefront's first record loads.
+    // meeting node; the barrier that wakes chain B's wavefront stands right behind the meeting record's hand-off.  The
+    // log-normaliser -- which nobody else waits for -- is chain B's wavefront's, behind its smoother (that wavefront
+    // reaches the statistics' exchange first): the meeting node's two operands follow the seven above, and the barrier's
+    // release covers them.
     TE_TICK(12)                                  // (phase indices of the S4 timing build: tools/te_phase_timing.py)
     te_smooth4<N>(a, b, 0, lane, tab_static, tab_static + 512, xch_static, lrecs, keep,
                   [&]() {
                     meeting_node();
+                    const TeLnzBlock h{xch_static, lane};
+                    h.put(5, qacc_m); h.put(6, vfull_m);
                     TE_TICK(13)
                     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
                     __syncthreads();
                     TE_TICK(10)
                   },
-                  [&]() {
-                    TE_TICK(4)
-                    log_normaliser();
-                    TE_TICK(14)
-                  }
+                  []() {}
 #ifdef SVAE_PHASE_TIMING
                   , tm, &tlast_
 #endif

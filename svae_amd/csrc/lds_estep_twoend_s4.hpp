@@ -78,15 +78,16 @@ __device__ __forceinline__ double reg_copy(double x) {       // a copy the compi
 // Both wavefronts of the workgroup call this function; it contains ONE __syncthreads() of its own (at the statistics'
 // exchange) and calls `hand_over` once, which contains the workgroup's other one: everything in front of that call reads
 // no record, so chain B's wavefront has it behind it when the barrier releases, and chain A's issues its loads before
-// the meeting node.  `after_loads` runs once, behind the first record loads (in flight for an L2 round trip): chain A's
-// wavefront computes the log-normaliser there.
+// the meeting node.  `before_exchange` runs once, behind the wavefront's last smoother step and in front of the
+// statistics' exchange: chain B's wavefront, which gets there first, computes the log-normaliser there from the operands
+// chain A's left in `xch` (so it has to read them before its own sums go into that buffer); chain A's does nothing.
 // ptm / ptlast: cycle counts per phase (-DSVAE_PHASE_TIMING builds only, tools/te_phase_timing.py).
 // lrecs / keep: the last `keep` records of each chain (local steps e+1-keep .. e, the ones read first) live in LDS
 // ([chain][slot][WS] doubles, written by the elimination phase) instead of the HBM workspace; keep = 0 or >= 3.
-template <int N, class HandOver, class AfterLoads>
+template <int N, class HandOver, class BeforeExchange>
 __device__ __forceinline__ void te_smooth4(const LdsArgs& a, const int b, const int dir, const int lane,
                                            double* tabw, double* wtw, double* xch, const double* lrecs, const int keep,
-                                           HandOver&& hand_over, AfterLoads&& after_loads,
+                                           HandOver&& hand_over, BeforeExchange&& before_exchange,
                                            [[maybe_unused]] long long* ptm = nullptr,
                                            [[maybe_unused]] long long* ptlast = nullptr) {
   constexpr bool STAGE_ASM = SVAE_S4_STAGE_ASM;
@@ -306,7 +307,6 @@ __device__ __forceinline__ void te_smooth4(const LdsArgs& a, const int b, const 
   if (keep > 0) {
     // records e .. s0 in LDS (keep >= 3: the first two steps find their next record there), s0-1 .. 0 in the HBM ring
     if (s0 > 0) { load_ops(R0); load_ops(R1); load_ops(R2); load_ops(R3); }   // HBM records s0-1 .. s0-4: long on their way
-    after_loads();
     Ops nx;
     lds_ops(nx, e);
     prep_products(std::true_type{}, nx, P);                        // the meeting record: G = 0
@@ -328,7 +328,6 @@ __device__ __forceinline__ void te_smooth4(const LdsArgs& a, const int b, const 
     }
   } else {
     load_ops(R0); load_ops(R1); load_ops(R2); load_ops(R3);       // records e, e-1, e-2, e-3
-    after_loads();
     {
       Ops first;
       static_for<0, J1>([&](auto j) { first.Pi[j] = reg_copy(R0.Pi[j]); });
@@ -354,6 +353,7 @@ __device__ __forceinline__ void te_smooth4(const LdsArgs& a, const int b, const 
   if (s >= 1) rstep(GEN, s - 1, P, R1);
   if (s >= 2) rstep(GEN, s - 2, P, R2);
   S4_TICK(7)
+  before_exchange();
 
   // ---- global statistics: chain B's sums travel to chain A's wavefront through LDS ---------------------------
   // S = S~ at the chain's end node (x_0 for A, x_{T-1} for B).  sumS = sum S~(s) over the chain's counted steps,
