@@ -1,4 +1,5 @@
-// hmm_args.hpp -- launch arguments shared by the HMM kernel units (hmm_estep.hip: K <= 16; hmm_estep_wide.hip: K <= 64).
+// hmm_args.hpp -- launch arguments shared by the HMM kernel units (hmm_estep.hip: K <= 16; hmm_estep_wide.hip: K <= 64)
+// and the sizes every HMM unit derives from K.  The host side of the entry points is hmm_units.hpp.
 #pragma once
 #include <stdint.h>
 
@@ -50,5 +51,12 @@ constexpr int HMM_WIDE_MAX_K = 64;
 constexpr int hmm_wide_kp(int K) { return K <= 32 ? 32 : 64; }
 constexpr int hmm_wide_rec(int KP) { return KP + 2; }
 constexpr double HMM_WIDE_TINY = 1e-200;
+// padded states of the Viterbi, sampling and derivative units, whose records have no width of their own below 17
+// states: 16 (one DPP row per sequence), 32 or 64 (one wavefront per sequence)
+constexpr int hmm_kp(int K) { return K <= 16 ? 16 : (K <= 32 ? 32 : 64); }
+// per-step units (hmm_perstep_kernel.hpp, hmm_perstep_vjp_kernel.hpp and the per-step decoders): lanes per sequence,
+// the smallest group that holds K states, and wavefronts per workgroup
+constexpr int hmm_perstep_group(int K) { return K <= 8 ? 8 : K <= 16 ? 16 : K <= 32 ? 32 : 64; }
+constexpr int hmm_perstep_waves(int K) { return K <= 16 ? 1 : 4; }
 
 }  // namespace svae

@@ -33,7 +33,7 @@
 #include <type_traits>
 
 #include "dpp.hpp"
-#include "hmm_args.hpp"
+#include "hmm_units.hpp"
 
 #ifndef SVAE_HMM_TWOEND
 #define SVAE_HMM_TWOEND 1      // two-ended kernel + one-directional fallback for flagged sequences (0: the one-directional kernel alone; A/B)
@@ -42,6 +42,9 @@
 // hmm_estep_wide.hip: the all-log-space pass over the sequences the kernels of this file flagged
 extern "C" int svae_hmm_row_logspace_launch(const svae::HmmArgs* a, void* stream);
 extern "C" int svae_hmm_row_logspace_ragged_launch(const svae::HmmRaggedArgs* a, void* stream);
+// ... and its scaled kernels of 17 <= K <= 64
+extern "C" int svae_hmm_wide_launch(const svae::HmmArgs* a, void* stream);
+extern "C" int svae_hmm_wide_ragged_launch(const svae::HmmRaggedArgs* a, void* stream);
 
 namespace svae {
 
@@ -566,26 +569,34 @@ __global__ __launch_bounds__(64 * HMM2_WAVES) void hmm_estep2_kernel(const HmmAr
 
 // the scaled pass, then the log-space pass over the sequences it flagged.  The scaled pass is the two-ended kernel
 // where there is a step for each of its wavefronts (T >= HMM2_WAVES; SVAE_HMM_TWOEND = 0: nowhere), else the
-// one-directional kernel: one wavefront does all there is
-template <int K>
-static int launch_hmm(const HmmArgs& a, hipStream_t s) {
-  if (SVAE_HMM_TWOEND && a.T >= HMM2_WAVES) {
-    if (a.pair_contr) hipLaunchKernelGGL((hmm_estep2_kernel<K, true>), dim3((a.B + 3) / 4), dim3(64 * HMM2_WAVES), 0, s, a);
-    else hipLaunchKernelGGL((hmm_estep2_kernel<K, false>), dim3((a.B + 3) / 4), dim3(64 * HMM2_WAVES), 0, s, a);
+// one-directional kernel: one wavefront does all there is.  RAG (per-sequence lengths): the one-directional kernel's
+// ragged instantiation, whatever T
+template <int K, bool RAG>
+static int launch_hmm(const std::conditional_t<RAG, HmmRaggedArgs, HmmArgs>& a, hipStream_t s) {
+  const dim3 grid((a.B + 3) / 4);
+  if constexpr (RAG) {
+    hipLaunchKernelGGL((hmm_estep_kernel<K, false, true>), grid, dim3(64), 0, s, a);
+  } else if (SVAE_HMM_TWOEND && a.T >= HMM2_WAVES) {
+    if (a.pair_contr) hipLaunchKernelGGL((hmm_estep2_kernel<K, true>), grid, dim3(64 * HMM2_WAVES), 0, s, a);
+    else hipLaunchKernelGGL((hmm_estep2_kernel<K, false>), grid, dim3(64 * HMM2_WAVES), 0, s, a);
   } else {
-    if (a.pair_contr) hipLaunchKernelGGL((hmm_estep_kernel<K, true>), dim3((a.B + 3) / 4), dim3(64), 0, s, a);
-    else hipLaunchKernelGGL((hmm_estep_kernel<K, false>), dim3((a.B + 3) / 4), dim3(64), 0, s, a);
+    if (a.pair_contr) hipLaunchKernelGGL((hmm_estep_kernel<K, true>), grid, dim3(64), 0, s, a);
+    else hipLaunchKernelGGL((hmm_estep_kernel<K, false>), grid, dim3(64), 0, s, a);
   }
   if (hipGetLastError() != hipSuccess) return -1000;
-  return svae_hmm_row_logspace_launch(&a, s);
+  if constexpr (RAG) return svae_hmm_row_logspace_ragged_launch(&a, s);
+  else return svae_hmm_row_logspace_launch(&a, s);
 }
 
-// per-sequence lengths: the one-directional kernel, then the log-space pass over the rows it flagged
-template <int K>
-static int launch_hmm_ragged(const HmmRaggedArgs& a, hipStream_t s) {
-  hipLaunchKernelGGL((hmm_estep_kernel<K, false, true>), dim3((a.B + 3) / 4), dim3(64), 0, s, a);
-  if (hipGetLastError() != hipSuccess) return -1000;
-  return svae_hmm_row_logspace_ragged_launch(&a, s);
+// K -> the launch above (K <= 16) or the wide unit's (hmm_estep_wide.hip: 17 <= K <= 64), for either kind of arguments
+template <bool RAG>
+static int hmm_dispatch(const std::conditional_t<RAG, HmmRaggedArgs, HmmArgs>& a, void* stream) {
+  return hmm_dispatch_k(
+      a.K, [&](auto k) { return launch_hmm<k, RAG>(a, (hipStream_t)stream); },
+      [&](auto) {
+        if constexpr (RAG) return svae_hmm_wide_ragged_launch(&a, stream);
+        else return svae_hmm_wide_launch(&a, stream);
+      });
 }
 
 // ---- glue of one SLDS coordinate-ascent sweep (slds_svae.py:159-175), after the HMM and the fused LDS kernels ----------
@@ -874,15 +885,11 @@ __global__ __launch_bounds__(256, SVAE_PC_WPC) void slds_pair_contract_kernel(in
 
 }  // namespace svae
 
-extern "C" int svae_hmm_wide_launch(const svae::HmmArgs* a, void* stream);     // hmm_estep_wide.hip: 17 <= K <= 64
-
 extern "C" size_t svae_hmm_workspace_bytes(int B, int T, int K) {
   if (B <= 0 || T <= 0 || K <= 0 || K > SVAE_HMM_MAX_K) return 0;
   if (K > 16) return (size_t)B * T * svae::hmm_wide_rec(svae::hmm_wide_kp(K)) * sizeof(double);
   return (size_t)B * T * svae::HMM_WS * sizeof(double);
 }
-
-static int hmm_dispatch(const svae::HmmArgs& a, void* stream);
 
 extern "C" int svae_hmm_estep_f64(int B, int T, int K, int pair_batched,
                                   const double* init_params, const double* pair_params,
@@ -908,7 +915,7 @@ extern "C" int svae_hmm_estep_f64(int B, int T, int K, int pair_batched,
   a.ws = (double*)workspace;
   a.seq_index = nullptr; a.n = 0; a.pair_contr = nullptr; a.lds_E_init = nullptr; a.init_J = nullptr; a.init_h = nullptr;
   a.cinit = nullptr; a.lz = nullptr; a.node_out = nullptr;
-  return hmm_dispatch(a, stream);
+  return svae::hmm_dispatch<false>(a, stream);
 }
 
 // HMM step of the SLDS coordinate ascent (hmm_meanfield, /root/reference/svae/models/slds_svae.py:108-115) on the rows
@@ -942,7 +949,7 @@ extern "C" int svae_slds_hmm_meanfield_f64(int B, int rows, int T, int K, int n,
   a.seq_index = seq_index; a.n = n;
   a.pair_contr = node_params ? nullptr : pair_contr; a.lds_E_init = lds_E_init; a.init_J = init_J; a.init_h = init_h;
   a.cinit = cinit; a.lz = lz; a.node_out = node_out;
-  return hmm_dispatch(a, stream);
+  return svae::hmm_dispatch<false>(a, stream);
 }
 
 // After the HMM and the fused LDS kernels of a sweep: per listed row the LDS bound with its mixed constants, the
@@ -1049,20 +1056,13 @@ extern "C" int svae_slds_pair_contract_f64(int B, int T, int K, int n, const dou
   return hipGetLastError() == hipSuccess ? 0 : -1000;
 }
 
-extern "C" int svae_hmm_wide_ragged_launch(const svae::HmmRaggedArgs* a, void* stream);     // hmm_estep_wide.hip
-
 // svae_hmm_estep_f64 with per-sequence lengths (include/svae_hip.h): every check before any HIP call
 extern "C" int svae_hmm_ragged_estep_f64(int B, int T, int K, int pair_batched,
                                          const double* init_params, const double* pair_params,
                                          const double* node_params, const int32_t* lengths,
                                          double* logZ, double* E_init, double* E_trans, double* E_states,
                                          int32_t* info, void* workspace, size_t ws_bytes, void* stream) {
-  if (B < 0) return -1;
-  if (T < 1) return -2;
-  if (K < 1 || K > SVAE_HMM_MAX_K) return -3;
-  if (pair_batched != 0 && pair_batched != 1) return -4;
-  if (!init_params) return -5;
-  if (!pair_params) return -6;
+  if (const int rc = svae::hmm_check_model(B, T, K, pair_batched, init_params, pair_params)) return rc;
   if (B == 0) return 0;
   if (!node_params) return -7;
   if (!lengths) return -8;
@@ -1074,35 +1074,11 @@ extern "C" int svae_hmm_ragged_estep_f64(int B, int T, int K, int pair_batched,
   if (!workspace) return -14;
   if (ws_bytes < svae_hmm_workspace_bytes(B, T, K)) return -15;
   svae::HmmRaggedArgs a;
-  a.B = B; a.T = T; a.K = K; a.pair_stride = pair_batched ? (long)K * K : 0;
-  a.init_params = init_params; a.pair_params = pair_params; a.node_params = node_params;
+  svae::hmm_set_model(a, B, T, K, pair_batched ? (long)K * K : 0, init_params, pair_params, node_params);
   a.logZ = logZ; a.E_init = E_init; a.E_trans = E_trans; a.E_states = E_states;
   a.ws = (double*)workspace;
   a.seq_index = nullptr; a.n = 0; a.pair_contr = nullptr; a.lds_E_init = nullptr; a.init_J = nullptr; a.init_h = nullptr;
   a.cinit = nullptr; a.lz = nullptr; a.node_out = nullptr;
   a.lengths = lengths; a.info = info;
-  if (K > 16) return svae_hmm_wide_ragged_launch(&a, stream);
-  hipStream_t s = (hipStream_t)stream;
-  switch (K) {
-#define SVAE_CASE(KK) case KK: return svae::launch_hmm_ragged<KK>(a, s);
-    SVAE_CASE(1) SVAE_CASE(2) SVAE_CASE(3) SVAE_CASE(4) SVAE_CASE(5) SVAE_CASE(6) SVAE_CASE(7)
-    SVAE_CASE(8) SVAE_CASE(9) SVAE_CASE(10) SVAE_CASE(11) SVAE_CASE(12) SVAE_CASE(13)
-    SVAE_CASE(14) SVAE_CASE(15) SVAE_CASE(16)
-#undef SVAE_CASE
-  }
-  return -3;
-}
-
-static int hmm_dispatch(const svae::HmmArgs& a, void* stream) {
-  const int K = a.K;
-  hipStream_t s = (hipStream_t)stream;
-  if (K > 16) return svae_hmm_wide_launch(&a, stream);
-  switch (K) {
-#define SVAE_CASE(KK) case KK: return svae::launch_hmm<KK>(a, s);
-    SVAE_CASE(1) SVAE_CASE(2) SVAE_CASE(3) SVAE_CASE(4) SVAE_CASE(5) SVAE_CASE(6) SVAE_CASE(7)
-    SVAE_CASE(8) SVAE_CASE(9) SVAE_CASE(10) SVAE_CASE(11) SVAE_CASE(12) SVAE_CASE(13)
-    SVAE_CASE(14) SVAE_CASE(15) SVAE_CASE(16)
-#undef SVAE_CASE
-  }
-  return -3;
+  return svae::hmm_dispatch<true>(a, stream);
 }

@@ -61,12 +61,7 @@ extern "C" int svae_hmm_perstep_estep_f64(int B, int T, int K, int pair_batched,
                                           const double* node_params, const int32_t* lengths,
                                           double* logZ, double* E_init, double* E_trans, double* E_states,
                                           int32_t* info, void* workspace, size_t ws_bytes, void* stream) {
-  if (B < 0) return -1;
-  if (T < 1) return -2;
-  if (K < 1 || K > SVAE_HMM_MAX_K) return -3;
-  if (pair_batched != 0 && pair_batched != 1) return -4;
-  if (!init_params) return -5;
-  if (!pair_params && T > 1) return -6;
+  if (const int rc = svae::hmm_check_model(B, T, K, pair_batched, init_params, pair_params, true)) return rc;
   if (B == 0) return 0;
   if (!node_params) return -7;
   if (!logZ) return -8;
@@ -77,16 +72,11 @@ extern "C" int svae_hmm_perstep_estep_f64(int B, int T, int K, int pair_batched,
   if (ws_bytes < svae_hmm_perstep_workspace_bytes(B, T, K)) return -13;
   if (((uintptr_t)workspace & 15) != 0) return -14;
   svae::HmmPerstepArgs a;
-  a.B = B; a.T = T; a.K = K; a.pair_stride = pair_batched ? (long)(T - 1) * K * K : 0;
-  a.init_params = init_params; a.pair_params = pair_params; a.node_params = node_params; a.lengths = lengths;
+  svae::hmm_set_model(a, B, T, K, pair_batched ? (long)(T - 1) * K * K : 0, init_params, pair_params, node_params);
+  a.lengths = lengths;
   a.logZ = logZ; a.E_init = E_init; a.E_trans = E_trans; a.E_states = E_states; a.info = info;
   a.ws = (double*)workspace;
   hipStream_t s = (hipStream_t)stream;
-  switch (svae::hmm_perstep_group(K)) {
-    case 8: svae::launch_perstep<8, 1>(a, s); break;
-    case 16: svae::launch_perstep<16, 1>(a, s); break;
-    case 32: svae::launch_perstep<32, 4>(a, s); break;
-    default: svae::launch_perstep<64, 4>(a, s); break;
-  }
+  svae::hmm_dispatch_group(K, [&](auto g, auto w) { svae::launch_perstep<g, w>(a, s); });
   return hipGetLastError() == hipSuccess ? 0 : -1000;
 }

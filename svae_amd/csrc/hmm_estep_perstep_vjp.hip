@@ -69,12 +69,7 @@ extern "C" int svae_hmm_perstep_estep_vjp_f64(int B, int T, int K, int pair_batc
                                               const double* g_logZ, const double* g_init, const double* g_trans,
                                               const double* g_states, double* d_init, double* d_pair, double* d_node,
                                               int32_t* info, void* workspace, size_t ws_bytes, void* stream) {
-  if (B < 0) return -1;
-  if (T < 1) return -2;
-  if (K < 1 || K > SVAE_HMM_MAX_K) return -3;
-  if (pair_batched != 0 && pair_batched != 1) return -4;
-  if (!init_params) return -5;
-  if (!pair_params && T > 1) return -6;
+  if (const int rc = svae::hmm_check_model(B, T, K, pair_batched, init_params, pair_params, true)) return rc;
   if (B == 0) return 0;
   if (!node_params) return -7;
   if (!d_init) return -8;
@@ -84,17 +79,12 @@ extern "C" int svae_hmm_perstep_estep_vjp_f64(int B, int T, int K, int pair_batc
   if (ws_bytes < svae_hmm_perstep_estep_vjp_workspace_bytes(B, T, K)) return -12;
   if (((uintptr_t)workspace & 15) != 0) return -13;
   svae::HmmPerstepVjpArgs a;
-  a.B = B; a.T = T; a.K = K; a.pair_stride = pair_batched ? (long)(T - 1) * K * K : 0;
-  a.init_params = init_params; a.pair_params = pair_params; a.node_params = node_params; a.lengths = lengths;
+  svae::hmm_set_model(a, B, T, K, pair_batched ? (long)(T - 1) * K * K : 0, init_params, pair_params, node_params);
+  a.lengths = lengths;
   a.g_logZ = g_logZ; a.g_init = g_init; a.g_trans = T > 1 ? g_trans : nullptr; a.g_states = g_states;
   a.d_init = d_init; a.d_pair = T > 1 ? d_pair : nullptr; a.d_node = d_node; a.info = info;
   a.ws = (double*)workspace;
   hipStream_t s = (hipStream_t)stream;
-  switch (svae::hmm_perstep_vjp_group(K)) {
-    case 8: svae::launch_perstep_vjp<8, 1>(a, s); break;
-    case 16: svae::launch_perstep_vjp<16, 1>(a, s); break;
-    case 32: svae::launch_perstep_vjp<32, 4>(a, s); break;
-    default: svae::launch_perstep_vjp<64, 4>(a, s); break;
-  }
+  svae::hmm_dispatch_group(K, [&](auto g, auto w) { svae::launch_perstep_vjp<g, w>(a, s); });
   return hipGetLastError() == hipSuccess ? 0 : -1000;
 }

@@ -34,21 +34,7 @@
 
 #include "../../include/svae_hip.h"
 #include "dpp.hpp"
-#include "hmm_estep_vjp_kernel.hpp"   // the kernel templates; this unit instantiates the uniform (RAGGED = false) ones
-
-namespace svae {
-
-template <int K>
-static void launch_vjp_row(const VjpArgs& a, hipStream_t s) {
-  hipLaunchKernelGGL((hmm_vjp_row_kernel<K, false>), dim3((a.B + 3) / 4), dim3(64), 0, s, a);
-}
-template <int KP>
-static void launch_vjp_wide(const VjpArgs& a, hipStream_t s) {
-  if constexpr (KP > 16) hipLaunchKernelGGL((hmm_vjp_wide_kernel<KP, false, false>), dim3(a.B), dim3(64), 0, s, a);
-  hipLaunchKernelGGL((hmm_vjp_wide_kernel<KP, true, false>), dim3(a.B), dim3(64), 0, s, a);
-}
-
-}  // namespace svae
+#include "hmm_estep_vjp_kernel.hpp"   // the kernel templates and their launch; this unit instantiates RAGGED = false
 
 extern "C" size_t svae_hmm_estep_vjp_workspace_bytes(int B, int T, int K) {
   if (B <= 0 || T <= 0 || K <= 0 || K > SVAE_HMM_MAX_K) return 0;
@@ -62,12 +48,7 @@ extern "C" int svae_hmm_estep_vjp_f64(int B, int T, int K, int pair_batched,
                                       const double* g_states,
                                       double* d_init, double* d_pair, double* d_node,
                                       void* workspace, size_t ws_bytes, void* stream) {
-  if (B < 0) return -1;
-  if (T < 1) return -2;
-  if (K < 1 || K > SVAE_HMM_MAX_K) return -3;
-  if (pair_batched != 0 && pair_batched != 1) return -4;
-  if (!init_params) return -5;
-  if (!pair_params) return -6;
+  if (const int rc = svae::hmm_check_model(B, T, K, pair_batched, init_params, pair_params)) return rc;
   if (B == 0) return 0;
   if (!node_params) return -7;
   if (!d_init) return -8;
@@ -77,24 +58,8 @@ extern "C" int svae_hmm_estep_vjp_f64(int B, int T, int K, int pair_batched,
   if (ws_bytes < svae_hmm_estep_vjp_workspace_bytes(B, T, K)) return -12;
   if (((uintptr_t)workspace & 15) != 0) return -13;
   svae::VjpArgs a;
-  a.B = B; a.T = T; a.K = K; a.pair_stride = pair_batched ? (long)K * K : 0;
-  a.init_params = init_params; a.pair_params = pair_params; a.node_params = node_params;
+  svae::hmm_set_model(a, B, T, K, pair_batched ? (long)K * K : 0, init_params, pair_params, node_params);
   a.g_logZ = g_logZ; a.g_init = g_init; a.g_trans = g_trans; a.g_states = g_states;
   a.d_init = d_init; a.d_pair = d_pair; a.d_node = d_node; a.ws = (double*)workspace;
-  hipStream_t s = (hipStream_t)stream;
-  if (K > 32) {
-    svae::launch_vjp_wide<64>(a, s);
-  } else if (K > 16) {
-    svae::launch_vjp_wide<32>(a, s);
-  } else {
-    switch (K) {
-#define SVAE_CASE(KK) case KK: svae::launch_vjp_row<KK>(a, s); break;
-      SVAE_CASE(1) SVAE_CASE(2) SVAE_CASE(3) SVAE_CASE(4) SVAE_CASE(5) SVAE_CASE(6) SVAE_CASE(7)
-      SVAE_CASE(8) SVAE_CASE(9) SVAE_CASE(10) SVAE_CASE(11) SVAE_CASE(12) SVAE_CASE(13)
-      SVAE_CASE(14) SVAE_CASE(15) SVAE_CASE(16)
-#undef SVAE_CASE
-    }
-    svae::launch_vjp_wide<16>(a, s);
-  }
-  return hipGetLastError() == hipSuccess ? 0 : -1000;
+  return svae::launch_vjp<false>(a, (hipStream_t)stream);
 }

@@ -25,7 +25,7 @@
 #include <type_traits>
 
 #include "dpp.hpp"
-#include "hmm_args.hpp"
+#include "hmm_units.hpp"
 #include "hmm_sample_kernel.hpp"      // smp_row_max16, smp_wave_sum, smp_wave_max, smp_lds_sync
 
 namespace svae {
@@ -52,8 +52,7 @@ struct VjpRaggedArgs : VjpArgs {
 template <bool RAGGED>
 using VjpArgsT = std::conditional_t<RAGGED, VjpRaggedArgs, VjpArgs>;
 
-constexpr int vjp_kp(int K) { return K <= 16 ? 16 : (K <= 32 ? 32 : 64); }
-constexpr size_t vjp_ws_doubles(long B, long T, int K) { return (size_t)(B * T * 2 * vjp_kp(K) + B); }
+constexpr size_t vjp_ws_doubles(long B, long T, int K) { return (size_t)(B * T * 2 * hmm_kp(K) + B); }
 
 // Between two walks over the same line: the second reads LDS again instead of keeping the first one's KP values (or the
 // KP sums made of them) in registers
@@ -514,6 +513,26 @@ __global__ __launch_bounds__(64) void hmm_vjp_wide_kernel(const VjpArgsT<RAGGED>
     flagged = __any(flagged);
     if (lane == 0) *flagp = flagged ? 1.0 : 0.0;
   }
+}
+
+// ---- host: the two launches behind svae_hmm_estep_vjp_f64 (RAGGED = false) and svae_hmm_ragged_estep_vjp_f64 (RAGGED =
+// true): the scaled kernel, then the log-space kernel of its width over the sequences it flagged (KP = 16 behind a row kernel)
+template <bool RAGGED>
+static int launch_vjp(const VjpArgsT<RAGGED>& a, hipStream_t s) {
+  auto redo = [&](auto kp) { hipLaunchKernelGGL((hmm_vjp_wide_kernel<kp, true, RAGGED>), dim3(a.B), dim3(64), 0, s, a); };
+  hmm_dispatch_k(
+      a.K,
+      [&](auto k) {
+        hipLaunchKernelGGL((hmm_vjp_row_kernel<k, RAGGED>), dim3((a.B + 3) / 4), dim3(64), 0, s, a);
+        redo(std::integral_constant<int, 16>{});
+        return 0;
+      },
+      [&](auto kp) {
+        hipLaunchKernelGGL((hmm_vjp_wide_kernel<kp, false, RAGGED>), dim3(a.B), dim3(64), 0, s, a);
+        redo(kp);
+        return 0;
+      });
+  return hipGetLastError() == hipSuccess ? 0 : -1000;
 }
 
 }  // namespace svae

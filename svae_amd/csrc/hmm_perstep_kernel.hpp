@@ -9,6 +9,8 @@
 #include <math.h>
 #include <stdint.h>
 
+#include "hmm_units.hpp"    // hmm_perstep_group, hmm_perstep_waves (hmm_args.hpp) and the entry points' host helpers
+
 namespace svae {
 
 // a separate type: the uniform kernels' HmmArgs and the ragged HmmRaggedArgs (hmm_args.hpp) stay what they are
@@ -27,8 +29,6 @@ struct HmmPerstepArgs {
   double* __restrict__ ws;                 // (B,T,K) log alpha
 };
 
-constexpr int hmm_perstep_group(int K) { return K <= 8 ? 8 : K <= 16 ? 16 : K <= 32 ? 32 : 64; }
-constexpr int hmm_perstep_waves(int K) { return K <= 16 ? 1 : 4; }
 // per group: tile, vector, and per wavefront the row factors and the partial (maximum, sum) pairs
 constexpr int hmm_perstep_lds_doubles(int K, int W) { return K * (K | 1) + K + 3 * W * K; }
 

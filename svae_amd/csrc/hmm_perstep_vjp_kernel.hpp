@@ -6,6 +6,8 @@
 #include <math.h>
 #include <stdint.h>
 
+#include "hmm_units.hpp"    // hmm_perstep_group, hmm_perstep_waves (hmm_args.hpp) and the entry points' host helpers
+
 namespace svae {
 
 struct HmmPerstepVjpArgs {
@@ -26,8 +28,6 @@ struct HmmPerstepVjpArgs {
   double* __restrict__ ws;                 // (B,T,2K): [la_t | r_t]
 };
 
-constexpr int hmm_perstep_vjp_group(int K) { return K <= 8 ? 8 : K <= 16 ? 16 : K <= 32 ? 32 : 64; }
-constexpr int hmm_perstep_vjp_waves(int K) { return K <= 16 ? 1 : 4; }
 // per group: the e tile and the V tile, the two broadcast vectors, and per wavefront the row factors and the partial
 // (maximum, sum, weighted sum) triples
 constexpr int hmm_perstep_vjp_lds_doubles(int K, int W) { return 2 * K * (K | 1) + 2 * K + 4 * W * K; }

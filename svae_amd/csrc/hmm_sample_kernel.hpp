@@ -23,7 +23,7 @@
 #include <type_traits>
 
 #include "dpp.hpp"
-#include "hmm_args.hpp"
+#include "hmm_units.hpp"
 
 namespace svae {
 
@@ -46,7 +46,6 @@ struct SampleRaggedArgs : SampleArgs {
 template <bool RAGGED>
 using SampleArgsT = std::conditional_t<RAGGED, SampleRaggedArgs, SampleArgs>;
 
-constexpr int sample_kp(int K) { return K <= 16 ? 16 : (K <= 32 ? 32 : 64); }
 constexpr double SMP_TINY = 1e-200;   // a normaliser below it (filter): the sequence is redone in log space; a weight
                                       // total below it (draw): that draw's weights in log space
 constexpr int SMP_AHEAD = 8;          // filter: node potentials in flight, steps
@@ -528,6 +527,40 @@ __global__ __launch_bounds__(64) void hmm_draw_wide_kernel(const SampleArgsT<RAG
   if constexpr (RAGGED) {
     for (int t = TL + lane; t < T; t += 64) out[t] = -1;
   }
+}
+
+}  // namespace svae
+
+// hmm_sample_log.hip: the log-space filter, at work on the sequences the scaled filter flagged
+extern "C" int svae_hmm_sample_log_launch(const svae::SampleArgs* a, void* stream);
+extern "C" int svae_hmm_sample_log_ragged_launch(const svae::SampleRaggedArgs* a, void* stream);
+
+namespace svae {
+
+// ---- host: the three launches behind svae_hmm_sample_f64 (RAGGED = false) and svae_hmm_ragged_sample_f64 (RAGGED = true):
+// the scaled filter, the log-space filter over what it flagged, the draw
+template <bool RAGGED>
+static int launch_sample(const SampleArgsT<RAGGED>& a, hipStream_t s) {
+  auto log_filter = [&] {
+    if constexpr (RAGGED) svae_hmm_sample_log_ragged_launch(&a, s);
+    else svae_hmm_sample_log_launch(&a, s);
+  };
+  const long R = (long)a.B * a.S;
+  hmm_dispatch_k(
+      a.K,
+      [&](auto k) {
+        hipLaunchKernelGGL((hmm_filter_row_kernel<k, RAGGED>), dim3((a.B + 3) / 4), dim3(64), 0, s, a);
+        log_filter();
+        hipLaunchKernelGGL((hmm_draw_row_kernel<k, RAGGED>), dim3((unsigned)((R + 3) / 4)), dim3(64), 0, s, a);
+        return 0;
+      },
+      [&](auto kp) {
+        hipLaunchKernelGGL((hmm_filter_wide_kernel<kp, RAGGED>), dim3(a.B), dim3(64), 0, s, a);
+        log_filter();
+        hipLaunchKernelGGL((hmm_draw_wide_kernel<kp, RAGGED>), dim3((unsigned)R), dim3(64), 0, s, a);
+        return 0;
+      });
+  return hipGetLastError() == hipSuccess ? 0 : -1000;
 }
 
 }  // namespace svae

@@ -202,12 +202,7 @@ extern "C" int svae_hmm_perstep_sample_f64(int B, int T, int K, int S, int pair_
                                            const double* node_params, const int32_t* lengths, const double* u,
                                            int32_t* states, double* logZ,
                                            int32_t* info, void* workspace, size_t ws_bytes, void* stream) {
-  if (B < 0) return -1;
-  if (T < 1) return -2;
-  if (K < 1 || K > SVAE_HMM_MAX_K) return -3;
-  if (pair_batched != 0 && pair_batched != 1) return -4;
-  if (!init_params) return -5;
-  if (!pair_params && T > 1) return -6;
+  if (const int rc = svae::hmm_check_model(B, T, K, pair_batched, init_params, pair_params, true)) return rc;
   if (B == 0) return 0;
   if (!node_params) return -7;
   if (S < 1) return -8;
@@ -219,19 +214,17 @@ extern "C" int svae_hmm_perstep_sample_f64(int B, int T, int K, int S, int pair_
   if (((uintptr_t)workspace & 15) != 0) return -14;
   const long stride = pair_batched ? (long)(T - 1) * K * K : 0;
   svae::HmmPerstepArgs f;
-  f.B = B; f.T = T; f.K = K; f.pair_stride = stride;
-  f.init_params = init_params; f.pair_params = pair_params; f.node_params = node_params; f.lengths = lengths;
+  svae::hmm_set_model(f, B, T, K, stride, init_params, pair_params, node_params);
+  f.lengths = lengths;
   f.logZ = logZ; f.E_init = nullptr; f.E_trans = nullptr; f.E_states = nullptr; f.info = info;
   f.ws = (double*)workspace;
   svae::PerstepDrawArgs d;
   d.B = B; d.T = T; d.K = K; d.S = S; d.pair_stride = stride;
   d.pair_params = pair_params; d.lengths = lengths; d.u = u; d.states = states; d.la = (const double*)workspace;
   hipStream_t s = (hipStream_t)stream;
-  switch (svae::hmm_perstep_group(K)) {
-    case 8: svae::launch_perstep_filter<8, 1>(f, s); svae::launch_perstep_draw<8>(d, s); break;
-    case 16: svae::launch_perstep_filter<16, 1>(f, s); svae::launch_perstep_draw<16>(d, s); break;
-    case 32: svae::launch_perstep_filter<32, 4>(f, s); svae::launch_perstep_draw<32>(d, s); break;
-    default: svae::launch_perstep_filter<64, 4>(f, s); svae::launch_perstep_draw<64>(d, s); break;
-  }
+  svae::hmm_dispatch_group(K, [&](auto g, auto w) {
+    svae::launch_perstep_filter<g, w>(f, s);
+    svae::launch_perstep_draw<g>(d, s);
+  });
   return hipGetLastError() == hipSuccess ? 0 : -1000;
 }

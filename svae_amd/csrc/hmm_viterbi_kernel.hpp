@@ -15,6 +15,7 @@
 #include <type_traits>
 
 #include "dpp.hpp"
+#include "hmm_units.hpp"
 
 namespace svae {
 
@@ -35,7 +36,6 @@ struct ViterbiRaggedArgs : ViterbiArgs {
 template <bool RAGGED>
 using ViterbiArgsT = std::conditional_t<RAGGED, ViterbiRaggedArgs, ViterbiArgs>;
 
-constexpr int viterbi_kp(int K) { return K <= 16 ? 16 : (K <= 32 ? 32 : 64); }
 constexpr int VIT_AHEAD = 8;          // node potentials in flight, steps
 
 // 16 back-pointer bytes (values 0..15) -> 16 nibbles
@@ -287,6 +287,22 @@ __global__ __launch_bounds__(64) void hmm_viterbi_wide_kernel(const ViterbiArgsT
   if constexpr (RAGGED) {
     for (int t = TL + lane; t < T; t += 64) out[t] = -1;
   }
+}
+
+// ---- host: the launch behind svae_hmm_viterbi_f64 (RAGGED = false) and svae_hmm_ragged_viterbi_f64 (RAGGED = true) ------
+template <bool RAGGED>
+static int launch_viterbi(const ViterbiArgsT<RAGGED>& a, hipStream_t s) {
+  hmm_dispatch_k(
+      a.K,
+      [&](auto k) {
+        hipLaunchKernelGGL((hmm_viterbi_row_kernel<k, RAGGED>), dim3((a.B + 3) / 4), dim3(64), 0, s, a);
+        return 0;
+      },
+      [&](auto kp) {
+        hipLaunchKernelGGL((hmm_viterbi_wide_kernel<kp, RAGGED>), dim3(a.B), dim3(64), 0, s, a);
+        return 0;
+      });
+  return hipGetLastError() == hipSuccess ? 0 : -1000;
 }
 
 }  // namespace svae

@@ -36,7 +36,7 @@
 
 #include "../../include/svae_hip.h"
 #include "dpp.hpp"
-#include "hmm_viterbi_kernel.hpp"     // vit_lds_sync, VitBlock, viterbi_kp (no kernel of that header is instantiated here)
+#include "hmm_viterbi_kernel.hpp"     // vit_lds_sync, VitBlock; hmm_units.hpp (no kernel of that header is instantiated here)
 
 namespace svae {
 
@@ -66,7 +66,7 @@ __device__ __forceinline__ double vps_bcast(double x, int tl) {
 
 template <int G, int W>
 __global__ __launch_bounds__(64 * W) void hmm_perstep_viterbi_kernel(const PerstepViterbiArgs a) {
-  constexpr int KP = G < 16 ? 16 : G;            // back-pointer bytes per step (viterbi_kp)
+  constexpr int KP = G < 16 ? 16 : G;            // back-pointer bytes per step (hmm_kp)
   constexpr int QMAX = G / W;                    // the most source states a wavefront reduces per step: 8 or 16
   constexpr int PF = 32 / QMAX;                  // steps of P_t in flight
   constexpr int NQ = KP / 16;                    // 16-byte pieces of a G-step back-pointer block, per lane
@@ -279,12 +279,7 @@ extern "C" int svae_hmm_perstep_viterbi_f64(int B, int T, int K, int pair_batche
                                             const double* node_params, const int32_t* lengths,
                                             int32_t* states, double* score,
                                             int32_t* info, void* workspace, size_t ws_bytes, void* stream) {
-  if (B < 0) return -1;
-  if (T < 1) return -2;
-  if (K < 1 || K > SVAE_HMM_MAX_K) return -3;
-  if (pair_batched != 0 && pair_batched != 1) return -4;
-  if (!init_params) return -5;
-  if (!pair_params && T > 1) return -6;
+  if (const int rc = svae::hmm_check_model(B, T, K, pair_batched, init_params, pair_params, true)) return rc;
   if (B == 0) return 0;
   if (!node_params) return -7;
   if (!states) return -8;
@@ -293,13 +288,10 @@ extern "C" int svae_hmm_perstep_viterbi_f64(int B, int T, int K, int pair_batche
   if (ws_bytes < svae_hmm_viterbi_workspace_bytes(B, T, K)) return -11;
   if (((uintptr_t)workspace & 15) != 0) return -12;   // back-pointer blocks are read back 16 bytes at a time
   svae::PerstepViterbiArgs a;
-  a.B = B; a.T = T; a.K = K; a.pair_stride = pair_batched ? (long)(T - 1) * K * K : 0;
-  a.init_params = init_params; a.pair_params = pair_params; a.node_params = node_params; a.lengths = lengths;
+  svae::hmm_set_model(a, B, T, K, pair_batched ? (long)(T - 1) * K * K : 0, init_params, pair_params, node_params);
+  a.lengths = lengths;
   a.states = states; a.score = score; a.info = info; a.ws = (uint8_t*)workspace;
   hipStream_t s = (hipStream_t)stream;
-  if (K <= 8) svae::launch_perstep_viterbi<8, 1>(a, s);
-  else if (K <= 16) svae::launch_perstep_viterbi<16, 1>(a, s);
-  else if (K <= 32) svae::launch_perstep_viterbi<32, 4>(a, s);
-  else svae::launch_perstep_viterbi<64, 4>(a, s);
+  svae::hmm_dispatch_group(K, [&](auto g, auto w) { svae::launch_perstep_viterbi<g, w>(a, s); });
   return hipGetLastError() == hipSuccess ? 0 : -1000;
 }

@@ -84,45 +84,117 @@ def _lengths_arg(lengths, node_params):
     return torch.as_tensor(np.asarray(lengths).astype(np.int32), device=dev)
 
 
-def hmm_estep(natparam, workspace=None, lengths=None, check=False):
-    init_params, pair_params, node_params = natparam
+def _shape_of(x):
+    return tuple(x.shape) if hasattr(x, "shape") else np.shape(x)
+
+
+def _node_shape(node_s):
+    """(B, T, K, batched) of node potentials of shape node_s; ValueError for a wrong rank, K outside 1..64 or T = 0"""
+    if len(node_s) not in (2, 3):
+        raise ValueError("node_params must be (T,K) or (B,T,K)")
+    batched = len(node_s) == 3
+    B = node_s[0] if batched else 1
+    T, K = node_s[-2:]
+    if not (1 <= K <= HMM_MAX_K):
+        raise ValueError("number of states K=%d outside 1..%d" % (K, HMM_MAX_K))
+    if T < 1:
+        raise ValueError("node_params has no steps")
+    return B, T, K, batched
+
+
+def _shapes(natparam):
+    """(B, T, K, batched, pair_batched) of a natparam with ONE transition matrix per sequence -- init (K), pair (K,K) or
+    (B,K,K), node (T,K) or (B,T,K) --, from shapes alone: every refusal is a ValueError raised before anything is
+    converted, copied or launched (no device is touched)."""
+    init_s, pair_s, node_s = (_shape_of(x) for x in natparam)
+    B, T, K, batched = _node_shape(node_s)
+    pair_batched = len(pair_s) == 3
+    if init_s != (K,) or pair_s[-2:] != (K, K) or len(pair_s) not in (2, 3) or (pair_batched and pair_s[0] != B):
+        raise ValueError("init/pair parameter shapes do not match the node potentials")
+    return B, T, K, batched, pair_batched
+
+
+def _on_device(natparam, lengths):
+    """(lens, dev, (init, pair, node)) of a call whose shapes have been accepted: the validated (B,) int32 lengths or
+    None, the device, and the three leaves there as contiguous float64 (only their addresses are passed on)"""
+    node_params = natparam[2]
     lens = None if lengths is None else _lengths_arg(lengths, node_params)
     dev = node_params.device if isinstance(node_params, torch.Tensor) and node_params.is_cuda \
         else torch.device("cuda", torch.cuda.current_device())
-    init_params, pair_params, node = (_dev64(x, dev) for x in (init_params, pair_params, node_params))
-    batched = node.dim() == 3
-    if node.dim() not in (2, 3):
-        raise ValueError("node_params must be (T,K) or (B,T,K)")
-    if not batched:
-        node = node[None]
-    B, T, K = node.shape
-    if not (1 <= K <= HMM_MAX_K):
-        raise ValueError("number of states K=%d outside 1..%d" % (K, HMM_MAX_K))
-    pair_batched = pair_params.dim() == 3
-    if tuple(init_params.shape) != (K,) or tuple(pair_params.shape[-2:]) != (K, K) or \
-            (pair_batched and pair_params.shape[0] != B):
-        raise ValueError("init/pair parameter shapes do not match the node potentials")
-    lib = _lib.load()
+    return lens, dev, tuple(_dev64(x, dev) for x in natparam)
+
+
+def _workspace(workspace, nbytes, B, T, K, dev):
+    """(tensor, its size in bytes): the caller's workspace as it is, else a fresh one of nbytes(B, T, K) bytes"""
+    if workspace is not None:
+        return workspace, workspace.numel() * workspace.element_size()
+    wsb = int(nbytes(max(B, 1), T, K))
+    return torch.empty(wsb, dtype=torch.uint8, device=dev), wsb
+
+
+def _call(name, dev, lens, check, *args):
+    """Entry point `name` of the library on args and the current stream of dev: RuntimeError for a return code other than
+    0; then, for a call with lengths and check=True, the status word is read"""
+    _lib.check(getattr(_lib.load(), name)(*args, _lib.current_stream(dev)), name)
+    if lens is not None and check:
+        check_lengths_status(dev)
+
+
+def _info(lens, dev):
+    return None if lens is None else _lib.ptr(_status_word(dev))
+
+
+def _unbatch(batched, *xs):
+    """xs, without their leading batch axis for an unbatched call (None stays None)"""
+    return xs if batched else tuple(None if x is None else x[0] for x in xs)
+
+
+def _sample_shapes(num_samples, u, B, T, batched):
+    """S = num_samples as an int; ValueError for a count that is no integer >= 1, B S T labels that a 32-bit index
+    cannot address, or uniforms of another shape than (B,S,T) ((S,T) for the unbatched call)"""
+    S = int(num_samples)
+    if S != num_samples or S < 1:
+        raise ValueError("num_samples must be an integer >= 1, got %r" % (num_samples,))
+    if B * S * T >= 2 ** 31:
+        raise ValueError("B * num_samples * T = %d is not below 2^31" % (B * S * T))
+    if u is not None and _shape_of(u) != ((B, S, T) if batched else (S, T)):
+        raise ValueError("u must have shape %r, got %r" % ((B, S, T) if batched else (S, T), _shape_of(u)))
+    return S
+
+
+def _uniforms(u, generator, B, S, T, dev):
+    """the (B,S,T) float64 uniforms on dev: the caller's, or drawn there with `generator`"""
+    if u is None:
+        return torch.rand(B, S, T, dtype=torch.float64, device=dev, generator=generator)
+    return _dev64(u, dev).reshape(B, S, T)
+
+
+def _cotangents(cotangents, shapes, batched):
+    """[g_logZ, g_init, g_trans, g_states] of cotangents = (g_logZ, (g_init, g_trans, g_states)), each None or of its
+    shape in `shapes` (without the batch axis for an unbatched call): ValueError otherwise"""
+    g_logZ, (g_init, g_trans, g_states) = cotangents
+    cots = [g_logZ, g_init, g_trans, g_states]
+    for name, x, shape in zip(("g_logZ", "g_init", "g_trans", "g_states"), cots, shapes):
+        want = shape if batched else shape[1:]
+        if x is not None and _shape_of(x) != want:
+            raise ValueError("%s must have shape %r, got %r" % (name, want, _shape_of(x)))
+    return cots
+
+
+def hmm_estep(natparam, workspace=None, lengths=None, check=False):
+    B, T, K, batched, pair_batched = _shapes(natparam)
+    lens, dev, leaves = _on_device(natparam, lengths)
+    lib, p = _lib.load(), _lib.ptr
+    ws, wsb = _workspace(workspace, lib.svae_hmm_workspace_bytes, B, T, K, dev)
     f64 = dict(dtype=torch.float64, device=dev)
-    wsb = int(lib.svae_hmm_workspace_bytes(max(B, 1), T, K))
-    ws = workspace if workspace is not None else torch.empty(wsb // 8, **f64)
     logZ = torch.empty(B, **f64)
     E_init, E_trans, E_states = torch.empty(B, K, **f64), torch.empty(B, K, K, **f64), torch.empty(B, T, K, **f64)
-    p = _lib.ptr
+    model, out = (B, T, K, int(pair_batched), *map(p, leaves)), (p(logZ), p(E_init), p(E_trans), p(E_states))
     if lens is not None:
-        rc = lib.svae_hmm_ragged_estep_f64(B, T, K, int(pair_batched), p(init_params), p(pair_params), p(node), p(lens),
-                                           p(logZ), p(E_init), p(E_trans), p(E_states), p(_status_word(dev)), p(ws), wsb,
-                                           _lib.current_stream(dev))
-        _lib.check(rc, "svae_hmm_ragged_estep_f64")
-        if check:
-            check_lengths_status(dev)
-        return logZ, (E_init, E_trans, E_states)
-    rc = lib.svae_hmm_estep_f64(B, T, K, int(pair_batched), p(init_params), p(pair_params), p(node),
-                                p(logZ), p(E_init), p(E_trans), p(E_states), p(ws), wsb,
-                                _lib.current_stream(dev))
-    _lib.check(rc, "svae_hmm_estep_f64")
-    if not batched:
-        return logZ[0], (E_init[0], E_trans[0], E_states[0])
+        _call("svae_hmm_ragged_estep_f64", dev, lens, check, *model, p(lens), *out, _info(lens, dev), p(ws), wsb)
+    else:
+        _call("svae_hmm_estep_f64", dev, None, False, *model, *out, p(ws), wsb)
+    logZ, E_init, E_trans, E_states = _unbatch(batched, logZ, E_init, E_trans, E_states)
     return logZ, (E_init, E_trans, E_states)
 
 
@@ -154,49 +226,19 @@ def hmm_viterbi(natparam, workspace=None, return_score=False, lengths=None, chec
     order, ties to the lowest index -- labels and score are reproducible bit for bit.
     workspace: any contiguous device tensor of at least svae_hmm_viterbi_workspace_bytes(B,T,K) bytes.
     lengths: (B,) integers, see the module docstring -- labels from a sequence's length on are -1."""
-    init_params, pair_params, node_params = natparam
-    lens = None if lengths is None else _lengths_arg(lengths, node_params)
-    dev = node_params.device if isinstance(node_params, torch.Tensor) and node_params.is_cuda \
-        else torch.device("cuda", torch.cuda.current_device())
-    init_params, pair_params, node = (_dev64(x, dev) for x in (init_params, pair_params, node_params))
-    batched = node.dim() == 3
-    if node.dim() not in (2, 3):
-        raise ValueError("node_params must be (T,K) or (B,T,K)")
-    if not batched:
-        node = node[None]
-    B, T, K = node.shape
-    if not (1 <= K <= HMM_MAX_K):
-        raise ValueError("number of states K=%d outside 1..%d" % (K, HMM_MAX_K))
-    if T < 1:
-        raise ValueError("node_params has no steps")
-    pair_batched = pair_params.dim() == 3
-    if tuple(init_params.shape) != (K,) or tuple(pair_params.shape[-2:]) != (K, K) or pair_params.dim() not in (2, 3) or \
-            (pair_batched and pair_params.shape[0] != B):
-        raise ValueError("init/pair parameter shapes do not match the node potentials")
-    lib = _lib.load()
-    if workspace is None:
-        wsb = int(lib.svae_hmm_viterbi_workspace_bytes(max(B, 1), T, K))
-        ws = torch.empty(wsb, dtype=torch.uint8, device=dev)
-    else:
-        ws = workspace
-        wsb = ws.numel() * ws.element_size()
+    B, T, K, batched, pair_batched = _shapes(natparam)
+    lens, dev, leaves = _on_device(natparam, lengths)
+    lib, p = _lib.load(), _lib.ptr
+    ws, wsb = _workspace(workspace, lib.svae_hmm_viterbi_workspace_bytes, B, T, K, dev)
     states = torch.empty(B, T, dtype=torch.int32, device=dev)
     score = torch.empty(B, dtype=torch.float64, device=dev) if return_score else None
-    p = _lib.ptr
+    model = (B, T, K, int(pair_batched), *map(p, leaves))
     if lens is not None:
-        rc = lib.svae_hmm_ragged_viterbi_f64(B, T, K, int(pair_batched), p(init_params), p(pair_params), p(node), p(lens),
-                                             p(states), p(score), p(_status_word(dev)), p(ws), wsb,
-                                             _lib.current_stream(dev))
-        _lib.check(rc, "svae_hmm_ragged_viterbi_f64")
-        if check:
-            check_lengths_status(dev)
-        return (states, score) if return_score else states
-    rc = lib.svae_hmm_viterbi_f64(B, T, K, int(pair_batched), p(init_params), p(pair_params), p(node),
-                                  p(states), p(score), p(ws), wsb, _lib.current_stream(dev))
-    _lib.check(rc, "svae_hmm_viterbi_f64")
-    if not batched:
-        states = states[0]
-        score = score[0] if return_score else None
+        _call("svae_hmm_ragged_viterbi_f64", dev, lens, check, *model, p(lens), p(states), p(score), _info(lens, dev),
+              p(ws), wsb)
+    else:
+        _call("svae_hmm_viterbi_f64", dev, None, False, *model, p(states), p(score), p(ws), wsb)
+    states, score = _unbatch(batched, states, score)
     return (states, score) if return_score else states
 
 
@@ -212,61 +254,21 @@ def hmm_sample(natparam, num_samples=1, u=None, generator=None, workspace=None, 
     u: the uniforms, (B,S,T) ((S,T) for the unbatched call); None draws torch.rand fp64 on the device with `generator`.
     workspace: any contiguous device tensor of at least svae_hmm_sample_workspace_bytes(B,T,K) bytes.
     lengths: (B,) integers, see the module docstring -- labels from a sequence's length on are -1."""
-    init_params, pair_params, node_params = natparam
-    lens = None if lengths is None else _lengths_arg(lengths, node_params)
-    dev = node_params.device if isinstance(node_params, torch.Tensor) and node_params.is_cuda \
-        else torch.device("cuda", torch.cuda.current_device())
-    init_params, pair_params, node = (_dev64(x, dev) for x in (init_params, pair_params, node_params))
-    batched = node.dim() == 3
-    if node.dim() not in (2, 3):
-        raise ValueError("node_params must be (T,K) or (B,T,K)")
-    if not batched:
-        node = node[None]
-    B, T, K = node.shape
-    if not (1 <= K <= HMM_MAX_K):
-        raise ValueError("number of states K=%d outside 1..%d" % (K, HMM_MAX_K))
-    if T < 1:
-        raise ValueError("node_params has no steps")
-    pair_batched = pair_params.dim() == 3
-    if tuple(init_params.shape) != (K,) or tuple(pair_params.shape[-2:]) != (K, K) or pair_params.dim() not in (2, 3) or \
-            (pair_batched and pair_params.shape[0] != B):
-        raise ValueError("init/pair parameter shapes do not match the node potentials")
-    S = int(num_samples)
-    if S != num_samples or S < 1:
-        raise ValueError("num_samples must be an integer >= 1, got %r" % (num_samples,))
-    if B * S * T >= 2 ** 31:
-        raise ValueError("B * num_samples * T = %d is not below 2^31" % (B * S * T))
-    if u is None:
-        u = torch.rand(B, S, T, dtype=torch.float64, device=dev, generator=generator)
-    else:
-        ushape = tuple(u.shape) if hasattr(u, "shape") else np.shape(u)
-        if ushape != ((B, S, T) if batched else (S, T)):
-            raise ValueError("u must have shape %r, got %r" % ((B, S, T) if batched else (S, T), ushape))
-        u = _dev64(u, dev).reshape(B, S, T)
-    lib = _lib.load()
-    if workspace is None:
-        wsb = int(lib.svae_hmm_sample_workspace_bytes(max(B, 1), T, K))
-        ws = torch.empty(wsb // 8, dtype=torch.float64, device=dev)
-    else:
-        ws = workspace
-        wsb = ws.numel() * ws.element_size()
+    B, T, K, batched, pair_batched = _shapes(natparam)
+    S = _sample_shapes(num_samples, u, B, T, batched)
+    lens, dev, leaves = _on_device(natparam, lengths)
+    u = _uniforms(u, generator, B, S, T, dev)
+    lib, p = _lib.load(), _lib.ptr
+    ws, wsb = _workspace(workspace, lib.svae_hmm_sample_workspace_bytes, B, T, K, dev)
     states = torch.empty(B, S, T, dtype=torch.int32, device=dev)
     logZ = torch.empty(B, dtype=torch.float64, device=dev) if return_logZ else None
-    p = _lib.ptr
+    model = (B, T, K, S, int(pair_batched), *map(p, leaves))
     if lens is not None:
-        rc = lib.svae_hmm_ragged_sample_f64(B, T, K, S, int(pair_batched), p(init_params), p(pair_params), p(node),
-                                            p(lens), p(u), p(states), p(logZ), p(_status_word(dev)), p(ws), wsb,
-                                            _lib.current_stream(dev))
-        _lib.check(rc, "svae_hmm_ragged_sample_f64")
-        if check:
-            check_lengths_status(dev)
-        return (states, logZ) if return_logZ else states
-    rc = lib.svae_hmm_sample_f64(B, T, K, S, int(pair_batched), p(init_params), p(pair_params), p(node), p(u),
-                                 p(states), p(logZ), p(ws), wsb, _lib.current_stream(dev))
-    _lib.check(rc, "svae_hmm_sample_f64")
-    if not batched:
-        states = states[0]
-        logZ = logZ[0] if return_logZ else None
+        _call("svae_hmm_ragged_sample_f64", dev, lens, check, *model, p(lens), p(u), p(states), p(logZ),
+              _info(lens, dev), p(ws), wsb)
+    else:
+        _call("svae_hmm_sample_f64", dev, None, False, *model, p(u), p(states), p(logZ), p(ws), wsb)
+    states, logZ = _unbatch(batched, states, logZ)
     return (states, logZ) if return_logZ else states
 
 
@@ -315,61 +317,20 @@ def hmm_estep_vjp(natparam, cotangents, workspace=None, lengths=None, check=Fals
     potentials --; a shared init or pair parameter's gradient is their sum over the batch.
     workspace: a contiguous float64 device tensor of at least svae_hmm_estep_vjp_workspace_bytes(B,T,K) bytes; afterwards
     vjp_redone_sequences(workspace, B, T, K) says which sequences took the log-space route."""
-    init_params, pair_params, node_params = natparam
-    lens = None if lengths is None else _lengths_arg(lengths, node_params)
-    dev = node_params.device if isinstance(node_params, torch.Tensor) and node_params.is_cuda \
-        else torch.device("cuda", torch.cuda.current_device())
-    init_params, pair_params, node = (_dev64(x, dev) for x in (init_params, pair_params, node_params))
-    batched = node.dim() == 3
-    if node.dim() not in (2, 3):
-        raise ValueError("node_params must be (T,K) or (B,T,K)")
-    if not batched:
-        node = node[None]
-    B, T, K = node.shape
-    if not (1 <= K <= HMM_MAX_K):
-        raise ValueError("number of states K=%d outside 1..%d" % (K, HMM_MAX_K))
-    if T < 1:
-        raise ValueError("node_params has no steps")
-    pair_batched = pair_params.dim() == 3
-    if tuple(init_params.shape) != (K,) or tuple(pair_params.shape[-2:]) != (K, K) or pair_params.dim() not in (2, 3) or \
-            (pair_batched and pair_params.shape[0] != B):
-        raise ValueError("init/pair parameter shapes do not match the node potentials")
-    g_logZ, (g_init, g_trans, g_states) = cotangents
-    cots = []
-    for name, x, shape in (("g_logZ", g_logZ, (B,)), ("g_init", g_init, (B, K)), ("g_trans", g_trans, (B, K, K)),
-                           ("g_states", g_states, (B, T, K))):
-        if x is not None:
-            want = shape if batched else shape[1:]
-            if tuple(x.shape) != want:
-                raise ValueError("%s must have shape %r, got %r" % (name, want, tuple(x.shape)))
-            x = _dev64(x, dev).reshape(shape)
-        cots.append(x)
-    lib = _lib.load()
+    B, T, K, batched, pair_batched = _shapes(natparam)
+    cots = _cotangents(cotangents, ((B,), (B, K), (B, K, K), (B, T, K)), batched)
+    lens, dev, leaves = _on_device(natparam, lengths)
+    cots = [None if x is None else _dev64(x, dev) for x in cots]
+    lib, p = _lib.load(), _lib.ptr
+    ws, wsb = _workspace(workspace, lib.svae_hmm_estep_vjp_workspace_bytes, B, T, K, dev)
     f64 = dict(dtype=torch.float64, device=dev)
-    wsb = int(lib.svae_hmm_estep_vjp_workspace_bytes(max(B, 1), T, K))
-    if workspace is None:
-        ws = torch.empty(wsb // 8, **f64)
-    else:
-        ws = workspace
-        wsb = ws.numel() * ws.element_size()
     d_init, d_pair, d_node = torch.empty(B, K, **f64), torch.empty(B, K, K, **f64), torch.empty(B, T, K, **f64)
-    p = _lib.ptr
+    model, grads = (B, T, K, int(pair_batched), *map(p, leaves)), (*map(p, cots), p(d_init), p(d_pair), p(d_node))
     if lens is not None:
-        rc = lib.svae_hmm_ragged_estep_vjp_f64(B, T, K, int(pair_batched), p(init_params), p(pair_params), p(node), p(lens),
-                                               p(cots[0]), p(cots[1]), p(cots[2]), p(cots[3]),
-                                               p(d_init), p(d_pair), p(d_node), p(_status_word(dev)), p(ws), wsb,
-                                               _lib.current_stream(dev))
-        _lib.check(rc, "svae_hmm_ragged_estep_vjp_f64")
-        if check:
-            check_lengths_status(dev)
-        return d_init, d_pair, d_node
-    rc = lib.svae_hmm_estep_vjp_f64(B, T, K, int(pair_batched), p(init_params), p(pair_params), p(node),
-                                    p(cots[0]), p(cots[1]), p(cots[2]), p(cots[3]),
-                                    p(d_init), p(d_pair), p(d_node), p(ws), wsb, _lib.current_stream(dev))
-    _lib.check(rc, "svae_hmm_estep_vjp_f64")
-    if not batched:
-        return d_init[0], d_pair[0], d_node[0]
-    return d_init, d_pair, d_node
+        _call("svae_hmm_ragged_estep_vjp_f64", dev, lens, check, *model, p(lens), *grads, _info(lens, dev), p(ws), wsb)
+    else:
+        _call("svae_hmm_estep_vjp_f64", dev, None, False, *model, *grads, p(ws), wsb)
+    return _unbatch(batched, d_init, d_pair, d_node)
 
 
 def vjp_redone_sequences(workspace, B, T, K):
@@ -428,23 +389,11 @@ def hmm_estep_differentiable(natparam, lengths=None, check=False):
 
 
 # ---- per-step transition potentials (svae_hmm_perstep_estep_f64, csrc/hmm_estep_perstep.hip) --------------------------------
-def _shape_of(x):
-    return tuple(x.shape) if hasattr(x, "shape") else np.shape(x)
-
-
 def _perstep_shapes(natparam):
     """(B, T, K, batched, pair_batched) of a per-step natparam, from shapes alone: every refusal is a ValueError raised
     before anything is converted, copied or launched."""
     init_s, pair_s, node_s = (_shape_of(x) for x in natparam)
-    if len(node_s) not in (2, 3):
-        raise ValueError("node_params must be (T,K) or (B,T,K)")
-    batched = len(node_s) == 3
-    B = node_s[0] if batched else 1
-    T, K = node_s[-2:]
-    if not (1 <= K <= HMM_MAX_K):
-        raise ValueError("number of states K=%d outside 1..%d" % (K, HMM_MAX_K))
-    if T < 1:
-        raise ValueError("node_params has no steps")
+    B, T, K, batched = _node_shape(node_s)
     if init_s != (K,):
         raise ValueError("init_params must have shape (K,) = (%d,), got %r" % (K, init_s))
     if len(pair_s) not in (3, 4):
@@ -472,32 +421,16 @@ def hmm_estep_perstep(natparam, workspace=None, lengths=None, check=False, want_
     lengths: (B,) integers, see the module docstring -- E_states[b, L:] and E_trans[b, L-1:] are exactly 0, and neither
     node[b, L:] nor pair[b, L-1:] is read."""
     B, T, K, batched, pair_batched = _perstep_shapes(natparam)
-    init_params, pair_params, node_params = natparam
-    lens = None if lengths is None else _lengths_arg(lengths, node_params)
-    dev = node_params.device if isinstance(node_params, torch.Tensor) and node_params.is_cuda \
-        else torch.device("cuda", torch.cuda.current_device())
-    init_params, pair_params, node = (_dev64(x, dev) for x in (init_params, pair_params, node_params))
-    lib = _lib.load()
+    lens, dev, leaves = _on_device(natparam, lengths)
+    lib, p = _lib.load(), _lib.ptr
+    ws, wsb = _workspace(workspace, lib.svae_hmm_perstep_workspace_bytes, B, T, K, dev)
     f64 = dict(dtype=torch.float64, device=dev)
-    if workspace is None:
-        wsb = int(lib.svae_hmm_perstep_workspace_bytes(max(B, 1), T, K))
-        ws = torch.empty(wsb // 8, **f64)
-    else:
-        ws = workspace
-        wsb = ws.numel() * ws.element_size()
     logZ = torch.empty(B, **f64)
     E_init, E_states = torch.empty(B, K, **f64), torch.empty(B, T, K, **f64)
     E_trans = torch.empty(B, T - 1, K, K, **f64) if want_trans else None
-    p = _lib.ptr
-    rc = lib.svae_hmm_perstep_estep_f64(B, T, K, int(pair_batched), p(init_params), p(pair_params), p(node), p(lens),
-                                        p(logZ), p(E_init), p(E_trans), p(E_states),
-                                        p(_status_word(dev)) if lens is not None else None, p(ws), wsb,
-                                        _lib.current_stream(dev))
-    _lib.check(rc, "svae_hmm_perstep_estep_f64")
-    if lens is not None and check:
-        check_lengths_status(dev)
-    if not batched:
-        return logZ[0], (E_init[0], None if E_trans is None else E_trans[0], E_states[0])
+    _call("svae_hmm_perstep_estep_f64", dev, lens, check, B, T, K, int(pair_batched), *map(p, leaves), p(lens),
+          p(logZ), p(E_init), p(E_trans), p(E_states), _info(lens, dev), p(ws), wsb)
+    logZ, E_init, E_trans, E_states = _unbatch(batched, logZ, E_init, E_trans, E_states)
     return logZ, (E_init, E_trans, E_states)
 
 
@@ -558,36 +491,17 @@ def hmm_estep_perstep_vjp(natparam, cotangents, workspace=None, lengths=None, ch
     lengths: (B,) integers -- the gradient of every sequence cut to its length; d_node[b, L:] and d_pair[b, L-1:] are
     exactly 0, and nothing of the potentials or cotangents from there on is read."""
     B, T, K, batched, pair_batched = _perstep_shapes(natparam)
-    g_logZ, (g_init, g_trans, g_states) = cotangents
-    for name, x, shape in (("g_logZ", g_logZ, (B,)), ("g_init", g_init, (B, K)), ("g_trans", g_trans, (B, T - 1, K, K)),
-                           ("g_states", g_states, (B, T, K))):
-        want = shape if batched else shape[1:]
-        if x is not None and _shape_of(x) != want:
-            raise ValueError("%s must have shape %r, got %r" % (name, want, _shape_of(x)))
-    lens, dev = _perstep_device(natparam, lengths)
-    init_params, pair_params, node = (_dev64(x, dev) for x in natparam)
-    cots = [None if x is None else _dev64(x, dev) for x in (g_logZ, g_init, g_trans, g_states)]
-    lib = _lib.load()
+    cots = _cotangents(cotangents, ((B,), (B, K), (B, T - 1, K, K), (B, T, K)), batched)
+    lens, dev, leaves = _on_device(natparam, lengths)
+    cots = [None if x is None else _dev64(x, dev) for x in cots]
+    lib, p = _lib.load(), _lib.ptr
+    ws, wsb = _workspace(workspace, lib.svae_hmm_perstep_estep_vjp_workspace_bytes, B, T, K, dev)
     f64 = dict(dtype=torch.float64, device=dev)
-    if workspace is None:
-        wsb = int(lib.svae_hmm_perstep_estep_vjp_workspace_bytes(max(B, 1), T, K))
-        ws = torch.empty(wsb // 8, **f64)
-    else:
-        ws = workspace
-        wsb = ws.numel() * ws.element_size()
     d_init, d_node = torch.empty(B, K, **f64), torch.empty(B, T, K, **f64)
     d_pair = torch.empty(B, T - 1, K, K, **f64) if want_pair else None
-    p = _lib.ptr
-    rc = lib.svae_hmm_perstep_estep_vjp_f64(B, T, K, int(pair_batched), p(init_params), p(pair_params), p(node), p(lens),
-                                            p(cots[0]), p(cots[1]), p(cots[2]), p(cots[3]), p(d_init), p(d_pair), p(d_node),
-                                            p(_status_word(dev)) if lens is not None else None, p(ws), wsb,
-                                            _lib.current_stream(dev))
-    _lib.check(rc, "svae_hmm_perstep_estep_vjp_f64")
-    if lens is not None and check:
-        check_lengths_status(dev)
-    if not batched:
-        return d_init[0], None if d_pair is None else d_pair[0], d_node[0]
-    return d_init, d_pair, d_node
+    _call("svae_hmm_perstep_estep_vjp_f64", dev, lens, check, B, T, K, int(pair_batched), *map(p, leaves), p(lens),
+          *map(p, cots), p(d_init), p(d_pair), p(d_node), _info(lens, dev), p(ws), wsb)
+    return _unbatch(batched, d_init, d_pair, d_node)
 
 
 class _HMMEStepPerstep(torch.autograd.Function):
@@ -634,15 +548,6 @@ def hmm_estep_perstep_differentiable(natparam, lengths=None, check=False):
     return logZ, (E_init, E_trans, E_states)
 
 
-def _perstep_device(natparam, lengths):
-    """(lens, dev) of a per-step call whose shapes have been accepted: the validated (B,) int32 lengths or None, the device"""
-    node_params = natparam[2]
-    lens = None if lengths is None else _lengths_arg(lengths, node_params)
-    dev = node_params.device if isinstance(node_params, torch.Tensor) and node_params.is_cuda \
-        else torch.device("cuda", torch.cuda.current_device())
-    return lens, dev
-
-
 def hmm_viterbi_perstep(natparam, workspace=None, return_score=False, lengths=None, check=False):
     """hmm_viterbi for the natparam hmm_estep_perstep takes -- init (K), pair (T-1,K,K) or (B,T-1,K,K), node (T,K) or
     (B,T,K), LOG potentials, finite or -inf: labels torch.int32 (T,) or (B,T); with return_score also the path's score
@@ -652,27 +557,14 @@ def hmm_viterbi_perstep(natparam, workspace=None, return_score=False, lengths=No
     lengths: (B,) integers, see the module docstring -- labels from a sequence's length on are -1, and neither node[b, L:]
     nor pair[b, L-1:] is read."""
     B, T, K, batched, pair_batched = _perstep_shapes(natparam)
-    lens, dev = _perstep_device(natparam, lengths)
-    init_params, pair_params, node = (_dev64(x, dev) for x in natparam)
-    lib = _lib.load()
-    if workspace is None:
-        wsb = int(lib.svae_hmm_viterbi_workspace_bytes(max(B, 1), T, K))
-        ws = torch.empty(wsb, dtype=torch.uint8, device=dev)
-    else:
-        ws = workspace
-        wsb = ws.numel() * ws.element_size()
+    lens, dev, leaves = _on_device(natparam, lengths)
+    lib, p = _lib.load(), _lib.ptr
+    ws, wsb = _workspace(workspace, lib.svae_hmm_viterbi_workspace_bytes, B, T, K, dev)
     states = torch.empty(B, T, dtype=torch.int32, device=dev)
     score = torch.empty(B, dtype=torch.float64, device=dev) if return_score else None
-    p = _lib.ptr
-    rc = lib.svae_hmm_perstep_viterbi_f64(B, T, K, int(pair_batched), p(init_params), p(pair_params), p(node), p(lens),
-                                          p(states), p(score), p(_status_word(dev)) if lens is not None else None,
-                                          p(ws), wsb, _lib.current_stream(dev))
-    _lib.check(rc, "svae_hmm_perstep_viterbi_f64")
-    if lens is not None and check:
-        check_lengths_status(dev)
-    if not batched:
-        states = states[0]
-        score = score[0] if return_score else None
+    _call("svae_hmm_perstep_viterbi_f64", dev, lens, check, B, T, K, int(pair_batched), *map(p, leaves), p(lens),
+          p(states), p(score), _info(lens, dev), p(ws), wsb)
+    states, score = _unbatch(batched, states, score)
     return (states, score) if return_score else states
 
 
@@ -688,36 +580,14 @@ def hmm_sample_perstep(natparam, num_samples=1, u=None, generator=None, workspac
     lengths: (B,) integers, see the module docstring -- labels from a sequence's length on are -1, and none of node[b, L:],
     pair[b, L-1:] and u[b, :, L:] is read."""
     B, T, K, batched, pair_batched = _perstep_shapes(natparam)
-    S = int(num_samples)
-    if S != num_samples or S < 1:
-        raise ValueError("num_samples must be an integer >= 1, got %r" % (num_samples,))
-    if B * S * T >= 2 ** 31:
-        raise ValueError("B * num_samples * T = %d is not below 2^31" % (B * S * T))
-    if u is not None and _shape_of(u) != ((B, S, T) if batched else (S, T)):
-        raise ValueError("u must have shape %r, got %r" % ((B, S, T) if batched else (S, T), _shape_of(u)))
-    lens, dev = _perstep_device(natparam, lengths)
-    init_params, pair_params, node = (_dev64(x, dev) for x in natparam)
-    if u is None:
-        u = torch.rand(B, S, T, dtype=torch.float64, device=dev, generator=generator)
-    else:
-        u = _dev64(u, dev).reshape(B, S, T)
-    lib = _lib.load()
-    if workspace is None:
-        wsb = int(lib.svae_hmm_perstep_workspace_bytes(max(B, 1), T, K))
-        ws = torch.empty(wsb // 8, dtype=torch.float64, device=dev)
-    else:
-        ws = workspace
-        wsb = ws.numel() * ws.element_size()
+    S = _sample_shapes(num_samples, u, B, T, batched)
+    lens, dev, leaves = _on_device(natparam, lengths)
+    u = _uniforms(u, generator, B, S, T, dev)
+    lib, p = _lib.load(), _lib.ptr
+    ws, wsb = _workspace(workspace, lib.svae_hmm_perstep_workspace_bytes, B, T, K, dev)
     states = torch.empty(B, S, T, dtype=torch.int32, device=dev)
     logZ = torch.empty(B, dtype=torch.float64, device=dev) if return_logZ else None
-    p = _lib.ptr
-    rc = lib.svae_hmm_perstep_sample_f64(B, T, K, S, int(pair_batched), p(init_params), p(pair_params), p(node), p(lens),
-                                         p(u), p(states), p(logZ), p(_status_word(dev)) if lens is not None else None,
-                                         p(ws), wsb, _lib.current_stream(dev))
-    _lib.check(rc, "svae_hmm_perstep_sample_f64")
-    if lens is not None and check:
-        check_lengths_status(dev)
-    if not batched:
-        states = states[0]
-        logZ = logZ[0] if return_logZ else None
+    _call("svae_hmm_perstep_sample_f64", dev, lens, check, B, T, K, S, int(pair_batched), *map(p, leaves), p(lens),
+          p(u), p(states), p(logZ), _info(lens, dev), p(ws), wsb)
+    states, logZ = _unbatch(batched, states, logZ)
     return (states, logZ) if return_logZ else states
