@@ -10,7 +10,16 @@ runs with homogeneous parameters, where the pair gradients must be exact zeros.
 Models come from `rand_lds_natparam`, redrawn while cond(init_J) or cond(J22) exceeds MAX_COND = 1e6 (below: what fp64
 resolves at the 1e-6 bound; an input-only criterion).
 Also: central finite differences of the HIP forward itself, the structural identities between the gradients, bit-exactness
-against the default call, and the error paths."""
+against the default call, and the error paths.
+The SHAPES here stop at B = 5, T = 7 and the default options word.  Tested elsewhere:
+  * every launch route of launch_vjp's PGR forms (B around 512 / 1024 / 2048, n = 13, S = 5 and 17, the producer bits of
+    the options word, the statistics cotangents, every forward variant), every edge of the reduction kernels (a second
+    term per chunk, the wrap of the four interleaved sums, the time pass, the entry tiling) and the slab loop at
+    B (T-1) > 65535, all against this file's oracle: tests/test_lds_param_grads_routes_hip.py;
+  * the parameter gradients against the 60-digit truth of oracle/lds_mp on the ill-conditioned draws:
+    tests/test_lds_truth_hip.py::test_param_gradients_against_truth;
+  * this file's oracle itself (torch_estep's fp64 autograd) against that truth, every coordinate, without a GPU:
+    tests/test_lds_param_grads_cpu.py."""
 import functools
 
 import numpy as np

@@ -10,7 +10,9 @@ the HIP kernel is still more than 3x further from the truth than the reference (
 Every model is handed over with exactly symmetric J0, J11, J22 (_symmetric_model).  Gradients are checked through
 <VJP(g), v> = <g, J v>: J v by
 oracle.lds_mp.jvp_mp (a central difference inside mp) at the coordinates where the fp64 sides disagree most and along a
-random direction; the node-h gradient of the E-step has a closed form (one more solve)."""
+random direction; the node-h gradient of the E-step has a closed form (one more solve).  The gradients w.r.t. the init and
+pair natural parameters (natparam_grad=True) have no compiled reference: their comparator is the fp64 CPU autograd of
+tests/_lds_large_torch.torch_estep (test_param_gradients_against_truth)."""
 import functools
 
 import numpy as np
@@ -35,7 +37,7 @@ FLOOR = 1e-11
 
 # Pins: measured HIP-vs-truth on MI355X x 3, rounded up.  Case keys: ("estep", draw, variant) -- B-independent: the
 # replicated draw at B = 513 / 1100 measures as B = 1 --, ("inference", B, accurate), ("tile", draw), ("host", entry),
-# ("vjp", draw, accurate, sampler), ("prim", kind, n, form), ("prim262", kind).
+# ("vjp", draw, accurate, sampler), ("prim", kind, n, form), ("prim262", kind), ("pgrad", draw, layout).
 # cond^2 * eps BY DESIGN (the lean [P^-1 | c] records), worst output array of the case: the
 # two-ended lean E-step variants from cond(J22) 2.6e5 on, the training forward below 1025 sequences, the default-mode VJP.
 LEAN_PINS = {
@@ -49,7 +51,7 @@ LEAN_PINS = {
     ("vjp", "n8_s116", False, False): 0.07, ("vjp", "n8_s116", False, True): 0.07,
 }
 # Output arrays of cond * eps paths that miss `<= max(3 x reference, 1e-11)`, pinned per array (every other array of the
-# case still meets the rule).  Open gaps, all within 3e-10 of the truth: the lognorm of the accurate E-step at
+# case still meets the rule).  Open gaps, all but the ("pgrad", ..) ones within 3e-10 of the truth: the lognorm of the accurate E-step at
 # cond(J22) = 2.2e9 (4.7x the reference's 3.8e-11), E_pair xx / xnxn at n = 10, T = 200 (3.5-6x the reference's 1.4e-11),
 # the n = 16 tile E-step (E[x] 4.9e-11 against 2.0e-12 .. 9.3e-12), two sampler-VJP cases at 1.1e-11 / 1.3e-11 (the
 # reference 1.5e-12 / 2.0e-12).  DESIGN sections 2 and 4.2b.
@@ -63,6 +65,18 @@ GAP_PINS = {
     ("tile", "n16_s207"): {"ExxT0": 1.4e-10, "Ex0": 1.5e-10, "Epair_xxn": 2e-10, "Enode_x": 1.5e-10, "sample0": 1.5e-10},
     ("prim", "sampler", 10, "inhomog"): {"grad": 3.3e-11},
     ("prim", "sampler", 15, "batched"): {"grad": 3.9e-11},
+    # The parameter gradients (natparam_grad=True; key ("pgrad", draw, layout)) run on the FULL per-step records in either
+    # mode -- a plan made for them has the [chol(P)^-T | c] records of set_accurate_smoother switched off, and only the packed
+    # sweep 2 on full records writes their blocks -- so from cond(J22) 2.6e5 on they are where the default-mode node gradients
+    # are (LEAN_PINS ("vjp", ..)): cond^2 * eps.  Open; the comparator (fp64 CPU autograd) is at 2e-13 .. 3e-13 on n7_s1,
+    # 8e-11 .. 9e-10 on n7_s262, 1e-9 .. 6e-9 on n8_s116 ("Parameter gradients: routes, edges, truth").
+    ("pgrad", "n7_s1", "homog"): {"J11": 2.2e-10, "J12": 6.9e-10, "J22": 2.2e-10},
+    ("pgrad", "n7_s262", "homog"): {"init_J": 5.5e-4, "init_h": 1.2e-4, "J11": 4e-4, "J12": 4e-4, "J22": 3.7e-4,
+                                    "random": 2.3e-5},
+    ("pgrad", "n8_s116", "homog"): {"init_J": 0.07, "init_h": 0.044, "J11": 0.073, "J12": 0.096, "J22": 0.07,
+                                    "random": 2.2e-3},
+    ("pgrad", "n7_s262", "homog_zero_noise"): {"init_J": 3.7e-4, "init_h": 9.2e-5, "J11": 3.3e-4, "J12": 3.7e-4,
+                                               "J22": 3.1e-4, "random": 2e-5},
 }
 
 
@@ -350,13 +364,14 @@ def _worst_seq(hip, want):
     return int(np.argmax([max(_dist(h[b], w[b]) for h, w in zip(hip, want)) for b in range(B)]))
 
 
-def _grad_truth(f, args, place, inner, hip, want, sym, rng, per_array):
+def _grad_truth(f, args, place, inner, hip, want, sym, rng, per_array, per_direction=False):
     """(HIP-vs-truth, reference-vs-truth) of gradient arrays of one sequence.  `place(vs)` puts direction arrays vs (one per
     gradient array) into f's argument structure; `inner(d)` = <g, J v> for jvp_mp's output d.  Arrays flagged in `sym` are
     gradients w.r.t. symmetric matrices: their directions are symmetric (E_ij + E_ji), so either convention of splitting
     the gradient between G_ij and G_ji pairs correctly.  Directions: the coordinate of largest normwise |HIP - reference|
     of each array (per_array) or of all arrays, then one random direction over all arrays; a coordinate gives
-    |a_k - truth_k| / max|truth|, the random direction a lower bound of the normwise distance."""
+    |a_k - truth_k| / max|truth|, the random direction a lower bound of the normwise distance.  per_direction=True (with
+    per_array): the pair of distances of every direction -- one per array, then the random one -- instead of their maxima."""
     hip = [np.asarray(a, float) for a in hip]
     want = [np.asarray(a, float) for a in want]
     view = lambda G, s: _sym(G) if s else G
@@ -373,12 +388,12 @@ def _grad_truth(f, args, place, inner, hip, want, sym, rng, per_array):
     rnd = [rng.standard_normal(w.shape) for w in want]
     rnd = [(r + np.swapaxes(r, -1, -2)) / 2 if s else r for r, s in zip(rnd, sym)]
     dirs.append((rnd, sum(sc * float(np.abs(r).sum()) for sc, r in zip(scale, rnd))))
-    out_h = out_w = 0.0
+    each = []
     for vs, norm in dirs:
         t = inner(lds_mp.jvp_mp(f, args, place(vs)))
         dot = lambda G: sum(float(np.sum(g * v)) for g, v in zip(G, vs))
-        out_h, out_w = max(out_h, abs(dot(hip) - t) / norm), max(out_w, abs(dot(want) - t) / norm)
-    return out_h, out_w
+        each.append((abs(dot(hip) - t) / norm, abs(dot(want) - t) / norm))
+    return each if per_direction else (max(h for h, _ in each), max(w for _, w in each))
 
 
 def _filter_run(n, T, B, form):
@@ -573,6 +588,101 @@ def seed262_primitive_case(kind):
 def test_primitive_vjp_seed262_against_truth(kind):
     hip, want = seed262_primitive_case(kind)
     _judge(("prim262", kind), {"grad": hip}, {"grad": want})
+
+
+# ------------------------------------------------------------------------ gradients w.r.t. the init / pair natural parameters
+# lds_inference_differentiable(..., natparam_grad=True).  The reference has no compiled parameter gradient: the comparator is
+# the fp64 CPU autograd of tests/_lds_large_torch.torch_estep (the oracle of tests/test_lds_param_grads_hip.py and
+# tests/test_lds_param_grads_routes_hip.py; pinned to 60 digits on small shapes by tests/test_lds_param_grads_cpu.py).
+
+PGRAD_NAMES = ("init_J", "init_h", "init_logZ", "J11", "J12", "J22", "logZ_pair")
+PGRAD_SYM = (True, False, False, True, False, True, False)
+PGRAD_STEP_T = 12
+
+
+def _param_grads(init, pair, node, cot, sampler, hip):
+    """the seven parameter gradients of g_l lognorm + <g_d, diag E[xx']> + <g_x, E[x]> [+ <g_s, sample at zero noise>] by
+    autograd through the HIP path (hip) or through torch_estep in fp64 on the CPU, as NumPy arrays"""
+    import _lds_large_torch as lt
+    from svae_amd.lds import lds_inference as li
+    g_l, g_d, g_x, g_s = cot
+    T, n = node[1].shape[1:]
+    t = lambda x: torch.as_tensor(np.asarray(x, float), dtype=torch.float64, device="cuda" if hip else "cpu")
+    P = [t(x).requires_grad_(True) for x in tuple(init[:3]) + tuple(pair[:4])]
+    eps = t(np.zeros((1, T, 1, n))) if sampler else None
+    if hip:
+        ln, (dxx, x), smp, _ = li.lds_inference_differentiable(((P[0], P[1], P[2]), tuple(P[3:])), tuple(t(a) for a in node),
+                                                               eps=eps, natparam_grad=True)
+    else:
+        ln, dxx, x, smp, _, _ = lt.torch_estep((P[0], P[1], P[2].reshape(1), P[3], P[4], P[5], P[6].reshape(-1)),
+                                               t(node[0]), t(node[1]), eps=eps)
+    loss = (ln * g_l).sum() + (dxx * t(g_d)[None]).sum() + (x * t(g_x)[None]).sum()
+    if sampler:
+        loss = loss + (smp[:, :, 0] * t(g_s)[None]).sum()
+    loss.backward()
+    return [np.zeros(tuple(p.shape)) if p.grad is None else _np(p.grad) for p in P]
+
+
+def _param_truth(init, pair, node, cot, sampler, hip, want, rng):
+    """{array: (HIP-vs-truth, comparator-vs-truth)} + "random": eight jvp_mp evaluations of estep_mp -- per array the
+    coordinate where HIP and the comparator part most, then one random direction over all seven.  A sample at zero noise is
+    E[x] (x_t = c_t + G_t x_{t+1}) and chol(P_t)^-T eps_t has no derivative at eps = 0: its truth is that of E[x]."""
+    g_l, g_d, g_x, g_s = cot
+    gx = g_x + g_s if sampler else g_x
+    inner = lambda d: g_l * float(d[0]) + float(np.sum(g_d * d[1][2][0])) + float(np.sum(gx * d[1][2][1]))
+    place = lambda vs: ((tuple(vs[:3]), tuple(vs[3:])), None)
+    each = _grad_truth(lds_mp.estep_mp, ((init, pair), (node[0][0], node[1][0])), place, inner, hip, want, PGRAD_SYM, rng,
+                       True, per_direction=True)
+    return dict(zip(PGRAD_NAMES + ("random",), each))
+
+
+def param_grad_case(key, layout, accurate=True):
+    """{array: (HIP-vs-truth, comparator-vs-truth)} of the seven parameter gradients of a random cotangent on (lognorm,
+    diag E[xx'], E[x]) on draw `key`.  layout "homog"; "homog_zero_noise": with the sampler at zero noise and a cotangent
+    on its sample too; "step": the draw cut to T = 12 with the homogeneous blocks repeated per step (T-1,n,n) -- the
+    per-step truth from jvp_mp on those arrays, and ("sum_" entries) the HIP gradient summed over t against the
+    homogeneous truth."""
+    from svae_amd.lds import lds_inference as li
+    n, T, seed = DRAWS[key]
+    init, pair, node = _draw(n, T, seed)
+    init, pair = tuple(init[:3]), tuple(np.asarray(x, float) for x in pair[:4])
+    sampler = layout == "homog_zero_noise"
+    if layout == "step":
+        T = PGRAD_STEP_T
+        node = tuple(x[:, :T] for x in node)
+    rng = np.random.default_rng(2000 + seed)
+    cot = (float(rng.standard_normal()), rng.standard_normal((T, n)), rng.standard_normal((T, n)), rng.standard_normal((T, n)))
+    models = [pair]
+    if layout == "step":
+        models.insert(0, tuple(np.repeat(x[None], T - 1, axis=0) for x in pair))
+    old = li.set_accurate_smoother(accurate)
+    try:
+        hip = _param_grads(init, models[0], node, cot, sampler, True)
+    finally:
+        li.set_default_options(old)
+    out = _param_truth(init, models[0], node, cot, sampler, hip, _param_grads(init, models[0], node, cot, sampler, False), rng)
+    if layout == "step":
+        summed = hip[:3] + [a.sum(0) for a in hip[3:]]
+        total = _param_truth(init, pair, node, cot, sampler, summed, _param_grads(init, pair, node, cot, sampler, False), rng)
+        out.update(("sum_" + k, v) for k, v in total.items())
+    return out
+
+
+PGRAD_CASES = [(key, "homog", accurate) for key in ("n7_s0", "n7_s1", "n7_s262", "n8_s116") for accurate in (True, False)] \
+    + [("n7_s262", "homog_zero_noise", True), ("n7_s1", "step", True)]
+
+
+@pytest.mark.parametrize("key,layout,accurate", PGRAD_CASES)
+def test_param_gradients_against_truth(key, layout, accurate):
+    """accurate mode: every array meets the cond * eps rule (or its GAP_PINS entry under ("pgrad", draw, layout)).  The
+    default mode is cond^2 * eps by design: the rule is applied on n7_s0 only, the other draws are printed (PGTRUTH).
+    Measured on MI355X: the two modes return the same figures on all four draws -- natparam_grad=True runs on the full
+    records either way (GAP_PINS)."""
+    d = param_grad_case(key, layout, accurate)
+    print("PGTRUTH %s %s %s: " % (key, layout, "accurate" if accurate else "default")
+          + ", ".join("%s %.2e|%.2e" % (k, h, w) for k, (h, w) in d.items()))
+    if accurate or key == "n7_s0":
+        _judge(("pgrad", key, layout), {k: h for k, (h, _) in d.items()}, {k: w for k, (_, w) in d.items()})
 
 
 # --------------------------------------------------------------------------------------------- host-array entry points
