@@ -558,6 +558,39 @@ int svae_hmm_ragged_viterbi_f64(int B, int T, int K, int pair_batched,
                                 int32_t* states, double* score /* or NULL */,
                                 int32_t* info, void* workspace, size_t ws_bytes, void* stream);
 
+/* svae_hmm_estep_f64 PARTITIONED IN TIME, for long sequences, K <= 16 -- csrc/hmm_estep_chunked.hip.  Additions to ABI 15
+ * (no new number).  The T steps are cut into C = ceil(T / chunk) chunks (the last may be as short as one step): stage 1
+ * builds every chunk's K x K transfer operator as K independently scaled rows, in parallel over (sequence, chunk, start
+ * state); stage 2 scans the C operators of a sequence for log Z and the messages at the chunk boundaries; stage 3 runs the
+ * scaled forward-backward of every chunk in parallel and sums the chunks' transition counts in chunk order (no
+ * floating-point atomics: the outputs are reproducible bit for bit).  Arguments and results are svae_hmm_estep_f64's.
+ *  chunk  : steps per chunk, >= 2.  chunk >= T runs svae_hmm_estep_f64's launches and nothing else (same bits).
+ *           svae_hmm_chunked_default_chunk(B,T,K) is the library's pick; it returns T where the serial route is expected
+ *           to win, and for arguments this entry refuses.
+ *  logZ only: E_init, E_trans and E_states all NULL -- stages 1 and 2 alone; a mix of NULL and non-NULL is refused.
+ *  Range  : the contract of svae_hmm_estep_f64.  A sequence keeps the chunked result only while every live component --
+ *           of every operator row from its chunk's second step on, of the first chunk's filter, of every weighted entry and
+ *           product of stage 2, of stage 3's forward messages -- stays >= 1e-250 of its scale and every normaliser above
+ *           1e-200.  Any other sequence is recomputed WHOLE by the serial route (an indexed launch over the flagged
+ *           sequences), whose own log-space redo stands behind it.  Which were is recorded: after the call with chunk < T
+ *           the workspace opens with B int32 route words, 1 = sequence b was recomputed by the serial route, else 0.
+ *  workspace: svae_hmm_chunked_workspace_bytes(B,T,K,chunk) = 8 B (1 + T (50 + K) + K K + K + C (2 K K + 3 K)) bytes,
+ *           C = ceil(T / chunk) (1 for chunk >= T): the route words and the recompute launch's slots, the serial route's
+ *           records (stage 3's alias them) and statistics (used for logZ only), the operators, their log scales, the
+ *           boundary messages and the chunks' counts (layout: csrc/hmm_args.hpp).  0 for B <= 0, T <= 0, K outside 1..16
+ *           or chunk < 2.  8-byte aligned.
+ *  Returns 0, or (decided on the host before any HIP call, the first failing check) -1 B < 0, -2 T < 1, -3 K outside
+ *  1..16, -4 pair_batched not 0 or 1, -5 init_params NULL, -6 pair_params NULL, [B = 0 returns 0 here], -7 chunk < 2,
+ *  -8 node_params NULL, -9 logZ NULL, -10 some but not all of E_init / E_trans / E_states NULL, -11 workspace NULL,
+ *  -12 ws_bytes too small; -1000 launch error.  Asynchronous on `stream`, no internal allocation, safe under graph
+ *  capture. */
+int svae_hmm_chunked_default_chunk(int B, int T, int K);
+size_t svae_hmm_chunked_workspace_bytes(int B, int T, int K, int chunk);
+int svae_hmm_chunked_estep_f64(int B, int T, int K, int pair_batched, int chunk,
+                               const double* init_params, const double* pair_params, const double* node_params,
+                               double* logZ, double* E_init /* or NULL */, double* E_trans /* or NULL */,
+                               double* E_states /* or NULL */, void* workspace, size_t ws_bytes, void* stream);
+
 /* Batched HMM posterior sampling: S state paths per chain, z_{0:T-1} ~ p(z | potentials), by forward filtering and
  * backward sampling, on the LOG potentials svae_hmm_viterbi_f64 takes (entries may be -inf), K <= SVAE_HMM_MAX_K --
  * csrc/hmm_sample.hip.  Additions to ABI 15 (no new number).  [pyhsmm's message interface, to which the reference

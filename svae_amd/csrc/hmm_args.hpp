@@ -59,4 +59,37 @@ constexpr int hmm_kp(int K) { return K <= 16 ? 16 : (K <= 32 ? 32 : 64); }
 constexpr int hmm_perstep_group(int K) { return K <= 8 ? 8 : K <= 16 ? 16 : K <= 32 ? 32 : 64; }
 constexpr int hmm_perstep_waves(int K) { return K <= 16 ? 1 : 4; }
 
+// time-chunked E-step (hmm_estep_chunked.hip; K <= HMM_CHUNKED_MAX_K, DPP rows): C = ceil(T / chunk) chunks per sequence,
+// stage-3 records of HMM_CHUNK_REC doubles per (sequence, step) = [alpha^_t (16) | e_t / c_t (16)].  The workspace, in
+// doubles (svae_hmm_chunked_workspace_bytes = 8 x total):
+//   route   B                  the route words (B int32: 1 = recomputed by the serial route), then the B int32 slots of the
+//                              indexed recompute launch
+//   serial  B T HMM_WS         the serial E-step's records (recompute, chunk >= T); stage 3's records alias their head
+//   stats   B (T K + K K + K)  E_states | E_trans | E_init of the serial route where the caller passes none (logZ only)
+//   ops     B C K K            chunk operators, rows renormalised (chunk 0: row 0 = its filtered message)
+//   scale   B C K              log scales of those rows
+//   ahat    B C K              filtered message at every chunk's last step
+//   bhat    B C K              backward message at every chunk's last step
+//   ctrans  B C K K            every chunk's own transition counts, its entering boundary term included
+constexpr int HMM_CHUNKED_MAX_K = 16;
+constexpr int HMM_CHUNK_REC = 32;
+static_assert(HMM_CHUNK_REC <= HMM_WS, "stage 3's records alias the serial records");
+struct HmmChunkedLayout {
+  long C, route, serial, stats, ops, scale, ahat, bhat, ctrans, total;      // offsets and total, in doubles
+};
+constexpr HmmChunkedLayout hmm_chunked_layout(long B, long T, long K, long chunk) {
+  HmmChunkedLayout l{};
+  l.C = chunk >= T ? 1 : (T + chunk - 1) / chunk;
+  l.route = 0;
+  l.serial = l.route + B;
+  l.stats = l.serial + B * T * HMM_WS;
+  l.ops = l.stats + B * (T * K + K * K + K);
+  l.scale = l.ops + B * l.C * K * K;
+  l.ahat = l.scale + B * l.C * K;
+  l.bhat = l.ahat + B * l.C * K;
+  l.ctrans = l.bhat + B * l.C * K;
+  l.total = l.ctrans + B * l.C * K * K;
+  return l;
+}
+
 }  // namespace svae

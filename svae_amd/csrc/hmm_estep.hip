@@ -918,6 +918,13 @@ extern "C" int svae_hmm_estep_f64(int B, int T, int K, int pair_batched,
   return svae::hmm_dispatch<false>(a, stream);
 }
 
+// The launches of svae_hmm_estep_f64 on arguments a sibling unit has checked and filled (hmm_estep_chunked.hip: the
+// indexed recompute of the sequences it flagged, with per-sequence pair parameters where the caller has them, and the
+// whole call where one chunk holds the sequence).
+extern "C" int svae_hmm_estep_args_launch(const svae::HmmArgs* a, void* stream) {
+  return svae::hmm_dispatch<false>(*a, stream);
+}
+
 // HMM step of the SLDS coordinate ascent (hmm_meanfield, /root/reference/svae/models/slds_svae.py:108-115) on the rows
 // `seq_index` lists, the node potentials taken from `node_params` (rows,T,K) if given, else built on the fly from the
 // fused LDS mean-field kernel's outputs (get_arhmm_local_nodeparams, :131-147).

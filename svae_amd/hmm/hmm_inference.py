@@ -3,6 +3,9 @@
   hmm_estep(natparam) -> (log_normalizer, (E_init, E_trans, E_states))      (:21-41)
   hmm_logZ(natparam)  -> log_normalizer                                      (:12-17, pyx:93-121)
   redone_sequences(workspace, B, T, K) -> which sequences of that E-step took the log-space route
+  hmm_estep_chunked(natparam, chunk) -> hmm_estep for LONG sequences, the steps cut into chunks worked on side by side;
+  hmm_logZ_chunked(natparam, chunk) its log-normaliser alone; chunked_redone_sequences(workspace, B, T, K, chunk) which
+                                 sequences the serial route recomputed; K <= 16 (csrc/hmm_estep_chunked.hip)
   hmm_viterbi(natparam) -> most probable state path (and its score)          (:54-63; csrc/hmm_viterbi.hip)
   hmm_sample(natparam, num_samples) -> state paths drawn from the posterior  (csrc/hmm_sample.hip)
   sample_redone_sequences(workspace, B, T, K) -> which sequences of that call had their filter redone in log space
@@ -217,6 +220,76 @@ def redone_sequences(workspace, B, T, K):
 
 def hmm_logZ(natparam, lengths=None):
     return hmm_estep(natparam, lengths=lengths)[0]
+
+
+# ---- the E-step partitioned in time (svae_hmm_chunked_estep_f64, csrc/hmm_estep_chunked.hip) -------------------------------
+HMM_CHUNKED_MAX_K = 16
+
+
+def _chunked_shapes(natparam, chunk):
+    """(B, T, K, batched, pair_batched, chunk) of a chunked call, from shapes alone (hmm_estep's refusals, then K > 16 and
+    a chunk that is no integer >= 2); chunk=None is resolved to the library's pick, which needs no device"""
+    B, T, K, batched, pair_batched = _shapes(natparam)
+    if K > HMM_CHUNKED_MAX_K:
+        raise ValueError("number of states K=%d above %d: the time-chunked E-step has DPP-row kernels only; use hmm_estep"
+                         % (K, HMM_CHUNKED_MAX_K))
+    if chunk is None:
+        chunk = max(2, int(_lib.load().svae_hmm_chunked_default_chunk(B, T, K)))
+    elif isinstance(chunk, bool) or not isinstance(chunk, (int, np.integer)) or chunk < 2:
+        raise ValueError("chunk must be an integer >= 2, got %r" % (chunk,))
+    return B, T, K, batched, pair_batched, int(min(chunk, 2 ** 31 - 1))
+
+
+def _chunked_call(natparam, chunk, workspace, want_stats):
+    B, T, K, batched, pair_batched, chunk = _chunked_shapes(natparam, chunk)
+    _, dev, leaves = _on_device(natparam, None)
+    lib, p = _lib.load(), _lib.ptr
+    ws, wsb = _workspace(workspace, lambda b, t, k: lib.svae_hmm_chunked_workspace_bytes(b, t, k, chunk), B, T, K, dev)
+    f64 = dict(dtype=torch.float64, device=dev)
+    logZ = torch.empty(B, **f64)
+    stats = (torch.empty(B, K, **f64), torch.empty(B, K, K, **f64), torch.empty(B, T, K, **f64)) if want_stats \
+        else (None, None, None)
+    _call("svae_hmm_chunked_estep_f64", dev, None, False, B, T, K, int(pair_batched), chunk, *map(p, leaves), p(logZ),
+          *map(p, stats), p(ws), wsb)
+    return _unbatch(batched, logZ, *stats)
+
+
+def hmm_estep_chunked(natparam, chunk=None, workspace=None):
+    """hmm_estep for LONG sequences: the T steps are cut into chunks of `chunk` steps that the chip works on side by side
+    (per chunk a K x K transfer operator, a scan over the chunks, then the E-step of every chunk; include/svae_hip.h,
+    svae_hmm_chunked_estep_f64), where hmm_estep runs one chain of T dependent steps per sequence whatever the batch.
+    natparam and the result (logZ, (E_init, E_trans, E_states)) are hmm_estep's -- (T,K) or (B,T,K) node potentials, a
+    shared or (B,K,K) pair parameter --, to rounding; K <= 16.  The range contract is hmm_estep's: a sequence that leaves
+    the range of the scaled chunked arithmetic is recomputed whole by hmm_estep's kernels, and
+    chunked_redone_sequences(workspace, B, T, K, chunk) says which were.
+    chunk: an integer >= 2; None takes svae_hmm_chunked_default_chunk(B, T, K); chunk >= T is hmm_estep, bit for bit.
+    workspace: a contiguous device tensor of at least svae_hmm_chunked_workspace_bytes(B, T, K, chunk) bytes."""
+    logZ, E_init, E_trans, E_states = _chunked_call(natparam, chunk, workspace, True)
+    return logZ, (E_init, E_trans, E_states)
+
+
+def hmm_logZ_chunked(natparam, chunk=None):
+    """The log-normaliser of hmm_estep_chunked alone, bit for bit: the chunk operators and the scan over them, without
+    the per-chunk E-step -- K forward filters over `chunk` steps and a scan over T / chunk operators."""
+    return _chunked_call(natparam, chunk, None, False)[0]
+
+
+def chunked_redone_sequences(workspace, B, T, K, chunk):
+    """Which sequences of the last hmm_estep_chunked call on `workspace` left the range of the chunked arithmetic and
+    were recomputed by the serial route: a (B,) bool tensor read from the B int32 route words the workspace opens with
+    (csrc/hmm_args.hpp).  The counterpart of redone_sequences; a call with chunk >= T is the serial route for every
+    sequence, writes no route word and reports none."""
+    if not (1 <= K <= HMM_CHUNKED_MAX_K):
+        raise ValueError("number of states K=%d outside 1..%d" % (K, HMM_CHUNKED_MAX_K))
+    if isinstance(chunk, bool) or not isinstance(chunk, (int, np.integer)) or chunk < 2:
+        raise ValueError("chunk must be an integer >= 2, got %r" % (chunk,))
+    ws = workspace.reshape(-1)
+    need = int(_lib.load().svae_hmm_chunked_workspace_bytes(max(B, 1), T, K, int(min(chunk, 2 ** 31 - 1))))
+    if ws.numel() * ws.element_size() < need:
+        raise ValueError("workspace is smaller than that of a (B=%d, T=%d, K=%d, chunk=%d) chunked E-step" % (B, T, K, chunk))
+    if chunk >= T:
+        return torch.zeros(B, dtype=torch.bool, device=ws.device)
+    return ws.view(torch.uint8)[:4 * B].view(torch.int32) != 0
 
 
 def hmm_viterbi(natparam, workspace=None, return_score=False, lengths=None, check=False):
