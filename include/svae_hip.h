@@ -591,6 +591,55 @@ int svae_hmm_chunked_estep_f64(int B, int T, int K, int pair_batched, int chunk,
                                double* logZ, double* E_init /* or NULL */, double* E_trans /* or NULL */,
                                double* E_states /* or NULL */, void* workspace, size_t ws_bytes, void* stream);
 
+/* svae_hmm_viterbi_f64 PARTITIONED IN TIME, for long sequences, K <= 16 -- csrc/hmm_viterbi_chunked.hip.  Additions to
+ * ABI 15 (no new number).  Arguments and results are svae_hmm_viterbi_f64's; there are no per-sequence lengths.
+ * The arithmetic, DEFINED here: fp64 adds and strict-`>` running maxima in the stated order, nothing else, so a restatement
+ * in the same order reproduces labels and score bit for bit.  L = chunk, C = ceil(T / L); chunk c covers steps
+ * t0 = c L .. t1 - 1, t1 = min((c + 1) L, T) (the last chunk may be one step).
+ *   step(d, t)[k] = (max_j (d[j] + pair[j][k])) + node[t][k], the running maximum in j order, the lowest j on ties
+ *   (the step of svae_hmm_viterbi_f64's recursion).
+ *  1 operators: for c >= 1, row j of M_c starts as pair[j][:] + node[t0][:] and takes `step` over t0+1 .. t1-1; chunk 0
+ *    is the recursion from delta_0 = init + node[0], its end vector D_0.  Parallel over (sequence, chunk, start state).
+ *  2 scan: D_c[k] = max_j (D_{c-1}[j] + M_c[j][k]), the running maximum in j order; serial over c, one row per sequence.
+ *  3 decode: chunk c enters with D_{c-1} (chunk 0 with init + node[0]) and runs `step` over its own steps (step t0 included
+ *    for c >= 1), keeping psi_t[k] = the lowest j attaining the maximum (psi_0 = 0).  The last chunk gives z_{T-1} = the
+ *    lowest k attaining the maximum of its final delta, and score = that maximum.  Then, for every end state k at once,
+ *    the path that ends the chunk in k is followed down to t0: cand[t][k] = its label at t, f_c[k] = psi_{t0}[cand[t0][k]]
+ *    = the end state of chunk c - 1 it arrives at.  Parallel over (sequence, chunk).
+ *  4 resolve: e_{C-1} = z_{T-1}; e_{c-1} = f_c[e_c].   5 gather: states[b,t] = cand[t][e_{c(t)}], c(t) = t / L.
+ * The serial call has chains of T and T steps; this one chains of L, C, L, L and C steps and one flat pass.
+ * Against svae_hmm_viterbi_f64:
+ *  (a) chunk >= T runs svae_hmm_viterbi_f64's launch and nothing else: the same bits.
+ *  (b) where every fp64 add of the recursion is exact (potentials that are multiples of 2^-q with
+ *      T max|potential| 2^q < 2^53, say; -inf entries included) max-plus is associative, D_{c-1} is the serial delta, and
+ *      labels and score equal svae_hmm_viterbi_f64's bit for bit, ties included.
+ *  (c) otherwise the boundary deltas differ from the serial ones in rounding: the labels are a path whose serially summed
+ *      score (((init + node_0) + pair) + node_1 ...) lies within 4 T 2^-53 A of svae_hmm_viterbi_f64's score, and so does
+ *      the returned score; A = max|init| + sum_t max_k |node_t| + (T - 1) max|pair| over the finite entries (the
+ *      first-order bound for <= 2 T roundings of partial sums no larger than A, doubled).
+ *  (d) NaN inputs: unspecified labels in 0..K-1, no fault, as for the serial entry.
+ *  (e) no atomics: the outputs are reproducible bit for bit.  Asynchronous on `stream`, no internal allocation, safe under
+ *      graph capture.
+ *  chunk  : steps per chunk, >= 2.  svae_hmm_chunked_viterbi_default_chunk(B,T,K) is the library's pick; it returns T
+ *           where the serial route is expected to win, and for arguments this entry refuses.
+ *  workspace: svae_hmm_chunked_viterbi_workspace_bytes(B,T,K,chunk) =
+ *           32 B T + 16 B C + 16 ceil(B C / 16) + 8 B C K (K + 1) bytes, C = ceil(T / chunk) (1 for chunk >= T): the
+ *           back-pointers (B T 16, at the head: never less than svae_hmm_viterbi_workspace_bytes(B,T,K), so route (a)
+ *           fits), the candidates (B T 16, a buffer of their own: they do not alias the back-pointers), the chunk maps f
+ *           (B C 16), the chunk end states e (B C bytes, padded to 16), the operators (B C K K doubles) and the boundary
+ *           deltas (B C K doubles) (layout: csrc/hmm_args.hpp).  0 for B <= 0, T <= 0, K outside 1..16 or chunk < 2.
+ *           16-byte aligned.
+ *  Returns 0, or (decided on the host before any HIP call, the first failing check) -1 B < 0, -2 T < 1, -3 K outside
+ *  1..16, -4 pair_batched not 0 or 1, -5 init_params NULL, -6 pair_params NULL, [B = 0 returns 0 here], -7 chunk < 2,
+ *  -8 node_params NULL, -9 states NULL, -10 workspace NULL, -11 ws_bytes too small, -12 workspace not 16-byte aligned;
+ *  -1000 launch error. */
+int svae_hmm_chunked_viterbi_default_chunk(int B, int T, int K);
+size_t svae_hmm_chunked_viterbi_workspace_bytes(int B, int T, int K, int chunk);
+int svae_hmm_chunked_viterbi_f64(int B, int T, int K, int pair_batched, int chunk,
+                                 const double* init_params, const double* pair_params, const double* node_params,
+                                 int32_t* states, double* score /* or NULL */,
+                                 void* workspace, size_t ws_bytes, void* stream);
+
 /* Batched HMM posterior sampling: S state paths per chain, z_{0:T-1} ~ p(z | potentials), by forward filtering and
  * backward sampling, on the LOG potentials svae_hmm_viterbi_f64 takes (entries may be -inf), K <= SVAE_HMM_MAX_K --
  * csrc/hmm_sample.hip.  Additions to ABI 15 (no new number).  [pyhsmm's message interface, to which the reference

@@ -92,4 +92,31 @@ constexpr HmmChunkedLayout hmm_chunked_layout(long B, long T, long K, long chunk
   return l;
 }
 
+// time-chunked Viterbi decoding (hmm_viterbi_chunked.hip; K <= HMM_CHUNKED_MAX_K, DPP rows): C = ceil(T / chunk) chunks
+// per sequence (1 for chunk >= T).  The workspace, in BYTES (svae_hmm_chunked_viterbi_workspace_bytes = total); every
+// offset is a multiple of 16:
+//   psi    B T 16             back-pointers, one byte per step and padded state -- the head of the workspace, where the
+//                             serial decoder keeps its own: the chunk >= T route (svae_hmm_viterbi_f64) fits
+//   cand   B T 16             candidate labels [b][t][k]: the label at t of the path that ends t's chunk in state k
+//                             (a buffer of its own: it does not alias psi)
+//   fmap   B C 16             f_c[k]: the end state of chunk c - 1 on the path that ends chunk c in state k
+//   ends   16 ceil(B C / 16)  e_c, one byte per chunk: the end state of chunk c on the decoded path
+//   ops    8 B C K K          max-plus chunk operators M_c (chunk 0's block is not used)
+//   delta  8 B C K            D_c, the recursion's value at every chunk's last step
+struct HmmChunkedViterbiLayout {
+  long C, psi, cand, fmap, ends, ops, delta, total;                         // offsets and total, in bytes
+};
+constexpr HmmChunkedViterbiLayout hmm_chunked_viterbi_layout(long B, long T, long K, long chunk) {
+  HmmChunkedViterbiLayout l{};
+  l.C = chunk >= T ? 1 : (T + chunk - 1) / chunk;
+  l.psi = 0;
+  l.cand = l.psi + B * T * 16;
+  l.fmap = l.cand + B * T * 16;
+  l.ends = l.fmap + B * l.C * 16;
+  l.ops = l.ends + (B * l.C + 15) / 16 * 16;
+  l.delta = l.ops + 8 * B * l.C * K * K;
+  l.total = l.delta + 8 * B * l.C * K;
+  return l;
+}
+
 }  // namespace svae

@@ -7,6 +7,8 @@
   hmm_logZ_chunked(natparam, chunk) its log-normaliser alone; chunked_redone_sequences(workspace, B, T, K, chunk) which
                                  sequences the serial route recomputed; K <= 16 (csrc/hmm_estep_chunked.hip)
   hmm_viterbi(natparam) -> most probable state path (and its score)          (:54-63; csrc/hmm_viterbi.hip)
+  hmm_viterbi_chunked(natparam, chunk) -> hmm_viterbi for LONG sequences, the steps cut into chunks decoded side by side;
+                                 K <= 16 (csrc/hmm_viterbi_chunked.hip)
   hmm_sample(natparam, num_samples) -> state paths drawn from the posterior  (csrc/hmm_sample.hip)
   sample_redone_sequences(workspace, B, T, K) -> which sequences of that call had their filter redone in log space
   hmm_estep_differentiable(natparam) -> hmm_estep's outputs, with gradients of all four to all three inputs
@@ -226,15 +228,16 @@ def hmm_logZ(natparam, lengths=None):
 HMM_CHUNKED_MAX_K = 16
 
 
-def _chunked_shapes(natparam, chunk):
+def _chunked_shapes(natparam, chunk, what="E-step", serial="hmm_estep", default="svae_hmm_chunked_default_chunk"):
     """(B, T, K, batched, pair_batched, chunk) of a chunked call, from shapes alone (hmm_estep's refusals, then K > 16 and
-    a chunk that is no integer >= 2); chunk=None is resolved to the library's pick, which needs no device"""
+    a chunk that is no integer >= 2); chunk=None is resolved to the library's pick, which needs no device.  what / serial /
+    default: the chunked unit's name, the serial function a K > 16 refusal points to, and the entry that picks the chunk"""
     B, T, K, batched, pair_batched = _shapes(natparam)
     if K > HMM_CHUNKED_MAX_K:
-        raise ValueError("number of states K=%d above %d: the time-chunked E-step has DPP-row kernels only; use hmm_estep"
-                         % (K, HMM_CHUNKED_MAX_K))
+        raise ValueError("number of states K=%d above %d: the time-chunked %s has DPP-row kernels only; use %s"
+                         % (K, HMM_CHUNKED_MAX_K, what, serial))
     if chunk is None:
-        chunk = max(2, int(_lib.load().svae_hmm_chunked_default_chunk(B, T, K)))
+        chunk = max(2, int(getattr(_lib.load(), default)(B, T, K)))
     elif isinstance(chunk, bool) or not isinstance(chunk, (int, np.integer)) or chunk < 2:
         raise ValueError("chunk must be an integer >= 2, got %r" % (chunk,))
     return B, T, K, batched, pair_batched, int(min(chunk, 2 ** 31 - 1))
@@ -311,6 +314,37 @@ def hmm_viterbi(natparam, workspace=None, return_score=False, lengths=None, chec
               p(ws), wsb)
     else:
         _call("svae_hmm_viterbi_f64", dev, None, False, *model, p(states), p(score), p(ws), wsb)
+    states, score = _unbatch(batched, states, score)
+    return (states, score) if return_score else states
+
+
+def hmm_viterbi_chunked(natparam, chunk=None, workspace=None, return_score=False):
+    """hmm_viterbi for LONG sequences: the T steps are cut into chunks of `chunk` steps that the chip works on side by side
+    (per chunk a K x K max-plus operator, a scan over the chunks for the recursion's value at every chunk boundary, then
+    every chunk decoded and chased from all K of its end states at once, the end states resolved across the chunks and the
+    labels gathered; include/svae_hip.h, svae_hmm_chunked_viterbi_f64), where hmm_viterbi runs one chain of T dependent
+    steps and a backtrace of T look-ups per sequence whatever the batch.  natparam and the result are hmm_viterbi's --
+    (T,K) or (B,T,K) node potentials, a shared or (B,K,K) pair parameter, entries finite or -inf; int32 labels (T,) or
+    (B,T), with return_score also the score --; K <= 16; there is no lengths=.
+    Against hmm_viterbi: (a) chunk >= T runs hmm_viterbi's launch and nothing else, the same bits; (b) where every fp64
+    add of the recursion is exact (potentials that are multiples of 2^-q with T max|potential| 2^q < 2^53, -inf included)
+    labels and score are hmm_viterbi's bit for bit, ties included; (c) otherwise the labels are a path whose serially
+    summed score lies within 4 T 2^-53 A of hmm_viterbi's score, and so does the returned score, A = max|init| +
+    sum_t max_k |node_t| + (T-1) max|pair| over the finite entries; (d) NaN inputs give unspecified labels in 0..K-1 and no
+    fault; (e) the outputs are reproducible bit for bit (no atomics), the call is asynchronous, allocates nothing inside
+    the library and is safe under graph capture.
+    chunk: an integer >= 2; None takes svae_hmm_chunked_viterbi_default_chunk(B, T, K).
+    workspace: a contiguous, 16-byte aligned device tensor of at least svae_hmm_chunked_viterbi_workspace_bytes(B, T, K,
+    chunk) bytes."""
+    B, T, K, batched, pair_batched, chunk = _chunked_shapes(natparam, chunk, "Viterbi decoder", "hmm_viterbi",
+                                                            "svae_hmm_chunked_viterbi_default_chunk")
+    _, dev, leaves = _on_device(natparam, None)
+    lib, p = _lib.load(), _lib.ptr
+    ws, wsb = _workspace(workspace, lambda b, t, k: lib.svae_hmm_chunked_viterbi_workspace_bytes(b, t, k, chunk), B, T, K, dev)
+    states = torch.empty(B, T, dtype=torch.int32, device=dev)
+    score = torch.empty(B, dtype=torch.float64, device=dev) if return_score else None
+    _call("svae_hmm_chunked_viterbi_f64", dev, None, False, B, T, K, int(pair_batched), chunk, *map(p, leaves), p(states),
+          p(score), p(ws), wsb)
     states, score = _unbatch(batched, states, score)
     return (states, score) if return_score else states
 
