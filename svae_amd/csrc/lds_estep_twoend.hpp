@@ -34,6 +34,11 @@
 #include "gj1r_gen.hpp"
 #include "lds_estep_twoend_s4.hpp"
 
+// 1: the S4 kernel issues the loads of local step 0's node potentials with its prologue's batch of parameter loads.
+// 0: behind the prologue's set-up, in front of the elimination loop (the A/B build; the same bytes).
+#ifndef SVAE_TE_EARLY_NODE
+#define SVAE_TE_EARLY_NODE 1
+#endif
 #ifndef SVAE_TE_LDS_SPLIT
 #define SVAE_TE_LDS_SPLIT 3     // bit 0: kernels without the cross-moment store, bit 1: CROSS (runs next to the filter kernel)
 #endif
@@ -439,7 +444,24 @@ __device__ __forceinline__ void lds_estep_twoend_body(const LdsArgs& a, const in
   // the other, were most of this wavefront's prologue.  Every index is valid in every lane.
   struct Pre { double x[N], c[N], c22[J], c11[J], ij[N], ih[N], j11[N]; };
   [[maybe_unused]] Pre pre;
+  // node potentials of local step s: global node t = s (A) / T-1-s (B); lanes >= N read element 0
+  auto node_off = [&](int s) -> long { return (long)(dir ? T - 1 - s : s) * N; };
+  // (the elimination loop's walk over them: see there)
+  const char* const nJu = reinterpret_cast<const char*>(a.node_J + (long)b * T * N);
+  const char* const nhu = reinterpret_cast<const char*>(a.node_h + (long)b * T * N);
+  unsigned noff = 8u * (unsigned)(node_off(0) + cc);
+  const unsigned nstep = dir ? 0u - 8u * N : 8u * N;
+  auto node_load = [&](double& Jo, double& ho) {
+    asm volatile("" : "+v"(noff));
+    Jo = *reinterpret_cast<const double*>(nJu + noff);
+    ho = *reinterpret_cast<const double*>(nhu + noff);
+  };
+  double Jo_n, ho_n;
+  // S4: local step 0's node potentials travel with that batch -- they need only the lane's offset -- instead of paying a
+  // cold round trip of their own behind the prologue's set-up
+  constexpr bool TE_EARLY_NODE = S4 && (SVAE_TE_EARLY_NODE);
   if constexpr (S4) {
+    if constexpr (TE_EARLY_NODE) node_load(Jo_n, ho_n);
     static_for<0, N>([&](auto i) {
       pre.x[i] = q12[i * si + xx * sc];
       pre.c[i] = q12[i * si + cc * sc];
@@ -578,9 +600,6 @@ __device__ __forceinline__ void lds_estep_twoend_body(const LdsArgs& a, const in
     });
   }
 
-  // node potentials of local step s: global node t = s (A) / T-1-s (B); lanes >= N read element 0
-  auto node_off = [&](int s) -> long { return (long)(dir ? T - 1 - s : s) * N; };
-
   // chain workspace: constant page [e_N (N+2) | zeros (N+2) | trash (2)], then the records
   double* wsb = a.ws + (long)b * te_seq_doubles(N, T);            // uniform: this sequence's two chains
   const unsigned choff = (unsigned)(dir * te_chain_doubles(N, T)) + ZP;   // per lane: its chain's records
@@ -626,17 +645,8 @@ __device__ __forceinline__ void lds_estep_twoend_body(const LdsArgs& a, const in
   // (walking per-lane pointers: recomputing node_off(s + 1) per step was two 64-bit multiply-adds and three selects)
   // (... and the pointers five 64-bit adds per step: the sequence's base is uniform, so the walk is ONE 32-bit add of
   //  the lane's byte offset -- kept out of hipcc's sight by an empty asm like the hand-off's, see hand_off below)
-  const char* const nJu = reinterpret_cast<const char*>(a.node_J + (long)b * T * N);
-  const char* const nhu = reinterpret_cast<const char*>(a.node_h + (long)b * T * N);
-  unsigned noff = 8u * (unsigned)(node_off(0) + cc);
-  const unsigned nstep = dir ? 0u - 8u * N : 8u * N;
-  auto node_load = [&](double& Jo, double& ho) {
-    asm volatile("" : "+v"(noff));
-    Jo = *reinterpret_cast<const double*>(nJu + noff);
-    ho = *reinterpret_cast<const double*>(nhu + noff);
-  };
-  double Jo_n, ho_n;
-  node_load(Jo_n, ho_n);
+  // (S4: the first pair is issued with the prologue's batch of parameter loads, see `pre` above)
+  if constexpr (!TE_EARLY_NODE) node_load(Jo_n, ho_n);
   const double jm2 = col ? -2.0 : 0.0, jadd = col ? 0.0 : 1.0;      // JoX = col ? -2 Jo : 1 as ONE multiply-add
   double Mp[N];             // partner chain's An at the hand-over point
   static_for<0, N>([&](auto i) { Mp[i] = 0.0; });

@@ -7,7 +7,7 @@ OUT=$(realpath -m "$1"); UNIT=$2; shift 2
 cd "$(dirname "$0")/../svae_amd/csrc"
 TMP=$(mktemp -d)
 /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC "$@" -c $UNIT.hip -o $TMP/u.o
-OBJS=$(ls build/*.o | grep -v "build/$UNIT.o" | grep -v sgb5)
+OBJS=$(ls build/*.o | grep -v "build/$UNIT.o" | grep -v sgb5 | grep -v s4ref)
 mkdir -p "$(dirname "$OUT")"
 /opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC $OBJS $TMP/u.o -o "$OUT"
 rm -rf $TMP

@@ -6,7 +6,7 @@ OUT=$(realpath -m "$1"); N=$2; shift 2
 cd "$(dirname "$0")/../svae_amd/csrc"
 TMP=$(mktemp -d)
 /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC "$@" -DSVAE_N=$N -c lds_vjp_n.hip -o $TMP/v.o
-OBJS=$(ls build/*.o | grep -v "lds_vjp_n$N.o" | grep -v sgb5)
+OBJS=$(ls build/*.o | grep -v "lds_vjp_n$N.o" | grep -v sgb5 | grep -v s4ref)
 mkdir -p "$(dirname "$OUT")"
 /opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC $OBJS $TMP/v.o -o "$OUT"
 rm -rf $TMP
