@@ -5,6 +5,15 @@ svae/lds/lds_inference.py:86-178) and the fp64 kernels differ by more than round
 the same model evaluated with ~3 more decimal digits tells which of the two carries the error.
 Plain NumPy on np.longdouble arrays (no LAPACK: Gauss-Jordan inverse with vectorised row updates),
 moment-form smoother; homogeneous or per-step pair parameters, diagonal node potentials.
+
+RANGE.  It is an arbiter up to cond(J22) ~ 1e6 (measured against the 50-digit oracle/lds_mp.py on rand_lds_natparam
+draws, n = 17 .. 128: 1e-14 or better there, except 5e-12 on the two draws whose INIT block has cond(J0) ~ 1e8 --
+cond(J22) does not see the init potential, and c = P^-1 h is formed with the explicit inverse).  Beyond that the
+moment-form recursion on an unpivoted Gauss-Jordan inverse loses more than the three digits long double adds: from cond(J22) ~ 1e7 on it is FURTHER from the truth than
+the fp64 restatement it would arbitrate (n = 17, cond 5.5e9: 1.4e-4 against 1.4e-8; n = 64, cond 4.0e10: 5.9e-4 against
+2.7e-8; tests/test_lds_mfma_truth_cpu.py records it on every truth fixture, DESIGN section 2 has the table).  No test may
+use it as the arbiter on a draw with cond(J22) above 1e6: there the truth is oracle/lds_mp.py, precomputed into
+tests/golden/ where it is too slow to run in a test.
 """
 import numpy as np
 

@@ -295,6 +295,21 @@ def sample_on_messages_mp(forward_messages, pair_params, eps, dps=DPS, as_float=
         return _f64(out) if as_float else out
 
 
+def inference_mp(natparam, node_params, eps, dps=DPS, as_float=True):
+    """the training forward (E-step + sampler on the filter's messages) in `dps` digits ->
+    (lognorm, (diag E[xx'] (T,n), E[x] (T,n)), samples (T,S,n)): estep_mp, and sample_on_messages_mp on filter_mp's
+    messages with the noise eps (T,S,n).  jvp_mp accepts it: the directional derivative of
+        L = g_l lognorm + <g_d, diag E[xx']> + <g_x, E[x]> + <g_s, samples>
+    is that combination of jvp_mp(inference_mp, (natparam, node_params, eps), direction)'s leaves."""
+    with _digits(dps):
+        init, pair = natparam
+        lognorm, (_, _, E_node) = estep_mp(natparam, node_params, dps=dps, as_float=False)
+        messages, _ = filter_mp(init, pair, node_params, dps=dps, as_float=False)
+        samples = sample_on_messages_mp(messages, pair, eps, dps=dps, as_float=False)
+        out = (lognorm, (E_node[0], E_node[1]), samples)
+        return _f64(out) if as_float else out
+
+
 def _axpy(x, v, s):
     """x + s v over matching nested structures (v None / 0 = no perturbation of that leaf); x's leaves become mp arrays"""
     if isinstance(x, (tuple, list)):
