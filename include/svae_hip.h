@@ -711,6 +711,69 @@ int svae_hmm_ragged_sample_f64(int B, int T, int K, int S, int pair_batched,
                                int32_t* states, double* logZ /* or NULL */,
                                int32_t* info, void* workspace, size_t ws_bytes, void* stream);
 
+/* svae_hmm_sample_f64 PARTITIONED IN TIME, for long sequences, K <= 16 -- csrc/hmm_sample_chunked.hip.  Additions to
+ * ABI 15 (no new number).  Arguments and results are svae_hmm_sample_f64's (u (B,S,T), states (B,S,T) int32 sample-major,
+ * potentials finite or -inf, logZ (B) or NULL); there are no per-sequence lengths.  With the uniforms fixed, the backward
+ * draw at step t is a MAP from z_{t+1} to z_t, like a Viterbi back-pointer.  The arithmetic, DEFINED here: L = chunk,
+ * C = ceil(T / L); chunk c covers steps t0 = c L .. t1 - 1, t1 = min((c + 1) L, T) (the last chunk may be one step).
+ *  1 operators, 2 forward scan: stages 1 and 2 of svae_hmm_chunked_estep_f64 in its log-Z-only form, by that unit's own
+ *    kernels.  They give the filtered message a^_c at every chunk's last step, log Z -- svae_hmm_chunked_estep_f64's bit
+ *    for bit at the same chunk -- and that call's range flags for these stages.
+ *  3 filter: chunk c runs the scaled step of svae_hmm_sample_f64's filter over its own steps, entered with a^_{c-1} in
+ *    place of the initial message (chunk 0: from `init`), and stores a_t, 16 doubles per step, padding lanes 0, under the
+ *    same per-step range test (live component >= 1e-250, normaliser > 1e-200, a NaN fails).  Parallel over (sequence, chunk).
+ *  4 maps: for every chain (b, s) and step t >= 1, psi_t[k] = the state drawn at t - 1 given z_t = k, for all K values of
+ *    k, from the record a_{t-1}, column k of the matrix and u[b,s,t-1]; z_{T-1} is drawn from a_{T-1} with u[b,s,T-1].
+ *    Weights and selection are exactly svae_hmm_sample_f64's (above): w[j] = a[j] exp(pair[j][k] - M) a rounded product
+ *    (not contracted into the sum), C summed in index order, thr = clamp(u) C[K-1] (a NaN u counts as 0),
+ *    z = #{j : C[j] <= thr and C[j] < C[K-1]}; the log-space recompute where the total is below 1e-200, and the log-space
+ *    weights at every step of a sequence whose record is a log record (no live entry > 0 in its record of step T-1).
+ *    One uniform serves all K conditioning states: a valid coupling, and only the entry on the realised path reaches the
+ *    output, so the labels are those of svae_hmm_sample_f64's draw run on the same records.  Flat over (chain, step).
+ *  5 chase: for every end state k of chunk c at once the maps are followed down to t0: cand[t][k] = the label at t of the
+ *    path that ends the chunk in k, f_c[k] = psi_{t0}[cand[t0][k]].  Parallel over (chain, chunk).
+ *  6 resolve: e_{C-1} = z_{T-1}; e_{c-1} = f_c[e_c].   7 gather: states[b,s,t] = cand[t][e_{c(t)}], c(t) = t / L -- the
+ *    chunked Viterbi decoder's kernels, on B S chains.
+ * The serial call has chains of T and T steps; this one chains of L, C, L, L and C steps and two flat passes.
+ * RANGE: svae_hmm_sample_f64's contract, whole.  A sequence flagged in any of stages 1 - 3 raises an int32 route word in the
+ * workspace (zeroed by a memset node at the start of the call); a small kernel writes -1 into the live lanes of its step-0
+ * record; the log-space filter launch of svae_hmm_sample_f64 then replaces all of its records and its log Z (its workgroups
+ * leave at once elsewhere), and stage 4 draws every step of it with the log-space weights.  So every sequence with finite
+ * log Z has the paths of the log-space definition to rounding.  A flagged sequence costs one serial log-space filter of T
+ * steps, K log-sum-exps of 16 terms each (an operation-count estimate; it has not been timed).  Afterwards "no live entry
+ * > 0 in the step-0 record" tells which sequences were redone, as for the serial call.
+ * Against svae_hmm_sample_f64: chunk >= T runs svae_hmm_sample_f64 on the head of the workspace and nothing else: the same
+ * bits.  Otherwise the records differ from the serial filter's in rounding (the boundary messages come from the scan), so
+ * a draw whose uniform lies within that rounding of a boundary of the cumulative weights may differ.  NaN potentials or a
+ * chain with log Z = -inf: unspecified labels in 0..K-1, no fault, no effect on other sequences.  No atomics: the outputs
+ * are reproducible bit for bit.  Asynchronous on `stream`, no internal allocation, safe under graph capture.
+ *  chunk  : steps per chunk, >= 2.  svae_hmm_chunked_sample_default_chunk(B,T,K,S) is the library's pick: the chunked
+ *           E-step's rule applied to B -- T (the serial route) for T < 500 or B > 128, else the power of two nearest
+ *           1.2 sqrt(T).  Derived from the table of DESIGN 4.5m (tools/bench_hmm_sample_chunked.py, one MI355X, K = 8 and
+ *           16, S = 1 and 8): chunked beat the serial call at every measured shape with T >= 500 and B <= 128 (1.9x - 5x at
+ *           T = 500, 2.7x - 25x at T = 5000, 10x - 93x at T = 50000), the rule's pick within 3.2 % of the best measured
+ *           chunk; at 512 x 500 it lost at K = 16.  T < 500 and 129 .. 511 sequences were not measured: serial.  It
+ *           returns T for arguments this entry refuses.
+ *  workspace: svae_hmm_chunked_sample_workspace_bytes(B,T,K,S,chunk) = 128 B T + r16(8 B) + r16(4 B) + r16(8 B C K K) +
+ *           2 r16(8 B C K) + 32 R T + 16 R C + r16(R C) bytes, R = B S, C = ceil(T / chunk) (1 for chunk >= T), r16(x) = x
+ *           rounded up to a multiple of 16: the records (B T 16 doubles AT THE HEAD, svae_hmm_sample_f64's layout: never
+ *           less than svae_hmm_sample_workspace_bytes(B,T,K), so the chunk >= T route fits), log Z where the caller passes
+ *           none, the route words, the operators, their log scales, the boundary messages a^, the maps (R T 16 bytes), the
+ *           candidates (R T 16, a buffer of their own: they do not alias the maps), the chunk maps f (R C 16) and the chunk
+ *           end states e (R C bytes) (layout: csrc/hmm_args.hpp).  0 for B <= 0, T <= 0, K outside 1..16, S <= 0 or
+ *           chunk < 2.  16-byte aligned.
+ *  Returns 0, or (decided on the host before any HIP call, the first failing check) -1 B < 0, -2 T < 1, -3 K outside
+ *  1..16, -4 pair_batched not 0 or 1, -5 init_params NULL, -6 pair_params NULL, [B = 0 returns 0 here], -7 chunk < 2,
+ *  -8 node_params NULL, -9 S < 1, -10 B S T not below 2^31, -11 u NULL, -12 states NULL, -13 workspace NULL, -14 ws_bytes
+ *  too small, -15 workspace not 16-byte aligned; -1000 launch error. */
+int svae_hmm_chunked_sample_default_chunk(int B, int T, int K, int S);
+size_t svae_hmm_chunked_sample_workspace_bytes(int B, int T, int K, int S, int chunk);
+int svae_hmm_chunked_sample_f64(int B, int T, int K, int S, int pair_batched, int chunk,
+                                const double* init_params, const double* pair_params,
+                                const double* node_params, const double* u,
+                                int32_t* states, double* logZ /* or NULL */,
+                                void* workspace, size_t ws_bytes, void* stream);
+
 /* Reverse-mode derivative of the batched HMM E-step (svae_hmm_estep_f64 / svae_hmm_ragged_estep_f64), K <=
  * SVAE_HMM_MAX_K -- csrc/hmm_estep_vjp.hip, which states the arithmetic.  Additions to ABI 15 (no new number).  The
  * cotangents of all four outputs are pulled back to all three inputs: with phi(z) = g_init[z_0] + sum_t g_trans[z_t,

@@ -92,6 +92,11 @@ SIGNATURES = {
     "svae_hmm_chunked_viterbi_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int] * 4),
     "svae_hmm_chunked_viterbi_f64": (ctypes.c_int, [ctypes.c_int] * 5 + [_c_double_p] * 3 + [_c_int_p, _c_double_p]
                                      + [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]),
+    # posterior sampling partitioned in time (1 <= K <= 16)
+    "svae_hmm_chunked_sample_default_chunk": (ctypes.c_int, [ctypes.c_int] * 4),
+    "svae_hmm_chunked_sample_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int] * 5),
+    "svae_hmm_chunked_sample_f64": (ctypes.c_int, [ctypes.c_int] * 6 + [_c_double_p] * 4 + [_c_int_p, _c_double_p]
+                                    + [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]),
     # posterior sampling (forward filter, backward draw; 1 <= K <= 64)
     "svae_hmm_sample_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int] * 3),
     "svae_hmm_sample_f64": (ctypes.c_int, [ctypes.c_int] * 5 + [_c_double_p] * 4 + [_c_int_p, _c_double_p]

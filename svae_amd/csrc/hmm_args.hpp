@@ -119,4 +119,41 @@ constexpr HmmChunkedViterbiLayout hmm_chunked_viterbi_layout(long B, long T, lon
   return l;
 }
 
+// time-chunked posterior sampling (hmm_sample_chunked.hip; K <= HMM_CHUNKED_MAX_K, DPP rows): C = ceil(T / chunk) chunks
+// per sequence (1 for chunk >= T), R = B S chains.  The workspace, in BYTES (svae_hmm_chunked_sample_workspace_bytes =
+// total); every offset is a multiple of 16, r16(x) = x rounded up to one:
+//   rec    128 B T            the serial sampler's records a_t (16 doubles per step; a redone sequence: log a_t) -- the
+//                             head of the workspace, where svae_hmm_sample_f64 keeps its own: the chunk >= T route fits
+//                             and sample_redone_sequences reads a chunked workspace unchanged
+//   lz     r16(8 B)           log Z where the caller passes none
+//   route  r16(4 B)           the route words (int32: 1 = left the range of stages 1 - 3, filtered again in log space)
+//   ops    r16(8 B C K K)     chunk operators of the chunked E-step's stage 1
+//   scale  r16(8 B C K)       their rows' log scales
+//   ahat   r16(8 B C K)       filtered message at every chunk's last step
+//   maps   16 R T             state maps psi_t[k], one byte per step and padded state
+//   cand   16 R T             candidate labels [r][t][k] (a buffer of its own: it does not alias the maps)
+//   fmap   16 R C             f_c[k]: the end state of chunk c - 1 on the path that ends chunk c in state k
+//   ends   r16(R C)           e_c, one byte per chunk
+struct HmmChunkedSampleLayout {
+  long C, rec, lz, route, ops, scale, ahat, maps, cand, fmap, ends, total;  // offsets and total, in bytes
+};
+constexpr long hmm_r16(long x) { return (x + 15) / 16 * 16; }
+constexpr HmmChunkedSampleLayout hmm_chunked_sample_layout(long B, long T, long K, long S, long chunk) {
+  HmmChunkedSampleLayout l{};
+  const long R = B * S;
+  l.C = chunk >= T ? 1 : (T + chunk - 1) / chunk;
+  l.rec = 0;
+  l.lz = l.rec + 128 * B * T;
+  l.route = l.lz + hmm_r16(8 * B);
+  l.ops = l.route + hmm_r16(4 * B);
+  l.scale = l.ops + hmm_r16(8 * B * l.C * K * K);
+  l.ahat = l.scale + hmm_r16(8 * B * l.C * K);
+  l.maps = l.ahat + hmm_r16(8 * B * l.C * K);
+  l.cand = l.maps + 16 * R * T;
+  l.fmap = l.cand + 16 * R * T;
+  l.ends = l.fmap + 16 * R * l.C;
+  l.total = l.ends + hmm_r16(R * l.C);
+  return l;
+}
+
 }  // namespace svae

@@ -438,6 +438,31 @@ static int launch_chunked(const HmmChunkedArgs& a, hipStream_t s) {
 
 }  // namespace svae
 
+// Stages 1 and 2 alone -- chunk operators and the forward boundary scan, the log-Z-only form -- on a caller's buffers
+// (hmm_sample_chunked.hip): logZ, ahat and the route words as svae_hmm_chunked_estep_f64 leaves them at this chunk.  The
+// route words are the caller's to zero; no recompute launch follows.  Host only: the kernels are the ones above.
+extern "C" int svae_hmm_chunked_forward_launch(int B, int T, int K, int L, int C, long pair_stride,
+                                               const double* init_params, const double* pair_params,
+                                               const double* node_params, double* logZ, int32_t* route, double* ops,
+                                               double* scale, double* ahat, void* stream) {
+  svae::HmmChunkedArgs a;
+  svae::hmm_set_model(a, B, T, K, pair_stride, init_params, pair_params, node_params);
+  a.L = L; a.C = C;
+  a.logZ = logZ; a.E_init = nullptr; a.E_trans = nullptr; a.E_states = nullptr;
+  a.route = route; a.index = nullptr; a.rec = nullptr;
+  a.ops = ops; a.scale = scale; a.ahat = ahat; a.bhat = nullptr; a.ctrans = nullptr;
+  hipStream_t s = (hipStream_t)stream;
+  return svae::hmm_dispatch_k(
+      K,
+      [&](auto k) {
+        const long op_rows = (long)a.B * a.C * k;
+        hipLaunchKernelGGL((svae::hmm_chunk_ops_kernel<k>), dim3((unsigned)((op_rows + 3) / 4)), dim3(64), 0, s, a);
+        hipLaunchKernelGGL((svae::hmm_chunk_scan_kernel<k>), dim3((unsigned)((a.B + 3) / 4)), dim3(64), 0, s, a);
+        return hipGetLastError() == hipSuccess ? 0 : -1000;
+      },
+      [&](auto) { return -3; });
+}
+
 // The chunk the library picks, from tools/bench_hmm_chunked.py on one MI355X (K = 8 and 16; DESIGN 4.5k has the table).
 // Chunked beat the serial call, by far more than the windows' spread (<= 5 %), at every measured shape with T >= 500 and
 // B <= 128 -- 1.3x - 1.8x at T = 500, 3x - 7x at T = 5000, 8x - 24x at T = 50000 -- and lost at 512 x 500 (and, at

@@ -302,6 +302,20 @@ static int launch_viterbi_chunked(const ViterbiChunkedArgs& a, hipStream_t s) {
 
 }  // namespace svae
 
+// Stages 4 and 5 alone -- resolve and gather -- on R chains of T steps whose candidates, chunk maps and last end states
+// (ends[r][C-1]) the caller has filled (hmm_sample_chunked.hip: R = B S).  Host only: the kernels are the ones above.
+extern "C" int svae_hmm_vchunk_resolve_gather_launch(int R, int T, int L, int C, int32_t* states, uint8_t* cand,
+                                                     uint8_t* fmap, uint8_t* ends, void* stream) {
+  svae::ViterbiChunkedArgs a{};
+  a.B = R; a.T = T; a.L = L; a.C = C;
+  a.states = states; a.cand = cand; a.fmap = fmap; a.ends = ends;
+  hipStream_t s = (hipStream_t)stream;
+  const long steps = (long)R * T;
+  hipLaunchKernelGGL(svae::hmm_vchunk_resolve_kernel, dim3((unsigned)((R + 63) / 64)), dim3(64), 0, s, a);
+  hipLaunchKernelGGL(svae::hmm_vchunk_gather_kernel, dim3((unsigned)((steps + 255) / 256)), dim3(256), 0, s, a);
+  return hipGetLastError() == hipSuccess ? 0 : -1000;
+}
+
 // The chunk the library picks, from tools/bench_hmm_viterbi_chunked.py on one MI355X (K = 8 and 16; DESIGN 4.5l has the
 // table).  It started as the chunked E-step's rule (the stage structure is the same) and the measurement kept its core:
 // the fastest chunk was 32 / 64 / 256 at T = 500 / 5000 / 50000 for both K up to 32 sequences (at 32 x 5000 chunk 128 was

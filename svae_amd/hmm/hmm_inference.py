@@ -231,13 +231,15 @@ HMM_CHUNKED_MAX_K = 16
 def _chunked_shapes(natparam, chunk, what="E-step", serial="hmm_estep", default="svae_hmm_chunked_default_chunk"):
     """(B, T, K, batched, pair_batched, chunk) of a chunked call, from shapes alone (hmm_estep's refusals, then K > 16 and
     a chunk that is no integer >= 2); chunk=None is resolved to the library's pick, which needs no device.  what / serial /
-    default: the chunked unit's name, the serial function a K > 16 refusal points to, and the entry that picks the chunk"""
+    default: the chunked unit's name, the serial function a K > 16 refusal points to, and the entry that picks the chunk
+    (its name, or a callable of (B, T, K))"""
     B, T, K, batched, pair_batched = _shapes(natparam)
     if K > HMM_CHUNKED_MAX_K:
         raise ValueError("number of states K=%d above %d: the time-chunked %s has DPP-row kernels only; use %s"
                          % (K, HMM_CHUNKED_MAX_K, what, serial))
     if chunk is None:
-        chunk = max(2, int(getattr(_lib.load(), default)(B, T, K)))
+        pick = default if callable(default) else getattr(_lib.load(), default)
+        chunk = max(2, int(pick(B, T, K)))
     elif isinstance(chunk, bool) or not isinstance(chunk, (int, np.integer)) or chunk < 2:
         raise ValueError("chunk must be an integer >= 2, got %r" % (chunk,))
     return B, T, K, batched, pair_batched, int(min(chunk, 2 ** 31 - 1))
@@ -379,11 +381,48 @@ def hmm_sample(natparam, num_samples=1, u=None, generator=None, workspace=None, 
     return (states, logZ) if return_logZ else states
 
 
+def hmm_sample_chunked(natparam, num_samples=1, u=None, generator=None, chunk=None, workspace=None, return_logZ=False):
+    """hmm_sample for LONG sequences: the T steps are cut into chunks of `chunk` steps that the chip works on side by side
+    (the chunked E-step's operators and forward scan for the filtered message at every chunk boundary, every chunk
+    filtered from there, then -- the uniforms being fixed -- every backward draw as a map from the next state to this one,
+    chased, resolved and gathered as the chunked Viterbi decoder does its back-pointers; include/svae_hip.h,
+    svae_hmm_chunked_sample_f64), where hmm_sample runs a filter of T and a draw of T dependent steps per chain whatever
+    the batch.  natparam and the result are hmm_sample's -- (T,K) or (B,T,K) node potentials, a shared or (B,K,K) pair
+    parameter, entries finite or -inf; int32 labels (S,T) or (B,S,T), with return_logZ also the log-normaliser, which is
+    hmm_logZ_chunked's bit for bit at the same chunk --; K <= 16; there is no lengths=.
+    The weights and the selection rule are hmm_sample's, on filtered distributions that differ from its own in rounding;
+    chunk >= T runs hmm_sample's launches and nothing else, the same bits.  The range contract is hmm_sample's: a sequence
+    that leaves the range of the scaled chunked arithmetic is filtered again, all of it, in log space and drawn with the
+    log-space weights, and sample_redone_sequences(workspace, B, T, K) says which were (it reads this call's workspace
+    unchanged).  NaN potentials give unspecified labels in 0..K-1 and no fault.  The outputs are reproducible bit for bit
+    (no atomics); the call is asynchronous, allocates nothing inside the library and is safe under graph capture.
+    u: the uniforms, (B,S,T) ((S,T) for the unbatched call); None draws torch.rand fp64 on the device with `generator`.
+    chunk: an integer >= 2; None takes svae_hmm_chunked_sample_default_chunk(B, T, K, S).
+    workspace: a contiguous, 16-byte aligned device tensor of at least svae_hmm_chunked_sample_workspace_bytes(B, T, K, S,
+    chunk) bytes."""
+    B, T, K, batched, pair_batched = _shapes(natparam)
+    S = _sample_shapes(num_samples, u, B, T, batched)
+    B, T, K, batched, pair_batched, chunk = _chunked_shapes(
+        natparam, chunk, "sampler", "hmm_sample", lambda b, t, k: _lib.load().svae_hmm_chunked_sample_default_chunk(b, t, k, S))
+    _, dev, leaves = _on_device(natparam, None)
+    u = _uniforms(u, generator, B, S, T, dev)
+    lib, p = _lib.load(), _lib.ptr
+    ws, wsb = _workspace(workspace, lambda b, t, k: lib.svae_hmm_chunked_sample_workspace_bytes(b, t, k, S, chunk), B, T, K, dev)
+    states = torch.empty(B, S, T, dtype=torch.int32, device=dev)
+    logZ = torch.empty(B, dtype=torch.float64, device=dev) if return_logZ else None
+    _call("svae_hmm_chunked_sample_f64", dev, None, False, B, T, K, S, int(pair_batched), chunk, *map(p, leaves), p(u),
+          p(states), p(logZ), p(ws), wsb)
+    states, logZ = _unbatch(batched, states, logZ)
+    return (states, logZ) if return_logZ else states
+
+
 def sample_redone_sequences(workspace, B, T, K):
     """Which sequences of the last hmm_sample call on `workspace` left the range of the scaled filter and were filtered
     again in log space: a (B,) bool tensor read from the records themselves (csrc/hmm_sample_kernel.hpp: B T KP doubles,
     KP = 16, 32 or 64; a scaled record a_t sums to 1 and so has a positive entry, a log-space record log a_t has none).
-    The counterpart of redone_sequences for the sampler; with lengths= every sequence has its step-0 record."""
+    The counterpart of redone_sequences for the sampler; with lengths= every sequence has its step-0 record.
+    It reads the workspace of an hmm_sample_chunked call unchanged: that call keeps the same records at the head of its
+    workspace, and a sequence that left the range of its chunked stages is filtered again in log space in the same way."""
     if not (1 <= K <= HMM_MAX_K):
         raise ValueError("number of states K=%d outside 1..%d" % (K, HMM_MAX_K))
     kp = 16 if K <= 16 else (32 if K <= 32 else 64)
